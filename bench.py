@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the ARC-NVFP4 GEMM benchmark of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,9 +15,13 @@ the timed region.  With N > 1 ranks every rank owns one column shard (its own 40
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   roofline      -- the dominant kernel against the MFMA roof it actually runs on (fp16/bf16 dense) plus the
                    fraction of the fp4 roof the north star asks about
+and, with --full only (a plain run measures the headline and nothing else):
   cpu_baseline  -- oracle/fake_quant.py (our port of the reference's CPU fake-quant path) on host cores
   extra         -- decode-shape (M=1, config[1]) GEMM vs the HBM roof, 8192^2 GEMM, equal-shape fp16
                    rocBLAS GEMM, quantiser timings, Qwen2.5-7B-shape decode tok/s, row-parallel + RCCL timing
+
+--dump-outputs DIR writes what the last timed step computed (the bf16 GEMM output, a fixed sample of its rows, as float32)
+to DIR/<name>.npy, so that two builds can be compared output for output on identical, seeded inputs.
 """
 from __future__ import annotations
 
@@ -110,6 +114,17 @@ def gemm_bytes(M, N, K):
     """Algorithmic HBM bytes of one ARC-NVFP4 GEMM launch: packed B + its scales, packed A
     + its scales, bf16 D."""
     return N * K * 9 / 16 + M * K * 9 / 16 + 2 * M * N
+
+
+def dump_output(dirname, name, t, rows):
+    """Write `rows` rows of the 2-D output `t` (all of them if it has fewer), chosen by a fixed seed, to dirname/name.npy as float32.
+    bf16 -> float32 is exact; the sample keeps the files small (the full 4096 x 4096 output is 64 MB in float32)."""
+    import numpy as np
+    if t.shape[0] > rows:
+        sel = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:rows].sort().values
+        t = t[sel.to(t.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
 
 
 def bench_extra(args, device, rank):
@@ -578,14 +593,21 @@ def main():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default, the contract's mode): every rank its own 4096 output columns, no data-path collective; strong: ONE "
                          "4096^2 ARC-GEMM split over the ranks (column-parallel shards + RCCL all-gather of the bf16 output) as the timed step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary measurements: the CPU baseline and `extra` (one GPU), the "
+                         "strong-scaling splits (--gpus N > 1).  Off by default: a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32, a fixed sample of rows)")
     ap.add_argument("--no-strong-extra", action="store_true",
-                    help="with --gpus N > 1: do NOT time the strong-scaling splits (ONE 4096^2 and ONE 8192^2 ARC-GEMM over the ranks, both "
-                         "tensor-parallel ways with their exchange; extra.strong_scaling).  They run in a helper process per rank, so a "
-                         "failing collective costs the JSON line nothing")
-    ap.add_argument("--strong-extra", action="store_true", help=argparse.SUPPRESS)      # round-2 spelling: now the default
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
+                    help="with --full and --gpus N > 1: do NOT time the strong-scaling splits (ONE 4096^2 and ONE 8192^2 ARC-GEMM over the "
+                         "ranks, both tensor-parallel ways with their exchange; extra.strong_scaling).  They run in a helper process per rank, "
+                         "so a failing collective costs the JSON line nothing")
+    ap.add_argument("--strong-extra", action="store_true", help=argparse.SUPPRESS)      # round-2 spelling: now part of --full
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary GPU measurements")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from arcquant_amd import launch
     if args.gpus > 1 and not launch.launched():
@@ -608,7 +630,7 @@ def main():
     # the strong-scaling extras run in a helper process of this rank, started NOW -- before this process touches the GPU (an exec
     # from a GPU-initialised process is refused on the pool) -- and idle until the headline has been measured
     helper = helper_conn = None
-    if world > 1 and not args.no_extra and not args.no_strong_extra:
+    if world > 1 and args.full and not args.no_extra and not args.no_strong_extra:
         import multiprocessing as mp
         ctx = mp.get_context("spawn")
         helper_conn, child_conn = ctx.Pipe()
@@ -679,6 +701,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:                         # what the last timed step left: `out` (weak, one file per rank) or the gathered output (strong)
+        if strong:
+            if rank == 0:
+                dump_output(args.dump_outputs, "out", gathered, 1024)
+        else:
+            dump_output(args.dump_outputs, "out" if world == 1 else f"out_rank{rank}", out, 1024 // world)
 
     flops = gemm_flops(M, N, K)
     # HBM traffic per launch from the committed PMC passes (FETCH_SIZE x2 per the gfx950 correction + WRITE_SIZE);
@@ -721,7 +749,7 @@ def main():
                              "(the rest: first loads + the 33.5 MB store burst at one tile per CU); "
                              "extra.gemm_4096.fp16_rocblas_TFLOPs is what the vendor fp16 GEMM sustains beside it in the same state"},
     }
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline()
         if not args.no_extra:

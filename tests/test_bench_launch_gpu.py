@@ -32,7 +32,8 @@ def _start(cmd, tmp_path):
 
 
 def test_bench_gpus_2_starts_its_own_ranks_and_prints_one_json_line(tmp_path):
-    r = _start([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--prewarm-ms", "0", "--no-cpu"], tmp_path)
+    r = _start([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--prewarm-ms", "0", "--no-cpu",
+                "--full"], tmp_path)
     assert r["rc"] == 0, r["stderr"]
     lines = r["stdout"].splitlines()                          # exactly ONE line, the JSON: library chatter (gloo prints to fd 1) goes to stderr
     assert len(lines) == 1 and lines[0].startswith("{"), r["stdout"]
@@ -43,6 +44,37 @@ def test_bench_gpus_2_starts_its_own_ranks_and_prints_one_json_line(tmp_path):
     assert "gemm_4096" in ss or "error" in ss, ss
     if "gemm_4096" in ss and "error" not in ss["gemm_4096"]:
         assert ss["gemm_4096"]["column_parallel_allgather"]["us"] > 0 and ss["gemm_4096"]["row_parallel_bf16_allreduce"]["us"] > 0
+
+
+def test_bench_plain_run_measures_the_headline_only_and_dumps_the_last_output(tmp_path):
+    """A plain run prints the headline line without the --full measurements; --dump-outputs writes the output of the timed GEMM,
+    which must be the product of the benchmark's own seeded operands."""
+    import numpy as np
+    import torch
+
+    import bench
+    dump = tmp_path / "dump"
+    r = _start([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--prewarm-ms", "0",
+                "--dump-outputs", str(dump)], tmp_path)
+    assert r["rc"] == 0, r["stderr"]
+    lines = r["stdout"].splitlines()
+    assert len(lines) == 1, r["stdout"]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["value"] > 0 and res["unit"] == "TFLOP/s"
+    assert "extra" not in res and "cpu_baseline" not in res
+    got = np.load(dump / "out.npy")
+    assert got.dtype == np.float32 and got.shape == (1024, 4096)
+
+    # the same problem in this process: the fp32 product of the dequantised operands, sampled by the same function
+    p = bench.make_problem(4096, 4096, 4096, 64, "cuda:0")
+    a = bench.dequant_fp16(p["qx"], p["sfx"], 4096, 4160).float()
+    b = bench.dequant_fp16(p["qw"], p["sfw"], 4096, 4160).float()
+    bench.dump_output(str(tmp_path / "ref"), "out", (a @ b.t()) * p["alpha"], 1024)
+    want = np.load(tmp_path / "ref" / "out.npy")
+    rel = np.linalg.norm(got.astype(np.float64) - want) / np.linalg.norm(want)
+    assert rel < 1e-2, rel
+    del p, a, b
+    torch.cuda.empty_cache()
 
 
 def test_e2e_tp_2_runs_one_decoder_layer_per_rank_with_its_collectives(tmp_path):
