@@ -50,6 +50,11 @@ SYMBOLS = {
     "arcq_linear_rmsnorm_silu_repacked": (_i32, [_p, _p, _f32, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _f32, _p, _p, _p, _p]),
     "arcq_linear_dynamic_repacked": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _f32, _p, _p, _i32, _p]),
     "arcq_silu_mul_quantize_x_dyn_slots": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i32, _i32, _p]),
+    "arcq_gemm_rw_route": (_i32, [_i64, _i64, _i64]),
+    "arcq_gemm_rw_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "arcq_gemm_nvfp4_rw": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p, _i64, _p]),
+    "arcq_gemm_rw_silu_mul_slots": (_i64, [_i64, _i64, _i64]),
+    "arcq_gemm_nvfp4_rw_silu_mul": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p]),
 }
 
 # include/arcq_harness.h: e2e-harness-only entry points (NOT the drop-in boundary)

@@ -266,13 +266,22 @@ def _quantize_dynamic(entry: str, who: str, X: torch.Tensor, KQ: int, reorder_in
     return QX, SFX, scale.reshape(())
 
 
+def _need_bytes(t: torch.Tensor, name: str, ndim: int):
+    # repack_w / unrepack_w: pure data movement, on whatever device the tensors live
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise RuntimeError(f"agemm: {name} must be a torch.uint8 tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != ndim or not t.is_contiguous():
+        raise RuntimeError(f"agemm: {name} must be a contiguous {ndim}-D tensor, got shape {tuple(t.shape)}")
+
+
 def repack_w(QW: torch.Tensor, SFW: torch.Tensor):
     """One-time re-layout of a quantised weight for the decode fast path (include/arcq.h, "REPACKED weight"): returns
     ``(RW, RSF)``.  Pure data movement with torch ops -- codes and scale bytes are those of ``reorder_quantize_w``:
     RW  = [row blocks of 16][tiles of 128 K][lane = 16*q + r][16 bytes], K padded to a multiple of 256, N to 16;
-    RSF = [row blocks][tile pairs][lane][4 bytes: the lane's two scale bytes in each tile of the pair]."""
-    _need(QW, torch.uint8, "QW", 2)
-    _need(SFW, torch.uint8, "SFW", 1)
+    RSF = [row blocks][tile pairs][lane][4 bytes: the lane's two scale bytes in each tile of the pair].
+    ``unrepack_w`` is its inverse; both also run on CPU tensors."""
+    _need_bytes(QW, "QW", 2)
+    _need_bytes(SFW, "SFW", 1)
     N, K = QW.shape[0], QW.shape[1] * 2
     if K % 64 or SFW.numel() < _sf_used(N, K):
         raise RuntimeError("Value error in repack_w: K % 64 != 0 or the scale buffer is too small")
@@ -294,6 +303,106 @@ def repack_w(QW: torch.Tensor, SFW: torch.Tensor):
     L = _lib.lib()
     assert RW.numel() == L.arcq_repacked_w_bytes(N, K) and RSF.numel() == L.arcq_repacked_sf_bytes(N, K)
     return RW, RSF
+
+
+def _sf_swizzle_offsets(N: int, K: int, dev):
+    # offset in the swizzled ue4m3 layout of scale group g of row r (include/arcq.h), as an [N, K/16] index tensor
+    r = torch.arange(N, device=dev).unsqueeze(1)
+    g = torch.arange(K // 16, device=dev).unsqueeze(0)
+    return ((r // 128) * (K // 64) + g // 4) * 512 + (r % 32) * 16 + ((r // 32) % 4) * 4 + g % 4
+
+
+def unrepack_w(RW: torch.Tensor, RSF: torch.Tensor, N: int, K: int):
+    """The exact inverse of ``repack_w`` (pure data movement with torch ops, on RW's device): returns ``(QW, SFW)`` in the reference
+    layout -- QW u8 [N, K/2], SFW u8 [sf_buffer_bytes(N, K)] with every byte outside the swizzled image of N rows zero -- so that a
+    layer that keeps only the repacked weight can still export the reference's checkpoint format."""
+    _need_bytes(RW, "RW", 1)
+    _need_bytes(RSF, "RSF", 1)
+    N, K = int(N), int(K)
+    if N <= 0 or K <= 0 or K % 64 or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
+        raise RuntimeError(f"Value error in unrepack_w: RW / RSF do not belong to a [{N}, {K}] weight")
+    dev = RW.device
+    Np, Kp = (N + 15) // 16 * 16, (K + 255) // 256 * 256
+    RB, T = Np // 16, Kp // 128
+    # codes: [RB, T, q, r, 16 B] -> [RB, r, T, q, 16 B] = [Np, Kp/2]
+    q = RW.view(RB, T, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(Np, Kp // 2)
+    QW = q[:N, : K // 2].contiguous()
+    # scales: [RB, T/2, q, r, tile, 2] -> [RB, r, T/2, tile, q, 2] = [Np, Kp/16], then back into the swizzled buffer
+    sf = RSF.view(RB, T // 2, 4, 16, 2, 2).permute(0, 3, 1, 4, 2, 5).reshape(Np, Kp // 16)
+    SFW = torch.zeros((sf_buffer_bytes(N, K),), dtype=torch.uint8, device=dev)
+    SFW[_sf_swizzle_offsets(N, K, dev)] = sf[:N, : K // 16]
+    return QW, SFW
+
+
+@functools.lru_cache(maxsize=None)
+def rw_route(M: int, N: int, K: int) -> int:
+    """Which kernels ``matmul_rw`` runs for this shape (aligned bias / residual; include/arcq.h): 1 = the repacked decode kernels
+    (exactly ``matmul_repacked``), 2 = register-tiled over RW, 3 = LDS-tiled over RW (both bit-identical to ``matmul`` on the
+    reference-layout weight, except the register-tiled decode shapes where ``matmul`` takes an LDS-transposing decode kernel),
+    0 = unsupported."""
+    return int(_lib.lib().arcq_gemm_rw_route(int(M), int(N), int(K)))
+
+
+def _alpha(scale, scale_host):
+    alpha_host, alpha_dev = float(scale_host), None
+    if isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1:
+        alpha_dev = scale
+    else:
+        alpha_host *= float(scale)
+    return alpha_host, alpha_dev
+
+
+def _same_device(who: str, A: torch.Tensor, *ts):
+    for t in ts:
+        if t is not None and t.device != A.device:
+            raise RuntimeError(f"agemm.{who}: every operand must live on A's device ({A.device}), got {t.device}")
+
+
+def matmul_rw(A: torch.Tensor, RW: torch.Tensor, SFA: torch.Tensor, RSF: torch.Tensor, scale, N: int, *, bias=None, residual=None,
+              out_dtype=torch.bfloat16, out=None, scale_host: float = 1.0):
+    """``matmul`` for EVERY M over the weight as ``repack_w`` left it (one weight copy per layer): same arguments and result as
+    ``matmul(A, B, ...)`` on the reference-layout weight, plus its row count ``N``.  Bit-identical to ``matmul_repacked`` where
+    ``rw_route`` is 1 and to ``matmul`` where it is 2 or 3 -- but the decode shapes ``matmul`` serves with an LDS-transposing kernel
+    (M <= 16 on very long K or very wide N), which agree up to fp32 summation order."""
+    _need(A, torch.uint8, "A", 2)
+    _need(RW, torch.uint8, "RW", 1)
+    _need(SFA, torch.uint8, "SFA")
+    _need(RSF, torch.uint8, "RSF", 1)
+    M, K, N = A.shape[0], A.shape[1] * 2, int(N)
+    if K % 64 or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
+        raise RuntimeError(f"Value error in matmul_rw: RW / RSF do not belong to a [{N}, {K}] weight")
+    if SFA.numel() < _sf_used(M, K):
+        raise RuntimeError("Value error in matmul_rw: SFA smaller than the swizzled layout of A")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError("agemm.matmul_rw: out_dtype must be bfloat16 or float32")
+    alpha_host, alpha_dev = _alpha(scale, scale_host)
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=A.device)
+    else:
+        _need(out, out_dtype, "out", 2)
+        if tuple(out.shape) != (M, N):
+            raise RuntimeError("agemm.matmul_rw: out has the wrong shape")
+    if bias is not None:
+        _need(bias, torch.bfloat16, "bias", 1)
+        if bias.numel() != N:
+            raise RuntimeError("agemm.matmul_rw: bias must have N entries")
+    if residual is not None:
+        _need(residual, torch.bfloat16, "residual", 2)
+        if tuple(residual.shape) != (M, N):
+            raise RuntimeError("agemm.matmul_rw: residual must be [M, N]")
+    _same_device("matmul_rw", A, RW, SFA, RSF, out, bias, residual, alpha_dev)
+    L = _lib.lib()
+    ws_bytes = int(L.arcq_gemm_rw_workspace_bytes(M, N, K))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=A.device) if ws_bytes else None
+    with _on(A.device):
+        st = L.arcq_gemm_nvfp4_rw(A.data_ptr(), RW.data_ptr(), SFA.data_ptr(), RSF.data_ptr(), out.data_ptr(), M, N, K, alpha_host,
+                                  alpha_dev.data_ptr() if alpha_dev is not None else None,
+                                  bias.data_ptr() if bias is not None else None,
+                                  residual.data_ptr() if residual is not None else None,
+                                  OUT_BF16 if out_dtype == torch.bfloat16 else OUT_F32,
+                                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream(A))
+    _lib.check(st, "matmul_rw")
+    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -379,6 +488,37 @@ def matmul_silu_mul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: to
                                         alpha_host, alpha_dev.data_ptr() if alpha_dev is not None else None,
                                         _opt(bias, torch.bfloat16, "bias", (N,)), _stream(A))
     _lib.check(st, "matmul_silu_mul")
+    return act, slots
+
+
+def matmul_rw_silu_mul(A: torch.Tensor, RW: torch.Tensor, SFA: torch.Tensor, RSF: torch.Tensor, scale, N: int, *, scale_host: float = 1.0,
+                       bias=None):
+    """``matmul_silu_mul`` over the weight as ``repack_w`` left it (rows interleaving gate and up), for M > 16 (prefill): returns
+    ``(act, absmax_slots)`` bit-identical to ``matmul_silu_mul`` on the reference-layout weight.  Decode (M <= 16) has its own
+    repacked SiLU paths (``matmul_repacked_silu_absmax``, ``rmsnorm_matmul_repacked_silu``) and raises here."""
+    _need(A, torch.uint8, "A", 2)
+    _need(RW, torch.uint8, "RW", 1)
+    _need(SFA, torch.uint8, "SFA")
+    _need(RSF, torch.uint8, "RSF", 1)
+    M, K, N = A.shape[0], A.shape[1] * 2, int(N)
+    if K % 64 or N % 8 or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
+        raise RuntimeError(f"Value error in matmul_rw_silu_mul: RW / RSF do not belong to a [{N}, {K}] weight, or N % 8 != 0")
+    if SFA.numel() < _sf_used(M, K):
+        raise RuntimeError("Value error in matmul_rw_silu_mul: SFA smaller than the swizzled layout of A")
+    alpha_host, alpha_dev = float(scale_host), None
+    if isinstance(scale, torch.Tensor) and scale.is_cuda:
+        alpha_dev = scale.reshape(-1)[:1].to(torch.float32)
+    else:
+        alpha_host *= float(scale)
+    bias_p = _opt(bias, torch.bfloat16, "bias", (N,))
+    _same_device("matmul_rw_silu_mul", A, RW, SFA, RSF, bias, alpha_dev)
+    L = _lib.lib()
+    act = torch.empty((M, N // 2), dtype=torch.bfloat16, device=A.device)
+    slots = torch.empty((max(1, int(L.arcq_gemm_rw_silu_mul_slots(M, N, K))),), dtype=torch.int32, device=A.device)
+    with _on(A.device):
+        st = L.arcq_gemm_nvfp4_rw_silu_mul(A.data_ptr(), RW.data_ptr(), SFA.data_ptr(), RSF.data_ptr(), act.data_ptr(), slots.data_ptr(), M, N, K,
+                                           alpha_host, alpha_dev.data_ptr() if alpha_dev is not None else None, bias_p, _stream(A))
+    _lib.check(st, "matmul_rw_silu_mul")
     return act, slots
 
 

@@ -180,6 +180,84 @@ torch::Tensor matmul_repacked(const torch::Tensor& A, const torch::Tensor& RW, c
   return D;
 }
 
+// ---- one weight copy for every M (include/arcq.h, arcq_gemm_nvfp4_rw): every operand must live on A's device
+void same_device(const char* who, const torch::Tensor& A, std::initializer_list<const torch::Tensor*> ts) {
+  for (const torch::Tensor* t : ts)
+    if (t && t->defined() && t->device() != A.device())
+      throw std::runtime_error(std::string("agemm.") + who + ": every operand must live on A's device");
+}
+const torch::Tensor* opt_t(const c10::optional<torch::Tensor>& t) { return t.has_value() ? &*t : nullptr; }
+
+torch::Tensor matmul_rw(const torch::Tensor& A, const torch::Tensor& RW, const torch::Tensor& SFA, const torch::Tensor& RSF, const py::object& scale, int64_t N,
+                        const c10::optional<torch::Tensor>& bias, const c10::optional<torch::Tensor>& residual, py::object out_dtype,
+                        const c10::optional<torch::Tensor>& out, double scale_host) {
+  const char* who = "matmul_rw";
+  need(A, torch::kUInt8, "A", 2);
+  need(SFA, torch::kUInt8, "SFA");
+  const int64_t M = A.size(0), K = A.size(1) * 2;
+  need_repacked(RW, RSF, N, K, who);
+  if (SFA.numel() < arcq_sf_used_bytes(M, K)) throw std::runtime_error("Value error in matmul_rw: SFA smaller than the swizzled layout of A");
+  const auto dt = out_dtype.is_none() ? torch::kBFloat16 : torch::python::detail::py_object_to_dtype(out_dtype);
+  const int oc = out_code(dt, who);
+  const Alpha al = alpha_of(scale, scale_host);
+  if (out.has_value()) need(*out, dt, "out", 2);
+  same_device(who, A, {&RW, &SFA, &RSF, opt_t(bias), opt_t(residual), opt_t(out), al.keep.defined() ? &al.keep : nullptr});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+  torch::Tensor D = out_of(out, M, N, dt, A, who);
+  const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
+  const void* rp = opt_ptr(residual, torch::kBFloat16, "residual", {M, N});
+  const int64_t ws_bytes = arcq_gemm_rw_workspace_bytes(M, N, K);
+  torch::Tensor ws;
+  if (ws_bytes) ws = torch::empty({ws_bytes}, A.options());
+  check(arcq_gemm_nvfp4_rw(A.data_ptr<uint8_t>(), RW.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), RSF.data_ptr<uint8_t>(), D.data_ptr(), M, N, K, al.host, al.dev,
+                           bp, rp, oc, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A)),
+        who);
+  return D;
+}
+
+std::tuple<torch::Tensor, torch::Tensor> matmul_rw_silu_mul(const torch::Tensor& A, const torch::Tensor& RW, const torch::Tensor& SFA, const torch::Tensor& RSF,
+                                                            const py::object& scale, int64_t N, double scale_host, const c10::optional<torch::Tensor>& bias) {
+  const char* who = "matmul_rw_silu_mul";
+  need(A, torch::kUInt8, "A", 2);
+  need(SFA, torch::kUInt8, "SFA");
+  const int64_t M = A.size(0), K = A.size(1) * 2;
+  need_repacked(RW, RSF, N, K, who);
+  if (N % 8) throw std::runtime_error("Value error in matmul_rw_silu_mul: N % 8 != 0");
+  if (SFA.numel() < arcq_sf_used_bytes(M, K)) throw std::runtime_error("Value error in matmul_rw_silu_mul: SFA smaller than the swizzled layout of A");
+  // (as the mirror: any CUDA scale tensor is read on the device as fp32)
+  float alpha_host = (float)scale_host;
+  torch::Tensor alpha_dev;
+  if (THPVariable_Check(scale.ptr()) && THPVariable_Unpack(scale.ptr()).is_cuda()) alpha_dev = THPVariable_Unpack(scale.ptr()).reshape({-1}).slice(0, 0, 1).to(torch::kFloat32);
+  else alpha_host *= THPVariable_Check(scale.ptr()) ? THPVariable_Unpack(scale.ptr()).item<float>() : scale.cast<float>();
+  same_device(who, A, {&RW, &SFA, &RSF, opt_t(bias), alpha_dev.defined() ? &alpha_dev : nullptr});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+  const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
+  auto act = torch::empty({M, N / 2}, A.options().dtype(torch::kBFloat16));
+  auto slots = torch::empty({std::max<int64_t>(1, arcq_gemm_rw_silu_mul_slots(M, N, K))}, A.options().dtype(torch::kInt32));
+  check(arcq_gemm_nvfp4_rw_silu_mul(A.data_ptr<uint8_t>(), RW.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), RSF.data_ptr<uint8_t>(), act.data_ptr(),
+                                    (uint32_t*)slots.data_ptr<int32_t>(), M, N, K, alpha_host, alpha_dev.defined() ? alpha_dev.data_ptr<float>() : nullptr, bp,
+                                    stream_of(A)),
+        who);
+  return {act, slots};
+}
+
+// the inverse of agemm.repack_w (data movement only): (QW [N, K/2], SFW [arcq_sf_alloc_bytes(N, K)], unused bytes zero)
+std::tuple<torch::Tensor, torch::Tensor> unrepack_w(const torch::Tensor& RW, const torch::Tensor& RSF, int64_t N, int64_t K) {
+  for (const auto* t : {&RW, &RSF})
+    if (t->scalar_type() != torch::kUInt8 || t->dim() != 1 || !t->is_contiguous()) throw std::runtime_error("agemm.unrepack_w: RW / RSF must be contiguous 1-D uint8 tensors");
+  if (N <= 0 || K <= 0 || K % 64 || RW.numel() != arcq_repacked_w_bytes(N, K) || RSF.numel() != arcq_repacked_sf_bytes(N, K))
+    throw std::runtime_error("Value error in unrepack_w: RW / RSF do not belong to a [N, K] weight of this shape");
+  const int64_t Np = (N + 15) / 16 * 16, Kp = (K + 255) / 256 * 256, RB = Np / 16, T = Kp / 128;
+  auto QW = RW.view({RB, T, 4, 16, 16}).permute({0, 3, 1, 2, 4}).reshape({Np, Kp / 2}).slice(0, 0, N).slice(1, 0, K / 2).contiguous();
+  auto sf = RSF.view({RB, T / 2, 4, 16, 2, 2}).permute({0, 3, 1, 4, 2, 5}).reshape({Np, Kp / 16}).slice(0, 0, N).slice(1, 0, K / 16);
+  const auto io = RW.options().dtype(torch::kInt64);
+  auto r = torch::arange(N, io).unsqueeze(1), g = torch::arange(K / 16, io).unsqueeze(0);
+  auto off = (r.div(128, "floor") * (K / 64) + g.div(4, "floor")) * 512 + r.remainder(32) * 16 + r.div(32, "floor").remainder(4) * 4 + g.remainder(4);
+  auto SFW = torch::zeros({arcq_sf_alloc_bytes(N, K)}, RW.options());
+  SFW.index_put_({off}, sf);
+  return {QW, SFW};
+}
+
 struct FusedShape {
   int64_t M, KQ, KE, K;
   int variant;
@@ -302,11 +380,17 @@ PYBIND11_MODULE(agemm, m) {
   m.def("rmsnorm_quantize_x", &rmsnorm_quantize_x, py::arg("X"), py::arg("W"), py::arg("eps"), py::arg("reorder_index"), py::arg("KE"));
   // decode extensions (arcquant_amd/agemm.py has the same functions through ctypes, and more)
   m.def("repacked_supported", [](int64_t M, int64_t N, int64_t K) { return arcq_gemm_repacked_supported(M, N, K) != 0; });
+  m.def("rw_route", [](int64_t M, int64_t N, int64_t K) { return arcq_gemm_rw_route(M, N, K); });
   m.def("fused_supported", [](int kind, int64_t M, int64_t N, int64_t KQ, int64_t KE) { return arcq_linear_fused_supported(kind, M, N, KQ, KE) != 0; });
   m.attr("SRC_RMSNORM") = ARCQ_SRC_RMSNORM;
   m.attr("SRC_DYNAMIC") = ARCQ_SRC_DYNAMIC;
   m.def("matmul_repacked", &matmul_repacked, py::arg("A"), py::arg("RW"), py::arg("SFA"), py::arg("RSF"), py::arg("scale"), py::arg("N"), py::kw_only(),
         py::arg("bias") = py::none(), py::arg("residual") = py::none(), py::arg("out_dtype") = py::none(), py::arg("out") = py::none(), py::arg("scale_host") = 1.0);
+  m.def("matmul_rw", &matmul_rw, py::arg("A"), py::arg("RW"), py::arg("SFA"), py::arg("RSF"), py::arg("scale"), py::arg("N"), py::kw_only(),
+        py::arg("bias") = py::none(), py::arg("residual") = py::none(), py::arg("out_dtype") = py::none(), py::arg("out") = py::none(), py::arg("scale_host") = 1.0);
+  m.def("matmul_rw_silu_mul", &matmul_rw_silu_mul, py::arg("A"), py::arg("RW"), py::arg("SFA"), py::arg("RSF"), py::arg("scale"), py::arg("N"), py::kw_only(),
+        py::arg("scale_host") = 1.0, py::arg("bias") = py::none());
+  m.def("unrepack_w", &unrepack_w, py::arg("RW"), py::arg("RSF"), py::arg("N"), py::arg("K"));
   m.def("rmsnorm_matmul_repacked", &rmsnorm_matmul_repacked, py::arg("X"), py::arg("W"), py::arg("eps"), py::arg("reorder_index"), py::arg("KE"), py::arg("RW"),
         py::arg("RSF"), py::arg("scale"), py::arg("N"), py::kw_only(), py::arg("bias") = py::none(), py::arg("residual") = py::none(),
         py::arg("out_dtype") = py::none(), py::arg("out") = py::none(), py::arg("scale_host") = 1.0, py::arg("variant") = py::none());

@@ -54,8 +54,10 @@ struct GemmArgs {
   int64_t workspace_bytes;
   int epilogue = 0;                  // kEpiPlain, or kEpiSiluMul: D = bf16 [M, N/2] silu(gate)*up of interleaved weight rows
   unsigned int* absmax_slots = nullptr;   // kEpiSiluMul: one max|D| word per workgroup / tile (see gemm_silu_slots)
+  int b_layout = 0;                  // kBRef: B / SFB in the reference layout; kBRepacked: B / SFB = RW / RSF of arcq.h (tile, regtile)
 };
 enum : int { kEpiPlain = 0, kEpiSiluMul = 1 };
+enum : int { kBRef = 0, kBRepacked = 1 };
 int64_t gemm_silu_slots(int64_t M, int64_t N, int64_t K);   // slots the silu-mul epilogue of this shape writes
 // gemm_stream.hip: persistent decode GEMM over a weight repacked into MFMA-operand-order tiles (see arcq.h), optionally with
 // the activation quantiser as its prologue
@@ -99,9 +101,11 @@ int gemm_splitk_finish(const GemmArgs& a, int splitk, hipStream_t stream);
 int gemm_skinny(const GemmArgs& a, hipStream_t stream);   // M <= 16, few tiles: weight-streaming MFMA GEMV, 16-row tiles
 int64_t gemm_decode_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int gemm_decode(const GemmArgs& a, hipStream_t stream);   // M <= 16, many tiles: 32-row tiles, two units per thread and item
-int gemm_tile(const GemmArgs& a, hipStream_t stream);     // general M: LDS-tiled MFMA GEMM
+int gemm_tile(const GemmArgs& a, hipStream_t stream);     // general M: LDS-tiled MFMA GEMM (either B layout)
+int gemm_tile_repacked(const GemmArgs& a, hipStream_t stream);   // gemm_tile_rw.hip: its B = RW / RSF instantiations (called by gemm_tile)
 // gemm_regtile.hip: 16 < M <~ 1024, grids the tiled kernel cannot fill: operand fragments straight into registers, K split over waves
 int gemm_regtile_cfg(int64_t M, int64_t N, int64_t K, int epilogue);   // 0 = not this kernel, else its configuration
-int gemm_regtile(const GemmArgs& a, int cfg, hipStream_t stream);
+int gemm_regtile(const GemmArgs& a, int cfg, hipStream_t stream);        // either B layout
+int gemm_regtile_fits(int64_t M, int64_t N, int64_t K, int b_layout);   // every operand addressable with the kernel's 32-bit offsets
 
 }  // namespace arcq

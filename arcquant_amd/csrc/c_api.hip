@@ -239,6 +239,92 @@ int arcq_gemm_nvfp4_repacked_silu_absmax(const uint8_t* A, const uint8_t* RW, co
   return gemm_repacked(a, RW, RSF, (hipStream_t)stream);
 }
 
+// ---- one weight copy for every M: arcq_gemm_nvfp4's contract over the repacked weight (RW, RSF) -----------------------------------------
+// Route 1 = the repacked decode kernels (exactly arcq_gemm_nvfp4_repacked); otherwise the RW instantiation of the kernel and configuration
+// arcq_gemm_nvfp4 would take (route 2 = register-tiled, 3 = LDS-tiled: bit-identical to it), except where that is an LDS-transposing decode
+// kernel (gemm_skinny / gemm_decode): those shapes take the register-tiled 16 x 16 configuration (id 9), also as route 2.
+static const int kRwDecodeCfg = 9;
+
+static int rw_route(int64_t M, int64_t N, int64_t K, bool epi_aligned, int* cfg) {
+  *cfg = 0;
+  if (M <= 0 || N <= 0 || K <= 0 || (K % 64) || M > INT32_MAX / 2 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40)) return 0;
+  if (epi_aligned && gemm_repacked_supported(M, N, K)) return 1;
+  *cfg = gemm_regtile_cfg(M, N, K, kEpiPlain);
+  if (*cfg == 0 && M <= kSkinnyMaxM) *cfg = kRwDecodeCfg;
+  if (*cfg) return gemm_regtile_fits(M, N, K, kBRepacked) ? 2 : 0;
+  return 3;
+}
+
+int arcq_gemm_rw_route(int64_t M, int64_t N, int64_t K) {
+  int cfg;
+  return rw_route(M, N, K, true, &cfg);
+}
+
+int64_t arcq_gemm_rw_workspace_bytes(int64_t M, int64_t N, int64_t K) {
+  int cfg;       // (a route-1 shape takes route 2 or 3 with a misaligned bias / residual view: size for that)
+  return rw_route(M, N, K, false, &cfg) == 3 ? gemm_tile_workspace_bytes(M, N, K) : 0;
+}
+
+int arcq_gemm_nvfp4_rw(const uint8_t* A, const uint8_t* RW, const uint8_t* SFA, const uint8_t* RSF, void* D, int64_t M, int64_t N, int64_t K,
+                       float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  const char* who = "arcq_gemm_nvfp4_rw";
+  if (M < 0 || N < 0 || K <= 0 || (K % 64))
+    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0 and K %% 64 == 0 (M=%lld N=%lld K=%lld)", who, (long long)M, (long long)N, (long long)K);
+  if (out_dtype != ARCQ_OUT_BF16 && out_dtype != ARCQ_OUT_F32) return fail(ARCQ_ERR_SHAPE, "%s: bad out_dtype %d", who, out_dtype);
+  if (M == 0 || N == 0) return ARCQ_OK;
+  if (!A || !RW || !SFA || !RSF || !D) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
+  if (M > INT32_MAX / 2 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40)) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
+  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(RW) | reinterpret_cast<uintptr_t>(D)) & 15)
+    return fail(ARCQ_ERR_SHAPE, "%s: A, RW and D must be 16-byte aligned", who);
+  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(RSF)) & 3) return fail(ARCQ_ERR_SHAPE, "%s: SFA and RSF must be 4-byte aligned", who);
+  // the repacked decode kernels reject bias / residual views that are not 8-byte aligned: those calls take route 2 / 3
+  const bool epi_aligned = ((reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) & 7) == 0;
+  int cfg;
+  const int route = rw_route(M, N, K, epi_aligned, &cfg);
+  if (route == 1) return arcq_gemm_nvfp4_repacked(A, RW, SFA, RSF, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, stream);
+  if (route == 0) return fail(ARCQ_ERR_UNSUPPORTED, "%s: the repacked weight of N=%lld K=%lld exceeds the register-tiled kernel's 32-bit offsets", who,
+                              (long long)N, (long long)K);
+  GemmArgs a;
+  a.A = A; a.B = RW; a.SFA = SFA; a.SFB = RSF; a.D = D;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = (const uint16_t*)bias; a.residual = (const uint16_t*)residual; a.out_dtype = out_dtype;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  a.b_layout = kBRepacked;
+  if (route == 2) return gemm_regtile(a, cfg, (hipStream_t)stream);
+  return gemm_tile(a, (hipStream_t)stream);
+}
+
+int64_t arcq_gemm_rw_silu_mul_slots(int64_t M, int64_t N, int64_t K) {
+  if (M <= kSkinnyMaxM || N <= 0 || K <= 0) return 0;
+  return gemm_tile_silu_slots(M, N, K);
+}
+
+int arcq_gemm_nvfp4_rw_silu_mul(const uint8_t* A, const uint8_t* RW, const uint8_t* SFA, const uint8_t* RSF, void* ACT, uint32_t* absmax_slots,
+                                int64_t M, int64_t N, int64_t K, float alpha_host, const float* alpha_dev, const void* bias, void* stream) {
+  const char* who = "arcq_gemm_nvfp4_rw_silu_mul";
+  if (M < 0 || N < 0 || K <= 0 || (K % 64) || (N % 8))
+    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0, K %% 64 == 0 and N %% 8 == 0 (M=%lld N=%lld K=%lld)", who, (long long)M, (long long)N,
+                (long long)K);
+  if (M == 0 || N == 0) return ARCQ_OK;
+  if (M <= kSkinnyMaxM)
+    return fail(ARCQ_ERR_UNSUPPORTED, "%s: M <= 16 is decode: use arcq_gemm_nvfp4_repacked_silu_absmax or arcq_linear_rmsnorm_silu_repacked", who);
+  if (!A || !RW || !SFA || !RSF || !ACT || !absmax_slots) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
+  if (M > INT32_MAX / 2 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40)) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
+  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(RW) | reinterpret_cast<uintptr_t>(ACT)) & 15)
+    return fail(ARCQ_ERR_SHAPE, "%s: A, RW and ACT must be 16-byte aligned", who);
+  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(RSF) | reinterpret_cast<uintptr_t>(absmax_slots)) & 3)
+    return fail(ARCQ_ERR_SHAPE, "%s: SFA, RSF and absmax_slots must be 4-byte aligned", who);
+  GemmArgs a;
+  a.A = A; a.B = RW; a.SFA = SFA; a.SFB = RSF; a.D = ACT;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = (const uint16_t*)bias; a.residual = nullptr; a.out_dtype = ARCQ_OUT_BF16;
+  a.workspace = nullptr; a.workspace_bytes = 0;
+  a.epilogue = kEpiSiluMul; a.absmax_slots = absmax_slots;
+  a.b_layout = kBRepacked;
+  return gemm_tile(a, (hipStream_t)stream);
+}
+
 int arcq_linear_fused_supported(int kind, int64_t M, int64_t N, int64_t KQ, int64_t KE) { return gemm_fused_supported(kind, M, N, KQ, KE); }
 
 static int fused_common_checks(const char* who, const void* X, const int16_t* idx, const uint8_t* RW, const uint8_t* RSF, void* D, int64_t M,

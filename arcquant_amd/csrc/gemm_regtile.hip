@@ -72,7 +72,11 @@ extern "C" void arcq_debug_set_regtile_stamps(void* p) { g_regtile_stamps = rein
 typedef uint32_t rt_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t rt_u32x2 __attribute__((ext_vector_type(2)));
 
-template <int TM, int TN, int WAVES_M, int WAVES_N, int KSPLIT>
+// kBLayout: kBRef = B / SFB in the reference layout, kBRepacked = the RW / RSF of arcq.h.  Only B's addresses and the assembly of its scale
+// dword differ: lane (r, c) of fragment t still takes row 16 t + r, atom 4 s + c of quad-step s, the same bytes into the same MFMA slots, so
+// the two produce identical sums.  In RW the atom's 16-byte halves are 256 bytes apart and a quad-step advances 2048 bytes; its four scale
+// bytes are two 2-byte pieces 64 bytes apart (groups 0-1 / 2-3), a quad-step advances 256 bytes.
+template <int TM, int TN, int WAVES_M, int WAVES_N, int KSPLIT, int kBLayout = kBRef>
 __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_regtile_kernel(RegTileParams p) {
   constexpr int kWaves = WAVES_M * WAVES_N * KSPLIT;
   constexpr int BM = 16 * TM * WAVES_M, BN = 16 * TN * WAVES_N;
@@ -100,6 +104,9 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_regtile_ke
 
   // per-fragment 32-bit byte offsets (the launcher keeps every operand below 2 GiB): rows beyond the matrix are clamped and simply
   // computed -- output element (m, n) depends on row m of A and row n of B only, and the epilogue stores nothing outside the matrix
+  constexpr bool kRW = kBLayout == kBRepacked;
+  constexpr int kBStep = kRW ? 2048 : 128, kBHi = kRW ? 256 : 16, kBSfStep = kRW ? 256 : 2048;   // bytes: B's quad-step, its second half, SFB's quad-step
+  const int rw_tiles = ((p.K + 255) >> 8) * 2;                      // kRW: 128-K tiles per padded row block
   uint32_t a_off[TM], a_sfo[TM], b_off[TN], b_sfo[TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
@@ -110,8 +117,13 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_regtile_ke
 #pragma unroll
   for (int t = 0; t < TN; ++t) {
     const int rc = min(n0 + 16 * t + r, p.N - 1);
-    b_off[t] = (uint32_t)rc * (uint32_t)half_k + c * 32;
-    b_sfo[t] = (uint32_t)sf_atom_offset(rc, c, atoms_k);
+    if constexpr (kRW) {                 // atom c of quad-step 0, first half; scale piece of groups 0-1 (stage_load_rw's terms)
+      b_off[t] = (uint32_t)(rc >> 4) * (uint32_t)(rw_tiles * 1024) + c * 512 + (rc & 15) * 16;
+      b_sfo[t] = (uint32_t)(rc >> 4) * (uint32_t)(rw_tiles * 128) + (c & 1) * 128 + (rc & 15) * 4 + ((c >> 1) & 1) * 2;
+    } else {
+      b_off[t] = (uint32_t)rc * (uint32_t)half_k + c * 32;
+      b_sfo[t] = (uint32_t)sf_atom_offset(rc, c, atoms_k);
+    }
   }
 
   f32x4 acc[TM][TN];
@@ -131,9 +143,11 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_regtile_ke
   // vector registers.  (With global loads hipcc built the addresses in registers that were still the targets of loads in flight and had to
   // wait for ALL of them before it could request the next step: M = 256 19.6 us, loads and multiplies one after the other.)
   const auto rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.A), 0, p.M * half_k, 0x00020000);
-  const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.B), 0, p.N * half_k, 0x00020000);
+  const int rw_rows = (p.N + 15) >> 4;                                // kRW: descriptors cover arcq_repacked_{w,sf}_bytes(N, K)
+  const auto rs_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.B), 0, kRW ? rw_rows * rw_tiles * 1024 : p.N * half_k, 0x00020000);
   const auto rs_sa = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.SFA), 0, ((p.M + 127) >> 7) * atoms_k * 512, 0x00020000);
-  const auto rs_sb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.SFB), 0, ((p.N + 127) >> 7) * atoms_k * 512, 0x00020000);
+  const auto rs_sb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(p.SFB), 0, kRW ? rw_rows * rw_tiles * 128 : ((p.N + 127) >> 7) * atoms_k * 512,
+                                                      0x00020000);
   auto load_lo = [&](Half& h, Scales& sc, int q, uint32_t drop = 0u) __attribute__((always_inline)) {     // + the step's scale bytes: needed from its first slice
 #ifdef ARCQ_EXPERIMENT_RT_NOLOAD
     // TIMING EXPERIMENT ONLY (results are WRONG): no operand is loaded, the multiply runs on register contents
@@ -150,8 +164,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_regtile_ke
     }
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
-      h.b[t] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, b_off[t] | drop, q * 128, 0);
-      sc.b[t] = __builtin_amdgcn_raw_buffer_load_b32(rs_sb, b_sfo[t] | drop, q * 2048, 0);
+      h.b[t] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, b_off[t] | drop, q * kBStep, 0);
+      if constexpr (kRW) {               // the reference's scale dword out of its two pieces
+        const uint32_t lo = __builtin_amdgcn_raw_buffer_load_b16(rs_sb, b_sfo[t] | drop, q * kBSfStep, 0);
+        const uint32_t hi = __builtin_amdgcn_raw_buffer_load_b16(rs_sb, (b_sfo[t] | drop) + 64, q * kBSfStep, 0);
+        sc.b[t] = lo | (hi << 16);
+      } else {
+        sc.b[t] = __builtin_amdgcn_raw_buffer_load_b32(rs_sb, b_sfo[t] | drop, q * kBSfStep, 0);
+      }
     }
   };
   auto load_hi = [&](Half& h, int q, uint32_t drop = 0u) __attribute__((always_inline)) {
@@ -165,7 +185,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_regtile_ke
 #pragma unroll
     for (int i = 0; i < TM; ++i) h.a[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, (a_off[i] | drop) + 16, q * 128, 0);
 #pragma unroll
-    for (int t = 0; t < TN; ++t) h.b[t] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, (b_off[t] | drop) + 16, q * 128, 0);
+    for (int t = 0; t < TN; ++t) h.b[t] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, (b_off[t] | drop) + kBHi, q * kBStep, 0);
   };
   // four MFMA K slices: slice j = dword j of the half, scale byte 2 * half + j / 2.  Weights are the MFMA A operand (rows = weight
   // rows), activations the B operand (columns = tokens): a lane ends up with four consecutive output columns n of one token
@@ -280,9 +300,19 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_regtile_ke
     }
 #pragma unroll
     for (int t = 0; t < TN; ++t) {
-      const rt_u32x2 w = *reinterpret_cast<const rt_u32x2*>((p.B + (size_t)atom * 32) + (b_off[t] - c * 24));
-      const uint32_t sf = *reinterpret_cast<const uint32_t*>((p.SFB + (size_t)atom * 512) + (b_sfo[t] - c * 512));
-      const f16x2 s2 = sf_pair_at(sf, 8 * c);
+      rt_u32x2 w;
+      f16x2 s2;
+      if constexpr (kRW) {               // group c = 8 bytes of half c >> 1; its scale byte is byte c & 1 of that half's piece
+        const uint32_t row_q = b_off[t] - c * 512, row_sf = b_sfo[t] - (c & 1) * 128 - ((c >> 1) & 1) * 2;
+        w = *reinterpret_cast<const rt_u32x2*>(p.B + (size_t)atom * 512 + row_q + (c >> 1) * 256 + (c & 1) * 8);
+        const uint32_t sf = *reinterpret_cast<const uint16_t*>(p.SFB + (size_t)((atom >> 2) * 256 + (atom & 1) * 128 + ((atom >> 1) & 1) * 2) + row_sf +
+                                                                (c >> 1) * 64);
+        s2 = sf_pair_at(sf, 8 * (c & 1));
+      } else {
+        w = *reinterpret_cast<const rt_u32x2*>((p.B + (size_t)atom * 32) + (b_off[t] - c * 24));
+        const uint32_t sf = *reinterpret_cast<const uint32_t*>((p.SFB + (size_t)atom * 512) + (b_sfo[t] - c * 512));
+        s2 = sf_pair_at(sf, 8 * c);
+      }
       xb[0][t] = dequant8(w.x, s2);
       xb[1][t] = dequant8(w.y, s2);
     }
@@ -352,7 +382,7 @@ static int regtile_override() {              // ARCQ_REGTILE_CFG: 0 = by shape, 
   return v;
 }
 
-template <int TM, int TN, int WAVES_M, int WAVES_N, int KSPLIT>
+template <int TM, int TN, int WAVES_M, int WAVES_N, int KSPLIT, int kBLayout>
 static int launch_regtile(const GemmArgs& a, hipStream_t stream) {
   RegTileParams p;
   p.A = a.A; p.B = a.B; p.SFA = a.SFA; p.SFB = a.SFB; p.D = a.D;
@@ -365,7 +395,7 @@ static int launch_regtile(const GemmArgs& a, hipStream_t stream) {
   p.stamps = g_regtile_stamps;
 #endif
   const int lds = KSPLIT > 1 ? kWaves * TM * TN * 64 * 16 : 0;
-  auto kern = gemm_regtile_kernel<TM, TN, WAVES_M, WAVES_N, KSPLIT>;
+  auto kern = gemm_regtile_kernel<TM, TN, WAVES_M, WAVES_N, KSPLIT, kBLayout>;
   static LdsOptIn lds_opt;
   if (lds > 0)
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_opt, lds, "arcq_gemm_nvfp4 (regtile)")) return rc;
@@ -381,9 +411,16 @@ static int launch_regtile(const GemmArgs& a, hipStream_t stream) {
 // kernel): N = K = 4096: M = 32 7.7 (32 x 16 tiles; 32 x 32: 9.5) / 15.7, 64 9.1 / 20.6, 128 11.3 / 25.8, 256 16.8 / 27.2, 512 27.5 / 32.6, 1024 46.8 / 46.5;
 // N = 10752, K = 3584: M = 32 11.4 / 20.1, 64 15.4 / 25.9, 128 25.9 / 28.7, 256 40.8 / 43.9, 512 75.6 / 65.0; N = 3584, K = 18944: M = 64 25.2 /
 // 34.1, 128 35.8 / 46.2, 256 54.3 / 59.6, 512 94.6 / 92.4, 1024 172 / 156.
+int gemm_regtile_fits(int64_t M, int64_t N, int64_t K, int b_layout) {
+  const int64_t lim = (int64_t)1 << 31;
+  if (b_layout == kBRepacked)    // A / SFA in the reference layout, B / SFB = RW / RSF (the tail reads of a wave stay below the descriptor ranges)
+    return M * (K / 2) < lim && ((M + 127) / 128) * (K / 64) * 512 < lim && gemm_repacked_w_bytes(N, K) < lim;
+  return (int64_t)max(M, N) * (K / 2) < lim && ((max(M, N) + 127) / 128) * (K / 64) * 512 < lim;
+}
+
 int gemm_regtile_cfg(int64_t M, int64_t N, int64_t K, int epilogue) {
   if (epilogue != kEpiPlain || (K & 63) != 0) return 0;
-  if ((int64_t)max(M, N) * (K / 2) >= ((int64_t)1 << 31) || ((max(M, N) + 127) / 128) * (K / 64) * 512 >= ((int64_t)1 << 31)) return 0;   // 32-bit offsets, buffer descriptors
+  if (!gemm_regtile_fits(M, N, K, kBRef)) return 0;   // 32-bit offsets, buffer descriptors
   const int ov = regtile_override();
   if (ov < 0) return 0;
   if (ov > 0) {
@@ -413,23 +450,33 @@ int gemm_regtile_cfg(int64_t M, int64_t N, int64_t K, int epilogue) {
   return 0;
 }
 
-int gemm_regtile(const GemmArgs& a, int cfg, hipStream_t stream) {
+template <int kBLayout>
+static int gemm_regtile_layout(const GemmArgs& a, int cfg, hipStream_t stream) {
   switch (cfg) {
-    case 1: return launch_regtile<4, 4, 1, 1, 8>(a, stream);
-    case 2: return launch_regtile<4, 4, 1, 2, 4>(a, stream);
-    case 3: return launch_regtile<4, 4, 2, 2, 2>(a, stream);
-    case 4: return launch_regtile<4, 4, 2, 4, 1>(a, stream);
-    case 5: return launch_regtile<2, 4, 1, 1, 8>(a, stream);
-    case 6: return launch_regtile<4, 2, 1, 1, 8>(a, stream);
-    case 7: return launch_regtile<2, 2, 1, 1, 8>(a, stream);
-    case 8: return launch_regtile<4, 4, 2, 1, 4>(a, stream);
-    case 9: return launch_regtile<1, 1, 1, 1, 8>(a, stream);
-    case 10: return launch_regtile<1, 2, 1, 1, 8>(a, stream);
-    case 11: return launch_regtile<1, 4, 1, 1, 8>(a, stream);
-    case 12: return launch_regtile<2, 1, 1, 1, 8>(a, stream);
-    case 13: return launch_regtile<4, 1, 1, 1, 8>(a, stream);
+    case 1: return launch_regtile<4, 4, 1, 1, 8, kBLayout>(a, stream);
+    case 2: return launch_regtile<4, 4, 1, 2, 4, kBLayout>(a, stream);
+    case 3: return launch_regtile<4, 4, 2, 2, 2, kBLayout>(a, stream);
+    case 4: return launch_regtile<4, 4, 2, 4, 1, kBLayout>(a, stream);
+    case 5: return launch_regtile<2, 4, 1, 1, 8, kBLayout>(a, stream);
+    case 6: return launch_regtile<4, 2, 1, 1, 8, kBLayout>(a, stream);
+    case 7: return launch_regtile<2, 2, 1, 1, 8, kBLayout>(a, stream);
+    case 8: return launch_regtile<4, 4, 2, 1, 4, kBLayout>(a, stream);
+    case 9: return launch_regtile<1, 1, 1, 1, 8, kBLayout>(a, stream);
+    case 10: return launch_regtile<1, 2, 1, 1, 8, kBLayout>(a, stream);
+    case 11: return launch_regtile<1, 4, 1, 1, 8, kBLayout>(a, stream);
+    case 12: return launch_regtile<2, 1, 1, 1, 8, kBLayout>(a, stream);
+    case 13: return launch_regtile<4, 1, 1, 1, 8, kBLayout>(a, stream);
     default: return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4 (regtile): unknown configuration %d", cfg);
   }
+}
+
+int gemm_regtile(const GemmArgs& a, int cfg, hipStream_t stream) {
+  if (a.b_layout == kBRepacked) {
+    if (!gemm_regtile_fits(a.M, a.N, a.K, kBRepacked))
+      return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4_rw (regtile): the repacked weight exceeds the kernel's 32-bit offsets");
+    return gemm_regtile_layout<kBRepacked>(a, cfg, stream);
+  }
+  return gemm_regtile_layout<kBRef>(a, cfg, stream);
 }
 
 }  // namespace arcq

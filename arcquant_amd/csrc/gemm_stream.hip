@@ -281,8 +281,8 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
         for (int j = 0; j < 8; ++j) {
           const int v = lane + 64 * j;
           if (v < bdx) {                                     // (implies 64 j < bdx: xa[j] / xb[j] were loaded)
-            lds_store_chunk(row, v, xa[j]);
-            lds_store_chunk(row, bdx + v, xb[j]);
+            lds_put_chunk(row, v, xa[j]);
+            lds_put_chunk(row, bdx + v, xb[j]);
             const uint32_t w8[8] = {xa[j].x, xa[j].y, xa[j].z, xa[j].w, xb[j].x, xb[j].y, xb[j].z, xb[j].w};
             float acc = 0.0f;
 #pragma unroll
@@ -409,9 +409,9 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
           misc[32 + wave] = (float)(1.0 / sqrt((double)var));                           // oracle assumption A4
         }
       }
-      if (tid < chunks) lds_store_chunk(reinterpret_cast<uint16_t*>(xstage + (size_t)p.M * p.xrow_bytes), tid, pre_wn);
+      if (tid < chunks) lds_put_chunk(reinterpret_cast<uint16_t*>(xstage + (size_t)p.M * p.xrow_bytes), tid, pre_wn);
       for (int cidx = tid + kStThreads; cidx < chunks; cidx += kStThreads)              // KQ > 8192 never reaches the RMSNorm path
-        lds_store_chunk(reinterpret_cast<uint16_t*>(xstage + (size_t)p.M * p.xrow_bytes), cidx, *reinterpret_cast<const uint4*>(p.Wn + (size_t)cidx * 8));
+        lds_put_chunk(reinterpret_cast<uint16_t*>(xstage + (size_t)p.M * p.xrow_bytes), cidx, *reinterpret_cast<const uint4*>(p.Wn + (size_t)cidx * 8));
       ARCQ_STAMP(8);
       __syncthreads();                                       // staged rows, norm weight and rstd visible
     } else {
@@ -427,8 +427,8 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
           }
           if (p.stage) {
             uint16_t* row = reinterpret_cast<uint16_t*>(xstage + (size_t)m * p.xrow_bytes);
-            lds_store_chunk(row, v, d0);
-            lds_store_chunk(row, bdx + v, d1);
+            lds_put_chunk(row, v, d0);
+            lds_put_chunk(row, bdx + v, d1);
           }
           amax = absmax_bits_chunk(d1, absmax_bits_chunk(d0, amax));
         }

@@ -30,8 +30,10 @@ namespace arcq {
 // DIAGNOSTIC build only: the in-kernel clock of the K loop = delta s_memtime / delta s_memrealtime x 100 MHz
 // (MI355X_MICROARCH.md, "DVFS give-back" item 6), stamped once around the loop by wave 0 of every workgroup into a buffer
 // nothing else reads (tools/tile_clock.py).  The product library has no stamps.
-static unsigned long long* g_tile_stamps = nullptr;
+static unsigned long long* g_tile_stamps = nullptr;     // (stays NULL in gemm_tile_rw.hip: its kernels are not stamped)
+#ifndef ARCQ_TILE_REPACKED_UNIT
 extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpret_cast<unsigned long long*>(p); }
+#endif
 #define ARCQ_TILE_STAMP(k)                                                                                     \
   do {                                                                                                         \
     if (p.stamps && tid == 0) {                                                                                \
@@ -50,7 +52,9 @@ extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpre
 // and then multiply step k+1 -- so that one wave's dequantise/ds_write phase overlaps the other's MFMA phase instead
 // of both waves of a SIMD leaving the matrix pipe idle together.  ONE loop body with a barrier on either side of the
 // staging block, each taken by one group (every wave still meets one barrier per step): no code is duplicated.
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool kMfma32, int kEpi, bool kStagger, bool kPipe>
+// kBLayout: kBRef = B / SFB in the reference layout, kBRepacked = the RW / RSF of arcq.h.  Only the addresses of B's staging loads
+// differ: the staged bytes, the LDS image, the K order and every MFMA are the same, so the two produce identical sums.
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool kMfma32, int kEpi, bool kStagger, bool kPipe, int kBLayout = kBRef>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TileParams p) {
   constexpr int kThreads = WAVES_M * WAVES_N * 64;
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;     // wave tile
@@ -120,8 +124,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
   for (int u = 0; u < B_UNITS; ++u) {
     const int unit = tid + u * kThreads, r = B_PARTIAL ? min(unit >> 1, BN - 1) : unit >> 1, h = unit & 1;
     const int row = n0 + r, rc = row < p.N ? row : p.N - 1;
-    b_q[u] = p.B + (size_t)rc * half_k + h * 16;
-    b_sf[u] = p.SFB + sf_atom_offset(rc, 0, atoms_k) + h * 2;
+    if constexpr (kBLayout == kBRepacked) {         // the atom-independent terms of stage_load_rw
+      const int tiles = ((p.K + 255) >> 8) * 2;
+      b_q[u] = p.B + (size_t)(rc >> 4) * tiles * 1024 + h * 256 + (rc & 15) * 16;
+      b_sf[u] = p.SFB + (size_t)(rc >> 4) * tiles * 128 + h * 64 + (rc & 15) * 4;
+    } else {
+      b_q[u] = p.B + (size_t)rc * half_k + h * 16;
+      b_sf[u] = p.SFB + sf_atom_offset(rc, 0, atoms_k) + h * 2;
+    }
     b_live[u] = row < p.N ? 0xffffu : 0u;
 #pragma unroll
     for (int j = 0; j < 4; ++j) b_slot[u][j] = kMfma32 ? lds_slot32(r, h * 4 + j) : lds_slot(r, h * 4 + j);
@@ -143,7 +153,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
 #pragma unroll
     for (int u = 0; u < A_UNITS; ++u) sa[u] = stage_load(a_q[u], a_sf[u], atom);
 #pragma unroll
-    for (int u = 0; u < B_UNITS; ++u) sb[u] = stage_load(b_q[u], b_sf[u], atom);
+    for (int u = 0; u < B_UNITS; ++u) sb[u] = kBLayout == kBRepacked ? stage_load_rw(b_q[u], b_sf[u], atom) : stage_load(b_q[u], b_sf[u], atom);
   };
   auto store_step = [&](unsigned char* la, unsigned char* lb) {
 #pragma unroll
@@ -510,7 +520,7 @@ static void tile_split(int64_t M, int64_t N, int64_t K, int BM, int BN, int* spl
   *atoms_per_split = per;
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool kMfma32 = false, int kEpi = kEpiPlain>
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool kMfma32 = false, int kEpi = kEpiPlain, int kBLayout = kBRef>
 static int launch_tile(const GemmArgs& a, hipStream_t stream, bool allow_split = false) {
   TileParams p;
   p.A = a.A; p.B = a.B; p.SFA = a.SFA; p.SFB = a.SFB; p.D = a.D;
@@ -535,9 +545,9 @@ static int launch_tile(const GemmArgs& a, hipStream_t stream, bool allow_split =
   }
   const size_t lds = 2 * (size_t)(BM + BN) * kRowBytes;
   constexpr bool kCanStagger = WAVES_M * WAVES_N == 8 && BM == 256 && BN == 256, kCanPipe = true;
-  auto kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false>;
-  if (kCanPipe && tile_pipe()) kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, kCanPipe>;
-  else if (kCanStagger && tile_stagger()) kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, kCanStagger, false>;
+  auto kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false, kBLayout>;
+  if (kCanPipe && tile_pipe()) kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, kCanPipe, kBLayout>;
+  else if (kCanStagger && tile_stagger()) kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, kCanStagger, false, kBLayout>;
   // per instantiation and per (pipe, stagger) variant of it, per device: the driver call costs host time on every launch otherwise
   static LdsOptIn lds_opt[3];
   const int which = (kCanPipe && tile_pipe()) ? 1 : (kCanStagger && tile_stagger()) ? 2 : 0;
@@ -574,6 +584,7 @@ static int effective_cfg(int64_t M, int64_t N, int64_t K, bool* may_split) {
   return id;
 }
 
+#ifndef ARCQ_TILE_REPACKED_UNIT
 // workgroups (= abs-max slots) of the silu-mul epilogue, which never splits K
 int64_t gemm_tile_silu_slots(int64_t M, int64_t N, int64_t K) {
   bool sp;
@@ -588,33 +599,41 @@ int64_t gemm_tile_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   if (sp) tile_split(M, N, K, c.bm, c.bn, &s, &per);
   return s > 1 ? (int64_t)s * M * N * (int64_t)sizeof(float) : 0;
 }
+#endif
 
-template <int kEpi>
+template <int kEpi, int kBLayout>
 static int gemm_tile_epi(const GemmArgs& a, hipStream_t stream) {
   bool sp;
   switch (effective_cfg(a.M, a.N, a.K, &sp)) {
-    case 1: case 9: return launch_tile<128, 128, 2, 2, false, kEpi>(a, stream, sp);
-    case 2: return launch_tile<256, 256, 2, 2, false, kEpi>(a, stream);
-    case 4: return launch_tile<128, 256, 2, 2, false, kEpi>(a, stream);
-    case 5: return launch_tile<256, 256, 2, 4, true, kEpi>(a, stream);
-    case 6: return launch_tile<128, 128, 2, 2, true, kEpi>(a, stream);
-    case 7: return launch_tile<64, 256, 1, 4, false, kEpi>(a, stream, sp);
-    case 8: return launch_tile<32, 256, 1, 4, false, kEpi>(a, stream, sp);
-    case 10: return launch_tile<128, 256, 2, 4, false, kEpi>(a, stream, sp);
-    case 11: return launch_tile<256, 128, 4, 2, false, kEpi>(a, stream, sp);
-    case 12: return launch_tile<128, 128, 2, 4, false, kEpi>(a, stream, sp);
-    case 13: return launch_tile<64, 256, 1, 8, false, kEpi>(a, stream, sp);
-    case 14: return launch_tile<64, 128, 2, 4, false, kEpi>(a, stream, sp);
-    case 15: return launch_tile<64, 64, 2, 2, false, kEpi>(a, stream, sp);
-    case 16: return launch_tile<64, 128, 2, 2, false, kEpi>(a, stream, sp);
-    case 17: return launch_tile<128, 64, 2, 2, false, kEpi>(a, stream, sp);
-    default: return launch_tile<256, 256, 2, 4, false, kEpi>(a, stream);
+    case 1: case 9: return launch_tile<128, 128, 2, 2, false, kEpi, kBLayout>(a, stream, sp);
+    case 2: return launch_tile<256, 256, 2, 2, false, kEpi, kBLayout>(a, stream);
+    case 4: return launch_tile<128, 256, 2, 2, false, kEpi, kBLayout>(a, stream);
+    case 5: return launch_tile<256, 256, 2, 4, true, kEpi, kBLayout>(a, stream);
+    case 6: return launch_tile<128, 128, 2, 2, true, kEpi, kBLayout>(a, stream);
+    case 7: return launch_tile<64, 256, 1, 4, false, kEpi, kBLayout>(a, stream, sp);
+    case 8: return launch_tile<32, 256, 1, 4, false, kEpi, kBLayout>(a, stream, sp);
+    case 10: return launch_tile<128, 256, 2, 4, false, kEpi, kBLayout>(a, stream, sp);
+    case 11: return launch_tile<256, 128, 4, 2, false, kEpi, kBLayout>(a, stream, sp);
+    case 12: return launch_tile<128, 128, 2, 4, false, kEpi, kBLayout>(a, stream, sp);
+    case 13: return launch_tile<64, 256, 1, 8, false, kEpi, kBLayout>(a, stream, sp);
+    case 14: return launch_tile<64, 128, 2, 4, false, kEpi, kBLayout>(a, stream, sp);
+    case 15: return launch_tile<64, 64, 2, 2, false, kEpi, kBLayout>(a, stream, sp);
+    case 16: return launch_tile<64, 128, 2, 2, false, kEpi, kBLayout>(a, stream, sp);
+    case 17: return launch_tile<128, 64, 2, 2, false, kEpi, kBLayout>(a, stream, sp);
+    default: return launch_tile<256, 256, 2, 4, false, kEpi, kBLayout>(a, stream);
   }
 }
 
+#ifndef ARCQ_TILE_REPACKED_UNIT
 int gemm_tile(const GemmArgs& a, hipStream_t stream) {
+  if (a.b_layout == kBRepacked) return gemm_tile_repacked(a, stream);       // gemm_tile_rw.hip
   // the epilogue is a template parameter: the plain kernels do not carry the exp code of silu-mul
-  return a.epilogue == kEpiSiluMul ? gemm_tile_epi<kEpiSiluMul>(a, stream) : gemm_tile_epi<kEpiPlain>(a, stream);
+  return a.epilogue == kEpiSiluMul ? gemm_tile_epi<kEpiSiluMul, kBRef>(a, stream) : gemm_tile_epi<kEpiPlain, kBRef>(a, stream);
 }
+#else
+int gemm_tile_repacked(const GemmArgs& a, hipStream_t stream) {
+  return a.epilogue == kEpiSiluMul ? gemm_tile_epi<kEpiSiluMul, kBRepacked>(a, stream) : gemm_tile_epi<kEpiPlain, kBRepacked>(a, stream);
+}
+#endif
 
 }  // namespace arcq

@@ -64,6 +64,16 @@ __device__ __forceinline__ Staged stage_load(const uint8_t* __restrict__ qrow, c
   return s;
 }
 
+// The same unit of a REPACKED weight (arcq.h, agemm.repack_w; T = K rounded up to 256, over 128): the 16 bytes of half h of row
+// 16 rb + r in atom a sit at RW + rb T 1024 + a 512 + h 256 + r 16, their two scale bytes at RSF + rb (T/2) 256 + (a >> 2) 256 +
+// (2 (a & 1) + h) 64 + r 4 + ((a >> 1) & 1) 2.  `qrow` / `sfrow` hold the atom-independent terms; the bytes are the reference's.
+__device__ __forceinline__ Staged stage_load_rw(const uint8_t* __restrict__ qrow, const uint8_t* __restrict__ sfrow, int atom) {
+  Staged s;
+  s.q = *reinterpret_cast<const uint4*>(qrow + (size_t)atom * 512);
+  s.sf = *reinterpret_cast<const uint16_t*>(sfrow + (atom >> 2) * 256 + (atom & 1) * 128 + ((atom >> 1) & 1) * 2);
+  return s;
+}
+
 // One quarter (8 elements, one 16-byte slot) of a staging unit: lets the K loop spread the dequantisation between its
 // MFMA groups.
 __device__ __forceinline__ void stage_piece(unsigned char* tile, int slot, const Staged& s, uint32_t live_mask, int j) {

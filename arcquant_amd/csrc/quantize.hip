@@ -162,7 +162,7 @@ __global__ __launch_bounds__(kQuantThreads) void quantize_rows_kernel(
     // the gather reads the norm weight of every channel: 16 scattered 2-byte global loads per group cost 2.6x
     // the whole static quantiser (41 vs 16 us at 4096^2), one LDS copy per workgroup does not
     for (int c = threadIdx.x; c < chunks; c += kQuantThreads)
-      lds_store_chunk(wn_lds, c, *reinterpret_cast<const uint4*>(Wn + (size_t)c * 8));
+      lds_put_chunk(wn_lds, c, *reinterpret_cast<const uint4*>(Wn + (size_t)c * 8));
     // visible after the barriers of the first row's reduction
   }
   // Every row of this workgroup gathers through the same reorder_index: the LDS byte offsets of a thread's first kGatherCache
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(kQuantThreads) void quantize_rows_kernel(
           for (int it = 0; it < 2; ++it) {
             const int c = it * bdx + v;
             uint4 d = *reinterpret_cast<const uint4*>(xrow + (size_t)c * 8);
-            lds_store_chunk(row_lds, c, d);
+            lds_put_chunk(row_lds, c, d);
             const uint32_t w4[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -219,10 +219,10 @@ __global__ __launch_bounds__(kQuantThreads) void quantize_rows_kernel(
       } else if (kSilu) {
         const uint16_t* urow = Xup + (size_t)row * ldx;
         for (int c = tid; c < chunks; c += kQuantThreads)
-          lds_store_chunk(row_lds, c, silu_act_chunk<kSilu>(xrow, urow, c));
+          lds_put_chunk(row_lds, c, silu_act_chunk<kSilu>(xrow, urow, c));
       } else {
         for (int c = tid; c < chunks; c += kQuantThreads)
-          lds_store_chunk(row_lds, c, *reinterpret_cast<const uint4*>(xrow + (size_t)c * 8));
+          lds_put_chunk(row_lds, c, *reinterpret_cast<const uint4*>(xrow + (size_t)c * 8));
       }
       __syncthreads();
     }

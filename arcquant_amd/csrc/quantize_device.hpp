@@ -85,7 +85,7 @@ __device__ __forceinline__ uint32_t absmax_bits_chunk(const uint4 d, uint32_t m)
 // than a random permutation, 47.2 vs 35.8 us at 8192^2).  With 36-byte groups the 64 lanes hit 64 different banks; a random
 // permutation is unaffected.  The pad is applied to a PAIR of int16 indices at once: e + 2 (e >> 4) <= 36861 fits 16 bits.
 __device__ __forceinline__ uint32_t lds_pad_pair(uint32_t w) { return w + (((w >> 4) & 0x0fff0fffu) << 1); }
-__device__ __forceinline__ void lds_store_chunk(uint16_t* row, int c, uint4 d) {       // chunk = 8 elements = half a group
+__device__ __forceinline__ void lds_put_chunk(uint16_t* row, int c, uint4 d) {       // chunk = 8 elements = half a group
   uint32_t* p = reinterpret_cast<uint32_t*>(row) + 4 * c + (c >> 1);
   p[0] = d.x; p[1] = d.y; p[2] = d.z; p[3] = d.w;
 }

@@ -66,19 +66,26 @@ class QLinear:
         self.in_f, self.out_f, self.KE = in_f, out_f, select_num
         self.RW = self.RSF = None
 
-    def repack(self):
-        """Second copy of the weight in MFMA-operand-order tiles for the decode path (agemm.repack_w)."""
+    def repack(self, release_reference=False):
+        """Second copy of the weight in MFMA-operand-order tiles for the decode path (agemm.repack_w).  release_reference: keep
+        ONLY that copy (W / SFW dropped; every M then runs through agemm.matmul_rw)."""
         self.RW, self.RSF = agemm.repack_w(self.W, self.SFW)
+        if release_reference:
+            self.W = self.SFW = None
 
     def matmul(self, A, SFA, scale, ops=agemm, **kw):
         """GEMM against this weight (+ its bias, in the epilogue): the repacked kernel for decode-sized token counts where available.
-        ``ops``: the module whose ``matmul_repacked`` is called (the ctypes mirror or the extension module)."""
+        ``ops``: the module whose ``matmul_repacked`` / ``matmul_rw`` is called (the ctypes mirror or the extension module)."""
         kw.setdefault("bias", self.bias)
+        if self.W is None:           # repacked only: one copy for every M (the repacked kernels where matmul_repacked would run)
+            return ops.matmul_rw(A, self.RW, SFA, self.RSF, scale, self.out_f, **kw)
         if self.RW is not None and agemm.repacked_supported(A.shape[0], self.out_f, self.in_f + self.KE):
             return ops.matmul_repacked(A, self.RW, SFA, self.RSF, scale, self.out_f, **kw)
         return agemm.matmul(A, self.W, SFA, self.SFW, scale, **kw)
 
     def bytes(self):
+        if self.W is None:           # repacked only: the padded RW / RSF it holds
+            return self.RW.numel() + self.RSF.numel()
         return self.W.numel() + self.out_f * (self.in_f + self.KE) // 16
 
 
@@ -88,10 +95,16 @@ class DecoderModel:
     `reorder_quantize_x_dynamic` (1-2 launches instead of 5), SiLU*up in the gate|up GEMM epilogue (`matmul_silu_mul`),
     residual add in the GEMM epilogue, one strided K|V cache append."""
 
-    def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current"):
+    def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
+                 repacked_only: bool = False):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
-        sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache."""
+        sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
+        repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
+        the repack and every GEMM the repacked kernels do not serve runs through agemm.matmul_rw / matmul_rw_silu_mul."""
+        if repacked_only and not fused:
+            raise ValueError("DecoderModel: repacked_only=True needs fused=True (the unfused model is the reference's call structure)")
         self.cfg, self.device, self.batch, self.max_len, self.fused = cfg, device, batch, max_len, fused
+        self.repacked_only = repacked_only
         self.attention = attention
         # the down projection's quantiser as its GEMM's prologue: every CU then quantises the whole M x intermediate activation
         # itself, which only pays while that is small (measured: Qwen2.5-7B, 4 x 18944: slower than the separate launch)
@@ -129,7 +142,7 @@ class DecoderModel:
         if fused:
             for L in self.layers:
                 for name in ("qkv", "o", "gateup", "down"):
-                    L[name].repack()
+                    L[name].repack(release_reference=repacked_only)
         self.idx_h = torch.arange(h, dtype=torch.int16, device=device)
         self.idx_i = torch.arange(it, dtype=torch.int16, device=device)
         self.inv_idx_i = torch.argsort(self.idx_i.long()).to(torch.int16)     # act_scatter_index of the gate|up epilogue
@@ -206,7 +219,10 @@ class DecoderModel:
                 else:
                     A, SFA = agemm.rmsnorm_quantize_x(hcur, L["ln2"], cfg.eps, self.idx_h, ke)
                     if T > 16:      # prefill: act_fn(gate) * up and its abs-max in the tile GEMM's epilogue
-                        act, slots = agemm.matmul_silu_mul(A, Gt.W, SFA, Gt.SFW, Gt.scale, bias=Gt.bias)
+                        if Gt.W is None:
+                            act, slots = agemm.matmul_rw_silu_mul(A, Gt.RW, SFA, Gt.RSF, Gt.scale, Gt.out_f, bias=Gt.bias)
+                        else:
+                            act, slots = agemm.matmul_silu_mul(A, Gt.W, SFA, Gt.SFW, Gt.scale, bias=Gt.bias)
                     elif Gt.RW is not None and Gt.bias is None and agemm.repacked_supported(T, Gt.out_f, h + ke):
                         # r1 path: the repacked GEMM leaves max |silu(g) * u| per row block, the quantiser applies SiLU*up itself
                         gu, slots = agemm.matmul_repacked_silu_absmax(A, Gt.RW, SFA, Gt.RSF, Gt.scale, Gt.out_f)
@@ -291,14 +307,17 @@ class DecoderModel:
 
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
-                 attention="current"):
-    """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps)."""
+                 attention="current", repacked_only=False):
+    """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
+    weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
     if layers:
         cfg.num_layers = layers
     device = torch.device(device)
     with torch.no_grad():
-        model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention)
+        mem0 = torch.cuda.memory_allocated(device)
+        model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only)
+        model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
         model.forward(tok, 0)
@@ -342,16 +361,19 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         wb = model.weight_bytes()
         kv = 2 * cfg.num_layers * batch * cfg.hidden_size * pos * 2 if attention == "cache" else 0
         assert out.shape == (batch, cfg.vocab_size)
-    return {"model": name, "fused": fused, "attention": attention, "layers": cfg.num_layers, "batch": batch, "prefill": prefill, "attn_window": pos,
-            "decode_ms_per_step_graph": round(best, 4), "decode_tok_per_s": round(batch / best * 1e3, 1),
-            "decode_ms_per_step_eager": round(eager_ms, 3), "prefill_ms": round(t_prefill * 1e3, 2),
-            "prefill_tok_per_s": round(batch * prefill / t_prefill, 0), "prefill_first_call_ms": round(t_prefill_first * 1e3, 1),
-            "weight_bytes": wb, "kv_bytes_read_per_step": kv,
-            "hbm_floor_ms_at_8TBps": round((wb + kv) / 8e12 * 1e3, 4)}
+    res = {"model": name, "fused": fused, "attention": attention, "layers": cfg.num_layers, "batch": batch, "prefill": prefill, "attn_window": pos,
+           "decode_ms_per_step_graph": round(best, 4), "decode_tok_per_s": round(batch / best * 1e3, 1),
+           "decode_ms_per_step_eager": round(eager_ms, 3), "prefill_ms": round(t_prefill * 1e3, 2),
+           "prefill_tok_per_s": round(batch * prefill / t_prefill, 0), "prefill_first_call_ms": round(t_prefill_first * 1e3, 1),
+           "weight_bytes": wb, "kv_bytes_read_per_step": kv,
+           "hbm_floor_ms_at_8TBps": round((wb + kv) / 8e12 * 1e3, 4)}
+    if repacked_only:
+        res.update(repacked_only=True, model_resident_bytes=int(model_bytes))
+    return res
 
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
-                   fused=True, attention="cache", graph=True, layers=None):
+                   fused=True, attention="cache", graph=True, layers=None, repacked_only=False):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -380,7 +402,7 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         return round(float(t.mean()), 3), round(1.96 * float(t.std(unbiased=False)), 3), max(peaks)
 
     with torch.no_grad():
-        model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention)
+        model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only)
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -411,12 +433,15 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         p_ms, p_ci, p_mem = module_benchmark(run_prefill)
         d_ms, d_ci, d_mem = module_benchmark(run_decode)
         e_ms, e_ci, e_mem = module_benchmark(run_e2e)
-    return {"protocol": "benchmark_e2e_arc.py: %d warm-up + %d timed calls x %d repeats, mean +- 1.96 sigma" % (warmup, steps, repeats),
-            "model": name, "layers": cfg.num_layers, "batch": batch, "prefill": prefill, "decode_steps": decode_steps, "fused": fused,
-            "attention": attention, "decode_from_hip_graph": bool(graph),
-            "prefill_ms": [p_ms, p_ci], "decode_ms": [d_ms, d_ci], "e2e_ms": [e_ms, e_ci],
-            "prefill_tok_per_s": round(batch * prefill / p_ms * 1e3, 0), "decode_tok_per_s": round(batch * decode_steps / d_ms * 1e3, 1),
-            "peak_memory_gb": round(max(p_mem, d_mem, e_mem) / 2 ** 30, 3)}
+    res = {"protocol": "benchmark_e2e_arc.py: %d warm-up + %d timed calls x %d repeats, mean +- 1.96 sigma" % (warmup, steps, repeats),
+           "model": name, "layers": cfg.num_layers, "batch": batch, "prefill": prefill, "decode_steps": decode_steps, "fused": fused,
+           "attention": attention, "decode_from_hip_graph": bool(graph),
+           "prefill_ms": [p_ms, p_ci], "decode_ms": [d_ms, d_ci], "e2e_ms": [e_ms, e_ci],
+           "prefill_tok_per_s": round(batch * prefill / p_ms * 1e3, 0), "decode_tok_per_s": round(batch * decode_steps / d_ms * 1e3, 1),
+           "peak_memory_gb": round(max(p_mem, d_mem, e_mem) / 2 ** 30, 3)}
+    if repacked_only:
+        res["repacked_only"] = True
+    return res
 
 
 # ---- BASELINE config[4]: one Llama-3-70B-shape decoder layer per rank of a tensor-parallel group -------------------------------------
@@ -546,11 +571,14 @@ if __name__ == "__main__":
         sys.exit(0)
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     name = args[0] if args else "qwen2.5-7b"
+    ro = "--repacked-only" in sys.argv       # one weight copy per linear (the fused model only)
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
-            print(json.dumps(bench_protocol(name, graph=graph)), flush=True)
+            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
-            print(json.dumps(bench_decode(name, fused=fused, attention=att)))
+            if ro and not fused:
+                continue
+            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro)))
             torch.cuda.empty_cache()

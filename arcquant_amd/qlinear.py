@@ -57,10 +57,13 @@ class QLinearLayer(nn.Module):
     """Weight quantised once at construction; forward = ARC-NVFP4 GEMM (+ bias) on pre-quantised activations."""
 
     def __init__(self, originalLayer: nn.Linear, select_num, reorder_index, out_reorder_index=None, quant_type="NVFP4",
-                 repack_for_decode: bool = False):
+                 repack_for_decode: bool = False, repacked_only: bool = False):
         """``repack_for_decode`` (extension, default off = the reference's behaviour and memory): additionally keep the
         weight in MFMA-operand-order tiles (``agemm.repack_w``) and use ``agemm.matmul_repacked`` for calls of at most 16
-        tokens."""
+        tokens.  ``repacked_only`` (extension): keep ONLY that copy -- ``W`` / ``scale_w`` are registered as None, every call
+        runs through ``agemm.matmul_rw`` (the same results as ``repack_for_decode``, but the decode shapes ``matmul`` serves with
+        an LDS-transposing kernel: there up to fp32 summation order); ``agemm.unrepack_w(RW, RSF, ...)`` rebuilds the
+        reference-layout pair."""
         super().__init__()
         if quant_type != "NVFP4":
             raise NotImplementedError("only quant_type='NVFP4' is supported")
@@ -78,10 +81,12 @@ class QLinearLayer(nn.Module):
         idx = reorder_index.to(device=dev, dtype=torch.int16)
         w = originalLayer.weight.data.to(torch.bfloat16)
         W, scale_w, scale = NVFP4_reorder_quantize_w(w, idx, self.select_num)
+        RW, RSF = agemm.repack_w(W, scale_w) if (repack_for_decode or repacked_only) else (None, None)
+        if repacked_only:
+            W = scale_w = None
         self.register_buffer("W", W)
         self.register_buffer("scale_w", scale_w)
         self.register_buffer("scale", scale)
-        RW, RSF = agemm.repack_w(W, scale_w) if repack_for_decode else (None, None)
         self.register_buffer("RW", RW)
         self.register_buffer("RSF", RSF)
 
@@ -91,7 +96,9 @@ class QLinearLayer(nn.Module):
         # `y = matmul(...); y = y + bias` (model/qLinearLayer.py:74-76): the bias add runs in the GEMM epilogue with the same
         # two roundings (the bf16 product, then the bf16 sum), so the result is bit-identical to the two torch steps
         bias = self.bias if self.bias is None or self.bias.dtype == torch.bfloat16 else None
-        if getattr(self, "RW", None) is not None and agemm.repacked_supported(qx.shape[0], self.out_features, qx.shape[1] * 2):
+        if self.W is None:
+            y = agemm.matmul_rw(qx, self.RW, scale_x, self.RSF, scale * self.scale, self.out_features, bias=bias)
+        elif getattr(self, "RW", None) is not None and agemm.repacked_supported(qx.shape[0], self.out_features, qx.shape[1] * 2):
             y = agemm.matmul_repacked(qx, self.RW, scale_x, self.RSF, scale * self.scale, self.out_features, bias=bias)
         else:
             y = agemm.matmul(qx, self.W, scale_x, self.scale_w, scale * self.scale, bias=bias)

@@ -195,6 +195,35 @@ int arcq_silu_mul_quantize_x_dyn_slots(const void *GU, const int16_t *reorder_in
                                        float *scale_out, const uint32_t *absmax_slots, int64_t nslots, int64_t M,
                                        int64_t KQ, int64_t KE, int variant, int layout, void *stream);
 
+/* ---- every M over the REPACKED weight: one weight copy per layer -------------------------------------------------------------
+ * arcq_gemm_nvfp4's contract (same A / SFA, alpha, bias, residual -- may alias D --, out_dtype, workspace) with B given as (RW, RSF)
+ * from arcq_repacked_{w,sf}_bytes / agemm.repack_w, for EVERY M: a layer that keeps only the repacked weight needs no second copy
+ * in the reference layout.  arcq_gemm_rw_route(M, N, K) says which kernels a call with 8-byte aligned bias / residual takes (pure, no GPU):
+ *   1  arcq_gemm_repacked_supported(M, N, K): the repacked decode kernels -- the call IS arcq_gemm_nvfp4_repacked;
+ *   2  the register-tiled kernel over RW in the configuration arcq_gemm_nvfp4 would use: bit-identical to arcq_gemm_nvfp4 on the
+ *      reference-layout weight.  Where arcq_gemm_nvfp4 takes an LDS-transposing decode kernel instead (M <= 16 on very long K or
+ *      very wide N, here called the G' shapes) its 16 x 16 configuration: equal up to fp32 summation order only;
+ *   3  the LDS-tiled kernel over RW, same configuration and split-K as arcq_gemm_nvfp4: bit-identical to it;
+ *   0  unsupported: an invalid shape, or a register-tiled route whose RW exceeds the kernel's 32-bit offsets (< 2 GiB).
+ * A bias / residual view that is not 8-byte aligned skips route 1 (the decode kernels reject it) and takes 2 or 3.
+ * Workspace: arcq_gemm_rw_workspace_bytes (= arcq_gemm_workspace_bytes on route 3; also sized for the route a route-1 shape
+ * takes with a misaligned view; 0 on route 2).  Validation as arcq_gemm_nvfp4:
+ * ARCQ_ERR_SHAPE for K % 64 / a bad out_dtype / misaligned A, RW, D (16 B) or SFA, RSF (4 B), ARCQ_ERR_NULL for a NULL operand,
+ * M == 0 or N == 0 returns ARCQ_OK, all before any HIP call. */
+int     arcq_gemm_rw_route(int64_t M, int64_t N, int64_t K);
+int64_t arcq_gemm_rw_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int     arcq_gemm_nvfp4_rw(const uint8_t *A, const uint8_t *RW, const uint8_t *SFA, const uint8_t *RSF, void *D,
+                           int64_t M, int64_t N, int64_t K, float alpha_host, const float *alpha_dev,
+                           const void *bias, const void *residual, int out_dtype,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+/* arcq_gemm_nvfp4_silu_mul over RW (rows interleaving gate and up, N % 8 == 0; the LDS-tiled kernel, bit-identical to it) for M > 16.
+ * M <= 16 returns ARCQ_ERR_UNSUPPORTED (before the pointer checks): decode has arcq_gemm_nvfp4_repacked_silu_absmax and
+ * arcq_linear_rmsnorm_silu_repacked.  absmax_slots: arcq_gemm_rw_silu_mul_slots(M, N, K) words (0 for M <= 16). */
+int64_t arcq_gemm_rw_silu_mul_slots(int64_t M, int64_t N, int64_t K);
+int     arcq_gemm_nvfp4_rw_silu_mul(const uint8_t *A, const uint8_t *RW, const uint8_t *SFA, const uint8_t *RSF,
+                                    void *ACT, uint32_t *absmax_slots, int64_t M, int64_t N, int64_t K,
+                                    float alpha_host, const float *alpha_dev, const void *bias, void *stream);
+
 /* ---- fused decode linear: the activation quantiser runs as the prologue of the repacked GEMM ------------------------------
  * One launch replaces  [rmsnorm_quantize_x | abs-max + x/scale + reorder_quantize_x]  ->  matmul (+ bias) (+ residual)
  * of a decode step (model/qLlamaLayer.py:73-77 + qLinearLayer.py:62-78; benchmarks/modeling_arc.py:211-228,279-310).  Every
