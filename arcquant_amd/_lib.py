@@ -55,6 +55,11 @@ SYMBOLS = {
     "arcq_gemm_nvfp4_rw": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p, _i64, _p]),
     "arcq_gemm_rw_silu_mul_slots": (_i64, [_i64, _i64, _i64]),
     "arcq_gemm_nvfp4_rw_silu_mul": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p]),
+    "arcq_mx_k_padded": (_i64, [_i64]),
+    "arcq_mx_sf_bytes": (_i64, [_i64, _i64]),
+    "arcq_mx_quantize_x": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "arcq_mx_quantize_w": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "arcq_gemm_mxfp4": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p, _i64, _p]),
 }
 
 # include/arcq_harness.h: e2e-harness-only entry points (NOT the drop-in boundary)

@@ -203,6 +203,103 @@ def matmul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: torch.Tenso
     return out
 
 
+
+# ---- MXFP4 (quant_type='MXFP4'; include/arcq.h "MXFP4", DESIGN.md "MXFP4") ----------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def mx_k_padded(K: int) -> int:
+    """round_up(K, 128): the stored K of an MXFP4 operand (codes [rows, Kp/2], scales [rows, Kp/32])."""
+    return int(_lib.lib().arcq_mx_k_padded(int(K)))
+
+
+def _mx_shape_first(*named):
+    # dtype and shape are checked before the device, so that a CPU tensor of the wrong dtype or shape is told what is wrong with it
+    for t, dtype, name, ndim in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise RuntimeError(f"agemm: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != ndim:
+            raise RuntimeError(f"agemm: {name} must be {ndim}-D, got shape {tuple(t.shape)}")
+
+
+def _mx_quantize(fn_name: str, X: torch.Tensor, reorder_index: torch.Tensor, KE: int):
+    xname = "X" if fn_name.endswith("_x") else "W"
+    _mx_shape_first((X, torch.bfloat16, xname, 2), (reorder_index, torch.int16, "reorder_index", 1))
+    rows, KQ = X.shape
+    KE = int(KE)
+    if reorder_index.numel() != KQ:
+        raise RuntimeError(f"agemm: reorder_index has {reorder_index.numel()} entries, expected {KQ}")
+    if KQ % 64 or KE % 64 or KE < 0 or KE > KQ or KQ > 32767:
+        raise RuntimeError(f"Value error in {fn_name}: KQ={KQ}, KE={KE} is not valid")
+    _need(X, torch.bfloat16, xname, 2)
+    _need(reorder_index, torch.int16, "reorder_index", 1)
+    if reorder_index.device != X.device:
+        raise RuntimeError(f"agemm.{fn_name}: reorder_index must live on {X.device}, got {reorder_index.device}")
+    Kp = mx_k_padded(KQ + KE)
+    Q = torch.empty((rows, Kp // 2), dtype=torch.uint8, device=X.device)
+    SF = torch.empty((rows, Kp // 32), dtype=torch.uint8, device=X.device)
+    L = _lib.lib()
+    fn = L.arcq_mx_quantize_x if fn_name.endswith("_x") else L.arcq_mx_quantize_w
+    with _on(X.device):
+        st = fn(X.data_ptr(), reorder_index.data_ptr(), Q.data_ptr(), SF.data_ptr(), rows, KQ, KE, _stream(X))
+    _lib.check(st, fn_name)
+    return Q, SF
+
+
+def mx_reorder_quantize_x(X: torch.Tensor, reorder_index: torch.Tensor, KE: int):
+    """MXFP4-ARC activation quantiser -> (QX u8 [M, Kp/2], SFX u8 E8M0 [M, Kp/32]); K = KQ + KE, Kp = round_up(K, 128).
+    Positions [KQ, K) hold the quantised residual of reordered channels [KQ-KE, KQ)."""
+    return _mx_quantize("mx_reorder_quantize_x", X, reorder_index, KE)
+
+
+def mx_reorder_quantize_w(W: torch.Tensor, reorder_index: torch.Tensor, KE: int):
+    """MXFP4-ARC weight quantiser -> (QW [N, Kp/2], SFW [N, Kp/32]); positions [KQ, K) copy reordered channels [KQ-KE, KQ)."""
+    return _mx_quantize("mx_reorder_quantize_w", W, reorder_index, KE)
+
+
+def mx_matmul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: torch.Tensor, scale, *, bias=None, residual=None,
+              out_dtype=torch.bfloat16, out=None, scale_host: float = 1.0):
+    """D = scale * deq(A) . deq(B)^T on the block-scaled fp4 MFMA -> [M, N] (bf16, or fp32 with ``out_dtype``).
+    ``matmul``'s semantics for ``scale`` (float or 0-dim fp32 device tensor), ``bias``, ``residual`` (may alias ``out``),
+    ``out`` and ``scale_host``.  N % 16 == 0."""
+    _mx_shape_first((A, torch.uint8, "A", 2), (B, torch.uint8, "B", 2), (SFA, torch.uint8, "SFA", 2), (SFB, torch.uint8, "SFB", 2))
+    M, N, K = A.shape[0], B.shape[0], A.shape[1] * 2
+    if B.shape[1] * 2 != K:
+        raise RuntimeError(f"agemm.mx_matmul: A has K={K}, B has K={B.shape[1] * 2}")
+    if K % 128:
+        raise RuntimeError(f"agemm.mx_matmul: K={K} is not a padded MXFP4 K (a multiple of 128)")
+    if N % 16:
+        raise RuntimeError(f"agemm.mx_matmul: N={N} must be a multiple of 16")
+    if tuple(SFA.shape) != (M, K // 32) or tuple(SFB.shape) != (N, K // 32):
+        raise RuntimeError("agemm.mx_matmul: SFA / SFB must be [rows, K/32]")
+    for t, name in ((A, "A"), (B, "B"), (SFA, "SFA"), (SFB, "SFB")):
+        _need(t, torch.uint8, name, 2)
+    _same_device("mx_matmul", A, B, SFA, SFB, scale if isinstance(scale, torch.Tensor) and scale.is_cuda else None, bias, residual, out)
+    alpha_host, alpha_dev = _alpha(scale, scale_host)
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError("agemm.mx_matmul: out_dtype must be bfloat16 or float32")
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=A.device)
+    else:
+        _need(out, out_dtype, "out", 2)
+        if tuple(out.shape) != (M, N):
+            raise RuntimeError("agemm.mx_matmul: out has the wrong shape")
+    if bias is not None:
+        _need(bias, torch.bfloat16, "bias", 1)
+        if bias.numel() != N:
+            raise RuntimeError("agemm.mx_matmul: bias must have N entries")
+    if residual is not None:
+        _need(residual, torch.bfloat16, "residual", 2)
+        if tuple(residual.shape) != (M, N):
+            raise RuntimeError("agemm.mx_matmul: residual must be [M, N]")
+    with _on(A.device):
+        st = _lib.lib().arcq_gemm_mxfp4(A.data_ptr(), B.data_ptr(), SFA.data_ptr(), SFB.data_ptr(), out.data_ptr(), M, N, K,
+                                        alpha_host, alpha_dev.data_ptr() if alpha_dev is not None else None,
+                                        bias.data_ptr() if bias is not None else None,
+                                        residual.data_ptr() if residual is not None else None,
+                                        OUT_BF16 if out_dtype == torch.bfloat16 else OUT_F32, None, 0, _stream(A))
+    _lib.check(st, "mx_matmul")
+    return out
+
 def absmax_scale(X: torch.Tensor) -> torch.Tensor:
     """Extension: ``max|X| / (448*6)`` as a 0-dim fp32 device tensor, no host sync.
     Equals ``torch.max(x.abs()).float() / (448.0*6.0)`` of model/qLlamaLayer.py:74 bit for bit (0-dim, so that

@@ -370,6 +370,48 @@ py::object kv_stub(const char* name) {
   });
 }
 
+// ---- MXFP4 (include/arcq.h "MXFP4"): the names and keywords of arcquant_amd/agemm.py's mx_* functions
+std::tuple<torch::Tensor, torch::Tensor> mx_quantize(bool is_x, const torch::Tensor& X, const torch::Tensor& reorder_index, int64_t KE) {
+  const char* who = is_x ? "mx_reorder_quantize_x" : "mx_reorder_quantize_w";
+  need(X, torch::kBFloat16, is_x ? "X" : "W", 2);
+  need(reorder_index, torch::kInt16, "reorder_index", 1);
+  same_device(who, X, {&reorder_index});
+  const int64_t rows = X.size(0), KQ = X.size(1), Kp = arcq_mx_k_padded(KQ + KE);
+  if (reorder_index.numel() != KQ || KQ % 64 || KE % 64 || KE < 0 || KE > KQ || KQ > 32767)
+    throw std::runtime_error(std::string("Value error in ") + who + ": KQ / KE / reorder_index are not valid");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  auto Q = torch::empty({rows, Kp / 2}, X.options().dtype(torch::kUInt8));
+  auto SF = torch::empty({rows, Kp / 32}, X.options().dtype(torch::kUInt8));
+  auto fn = is_x ? arcq_mx_quantize_x : arcq_mx_quantize_w;
+  check(fn(X.data_ptr(), reorder_index.data_ptr<int16_t>(), Q.data_ptr<uint8_t>(), SF.data_ptr<uint8_t>(), rows, KQ, KE, stream_of(X)), who);
+  return {Q, SF};
+}
+
+torch::Tensor mx_matmul(const torch::Tensor& A, const torch::Tensor& B, const torch::Tensor& SFA, const torch::Tensor& SFB, const py::object& scale,
+                        const c10::optional<torch::Tensor>& bias, const c10::optional<torch::Tensor>& residual, py::object out_dtype,
+                        const c10::optional<torch::Tensor>& out, double scale_host) {
+  const char* who = "mx_matmul";
+  need(A, torch::kUInt8, "A", 2);
+  need(B, torch::kUInt8, "B", 2);
+  need(SFA, torch::kUInt8, "SFA", 2);
+  need(SFB, torch::kUInt8, "SFB", 2);
+  const int64_t M = A.size(0), N = B.size(0), K = A.size(1) * 2;
+  if (B.size(1) * 2 != K) throw std::runtime_error("agemm.mx_matmul: A and B disagree on K");
+  if (K % 128 || N % 16) throw std::runtime_error("agemm.mx_matmul: K must be a multiple of 128 and N of 16");
+  if (SFA.size(0) != M || SFA.size(1) != K / 32 || SFB.size(0) != N || SFB.size(1) != K / 32)
+    throw std::runtime_error("agemm.mx_matmul: SFA / SFB must be [rows, K/32]");
+  const auto dt = out_dtype.is_none() ? torch::kBFloat16 : torch::python::detail::py_object_to_dtype(out_dtype);
+  const int oc = out_code(dt, who);
+  const Alpha al = alpha_of(scale, scale_host);
+  same_device(who, A, {&B, &SFA, &SFB, opt_t(bias), opt_t(residual), opt_t(out), al.keep.defined() ? &al.keep : nullptr});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+  torch::Tensor D = out_of(out, M, N, dt, A, who);
+  check(arcq_gemm_mxfp4(A.data_ptr<uint8_t>(), B.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), SFB.data_ptr<uint8_t>(), D.data_ptr(), M, N, K, al.host, al.dev,
+                        opt_ptr(bias, torch::kBFloat16, "bias", {N}), opt_ptr(residual, torch::kBFloat16, "residual", {M, N}), oc, nullptr, 0, stream_of(A)),
+        who);
+  return D;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(agemm, m) {
@@ -402,6 +444,12 @@ PYBIND11_MODULE(agemm, m) {
         py::arg("out_dtype") = py::none(), py::arg("out") = py::none(), py::arg("variant") = py::none());
   m.def("reorder_quantize_x_dynamic", &reorder_quantize_x_dynamic, py::arg("X"), py::arg("reorder_index"), py::arg("KE"), py::arg("variant") = py::none(),
         py::kw_only(), py::arg("absmax_slots"));
+  m.def("mx_reorder_quantize_x", [](const torch::Tensor& X, const torch::Tensor& idx, int64_t KE) { return mx_quantize(true, X, idx, KE); }, py::arg("X"),
+        py::arg("reorder_index"), py::arg("KE"));
+  m.def("mx_reorder_quantize_w", [](const torch::Tensor& W, const torch::Tensor& idx, int64_t KE) { return mx_quantize(false, W, idx, KE); }, py::arg("W"),
+        py::arg("reorder_index"), py::arg("KE"));
+  m.def("mx_matmul", &mx_matmul, py::arg("A"), py::arg("B"), py::arg("SFA"), py::arg("SFB"), py::arg("scale"), py::kw_only(), py::arg("bias") = py::none(),
+        py::arg("residual") = py::none(), py::arg("out_dtype") = py::none(), py::arg("out") = py::none(), py::arg("scale_host") = 1.0);
   for (const char* n : {"batch_decode_i4", "init_kv_i4", "append_kv_i4", "batch_decode_f16", "init_kv_f16", "append_kv_f16"}) m.attr(n) = kv_stub(n);
   m.attr("abi_version") = arcq_abi_version();
 }

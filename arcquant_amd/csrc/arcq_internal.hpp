@@ -37,6 +37,12 @@ int silu_mul_quantize_x_dyn_slots(const void* GU, const int16_t* idx, uint8_t* Q
 int silu_mul_quantize_x_dyn(const void* GU, const int16_t* idx, uint8_t* QX, uint8_t* SFX, float* scale_out, void* state, int64_t M,
                             int64_t KQ, int64_t KE, int variant, int layout, hipStream_t stream);
 
+// quantize_mx.hip / gemm_mx.hip: the MXFP4 path (arcq.h "MXFP4"); K of gemm_mx is the padded K of the operands
+int mx_quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, hipStream_t stream);
+int mx_quantize_w(const void* W, const int16_t* idx, uint8_t* QW, uint8_t* SFW, int64_t N, int64_t KQ, int64_t KE, hipStream_t stream);
+int gemm_mx(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t Kp,
+            float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, hipStream_t stream);
+
 // gemm_skinny.hip / gemm_tile.hip
 struct GemmArgs {
   const uint8_t* A;     // [M, K/2]

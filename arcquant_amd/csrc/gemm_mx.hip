@@ -1,0 +1,249 @@
+// MXFP4 GEMM for gfx950 on the block-scaled fp4 MFMA (v_mfma_scale_f32_{32x32x64,16x16x128}_f8f6f4, cbsz = blgp = 4).
+//
+//   D[m,n] = alpha * sum_{k < Kp} deq(A[m,k]) * deq(B[n,k])      A [M, Kp/2], B [N, Kp/2] e2m1, SFA / SFB [rows, Kp/32] E8M0
+//
+// Every product of two e2m1 codes and two power-of-two scales is exact, so the instruction takes the packed codes and the
+// scale bytes as they are stored: no dequantisation instruction, the matrix pipe at the fp4 rate.
+//
+// Operand map of the fp4 form (pinned by tests/test_mx_gpu.py::test_lane_map_exact with exact integer data):
+//   16x16x128: lane l supplies row l & 15, K elements [32 (l >> 4), +32) = 16 bytes, and the scale byte of that 32-block;
+//   32x32x64:  lane l supplies row l & 31, K elements [32 (l >> 5), +32) and the scale byte of that block.
+//   The scale operand is a VGPR; op_sel picks one of its bytes for the whole wave, so each lane shifts its byte down and
+//   op_sel stays 0.  C/D as every gfx950 MFMA: 32x32 reg r of lane l = D[(r & 3) + 8 (r >> 2) + 4 (l >> 5)][l & 31],
+//   16x16 reg r of lane l = D[4 (l >> 4) + r][l & 15]  (row = A's row, column = B's row).
+//
+// Two configurations:
+//   mx_tile_kernel   M > kMxSmallM: 128 x 128 tiles, 4 waves of 64 x 64 (2 x 2 MFMA 32x32x64), K steps of 128 staged through
+//                    LDS (XOR-swizzled 64-byte rows: the 16-byte fragment reads are bank-conflict free), double-buffered: the
+//                    global loads of step s + 1 are in flight while step s computes.
+//   mx_small_kernel  M <= kMxSmallM: one 16-column slice of B per workgroup (each weight byte is read by ONE workgroup
+//                    when M <= 16), 8 waves splitting K, four K steps of loads in flight per wave, 16x16x128 MFMA, partial
+//                    sums added in LDS in a fixed order.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "arcq_device.hpp"
+#include "arcq_internal.hpp"
+#include "gemm_common.hpp"
+
+namespace arcq {
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+struct MxArgs {
+  const uint8_t* A;
+  const uint8_t* B;
+  const uint8_t* SFA;
+  const uint8_t* SFB;
+  void* D;
+  int M, N, Kp;
+  float alpha_host;
+  const float* alpha_dev;
+  const uint16_t* bias;
+  const uint16_t* residual;
+  int out_dtype;
+};
+
+__device__ __forceinline__ i32x8 frag(uint4 u) {
+  i32x8 f = {(int)u.x, (int)u.y, (int)u.z, (int)u.w, 0, 0, 0, 0};     // fp4: the instruction reads the first four dwords only
+  return f;
+}
+__device__ __forceinline__ i32x8 frag(i32x4 u) {
+  i32x8 f = {u.x, u.y, u.z, u.w, 0, 0, 0, 0};
+  return f;
+}
+
+// alpha * acc (+ bias) (+ residual) -> D[m, n] with arcq_gemm_nvfp4's roundings (gemm_common.hpp finish4)
+__device__ __forceinline__ void mx_store(const MxArgs& p, float alpha, int m, int n, float acc) {
+  const size_t o = (size_t)m * (size_t)p.N + (size_t)n;
+  float d = alpha * acc;
+  const bool f32 = p.out_dtype == ARCQ_OUT_F32;
+  if (p.bias) d = (f32 ? d : bf16_bits_to_f32(f32_to_bf16_bits(d))) + bf16_bits_to_f32(p.bias[n]);
+  if (p.residual) d = (f32 ? d : bf16_bits_to_f32(f32_to_bf16_bits(d))) + bf16_bits_to_f32(p.residual[o]);
+  if (f32) reinterpret_cast<float*>(p.D)[o] = d;
+  else reinterpret_cast<uint16_t*>(p.D)[o] = (uint16_t)f32_to_bf16_bits(d);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- tiled
+constexpr int kMxTile = 128;
+constexpr int kMxOpBytes = kMxTile * 64;                     // one operand tile of one K step: 128 rows x 64 bytes
+constexpr int kMxBufBytes = 2 * kMxOpBytes + 2 * kMxTile * 4;   // A, B, then one scale dword per row of A and of B
+
+// LDS byte offset of 16-byte chunk c (0..3) of staged row r.  The chunk index is XORed with (r >> 2) & 3: the 16 lanes of each
+// ds_read_b128 lane group read 16 different rows at one logical chunk; rows equal mod 4 would share banks in a plain 64-byte
+// layout, the swizzle gives them four different chunks (conflict-free, and no padding: 4 workgroups fit a CU's LDS).
+__device__ __forceinline__ int mx_lds_off(int r, int c) { return r * 64 + ((c ^ (r >> 2)) & 3) * 16; }
+
+__global__ __launch_bounds__(256) void mx_tile_kernel(MxArgs p) {
+  __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kMxBufBytes];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int m0 = blockIdx.y * kMxTile, n0 = blockIdx.x * kMxTile;
+  const size_t rowb = (size_t)(p.Kp >> 1), rows = (size_t)(p.Kp >> 5);
+  const int steps = p.Kp >> 7;
+
+  // staging: thread t moves 16-byte chunks t and t + 256 of each operand tile (row = chunk / 4) and one scale dword
+  const int cr = tid >> 2, cc = tid & 3;
+  const uint8_t* gA0 = p.A + (size_t)min(m0 + cr, p.M - 1) * rowb + cc * 16;
+  const uint8_t* gA1 = p.A + (size_t)min(m0 + cr + 64, p.M - 1) * rowb + cc * 16;
+  const uint8_t* gB0 = p.B + (size_t)min(n0 + cr, p.N - 1) * rowb + cc * 16;
+  const uint8_t* gB1 = p.B + (size_t)min(n0 + cr + 64, p.N - 1) * rowb + cc * 16;
+  const uint8_t* gS = tid < kMxTile ? p.SFA + (size_t)min(m0 + tid, p.M - 1) * rows
+                                    : p.SFB + (size_t)min(n0 + tid - kMxTile, p.N - 1) * rows;
+  const int l0 = mx_lds_off(cr, cc), l1 = mx_lds_off(cr + 64, cc);
+  // the load of a step past the end re-reads the last step (stashed where nothing reads it): no branch around the loads
+  uint4 ra0, ra1, rb0, rb1;
+  uint32_t rs;
+  auto load = [&](int s) __attribute__((always_inline)) {
+    const size_t o = (size_t)min(s, steps - 1) * 64;
+    ra0 = *reinterpret_cast<const uint4*>(gA0 + o);
+    ra1 = *reinterpret_cast<const uint4*>(gA1 + o);
+    rb0 = *reinterpret_cast<const uint4*>(gB0 + o);
+    rb1 = *reinterpret_cast<const uint4*>(gB1 + o);
+    rs = *reinterpret_cast<const uint32_t*>(gS + o / 16);
+  };
+  auto stash = [&](int buf) __attribute__((always_inline)) {
+    uint8_t* L = lds + buf * kMxBufBytes;
+    *reinterpret_cast<uint4*>(L + l0) = ra0;
+    *reinterpret_cast<uint4*>(L + l1) = ra1;
+    *reinterpret_cast<uint4*>(L + kMxOpBytes + l0) = rb0;
+    *reinterpret_cast<uint4*>(L + kMxOpBytes + l1) = rb1;
+    reinterpret_cast<uint32_t*>(L + 2 * kMxOpBytes)[tid] = rs;
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+
+  const int r32 = lane & 31, h = lane >> 5;
+  auto compute = [&](int buf) __attribute__((always_inline)) {
+    const uint8_t* L = lds + buf * kMxBufBytes;
+    const uint32_t* LS = reinterpret_cast<const uint32_t*>(L + 2 * kMxOpBytes);
+    uint32_t sa[2], sb[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      sa[i] = LS[wm * 64 + i * 32 + r32];
+      sb[i] = LS[kMxTile + wn * 64 + i * 32 + r32];
+    }
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub) {            // two K-64 halves of the step: logical chunk 2 sub + h of each row
+      const int sh = 8 * (2 * sub + h);
+      i32x8 a[2], b[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        a[i] = frag(*reinterpret_cast<const uint4*>(L + mx_lds_off(wm * 64 + i * 32 + r32, 2 * sub + h)));
+        b[i] = frag(*reinterpret_cast<const uint4*>(L + kMxOpBytes + mx_lds_off(wn * 64 + i * 32 + r32, 2 * sub + h)));
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[i], b[j], acc[i][j], 4, 4, 0, (int)(sa[i] >> sh), 0,
+                                                                      (int)(sb[j] >> sh));
+    }
+  };
+
+  // the loads of step s + 1 are issued before step s computes and stored to the other LDS buffer after it.  The scheduling
+  // barriers pin that order: left to itself the compiler hoists the LDS stores above the MFMAs (or sinks the loads below
+  // them), and every step then waits out the full global latency.
+  load(0);
+  stash(0);
+  __syncthreads();
+  for (int s = 0; s < steps; ++s) {
+    load(s + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    compute(s & 1);
+    __builtin_amdgcn_sched_barrier(0);
+    stash((s + 1) & 1);
+    __syncthreads();
+  }
+
+  const float alpha = p.alpha_host * (p.alpha_dev ? *p.alpha_dev : 1.0f);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int n = n0 + wn * 64 + j * 32 + r32;
+      if (n >= p.N) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (m < p.M) mx_store(p, alpha, m, n, acc[i][j][r]);
+      }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- small M
+constexpr int kMxSmallM = 64;
+constexpr int kMxSmallWaves = 8;
+constexpr int kMxSmallUnroll = 4;
+
+__global__ __launch_bounds__(64 * kMxSmallWaves) void mx_small_kernel(MxArgs p) {
+  __shared__ float part[kMxSmallWaves][64][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n0 = blockIdx.x * 16, m0 = blockIdx.y * 16;
+  const size_t rowb = (size_t)(p.Kp >> 1), rows = (size_t)(p.Kp >> 5);
+  const int steps = p.Kp >> 7;
+  const int r16 = lane & 15, q = lane >> 4;
+  const uint8_t* gA = p.A + (size_t)min(m0 + r16, p.M - 1) * rowb + q * 16;
+  const uint8_t* gB = p.B + (size_t)(n0 + r16) * rowb + q * 16;                     // N % 16 == 0: always in range
+  const uint8_t* gSA = p.SFA + (size_t)min(m0 + r16, p.M - 1) * rows;
+  const uint8_t* gSB = p.SFB + (size_t)(n0 + r16) * rows;
+  const int sh = 8 * q;
+  f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int s0 = wave; s0 < steps; s0 += kMxSmallWaves * kMxSmallUnroll) {
+    i32x4 a[kMxSmallUnroll], b[kMxSmallUnroll];
+    uint32_t sa[kMxSmallUnroll], sb[kMxSmallUnroll];
+#pragma unroll
+    for (int u = 0; u < kMxSmallUnroll; ++u) {
+      const int s = min(s0 + u * kMxSmallWaves, steps - 1);      // clamped loads; the MFMA of a step past the end is skipped
+      b[u] = ARCQ_WLOAD(reinterpret_cast<const i32x4*>(gB + (size_t)s * 64));
+      sb[u] = ARCQ_WLOAD(reinterpret_cast<const uint32_t*>(gSB + (size_t)s * 4));
+      a[u] = *reinterpret_cast<const i32x4*>(gA + (size_t)s * 64);
+      sa[u] = *reinterpret_cast<const uint32_t*>(gSA + (size_t)s * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < kMxSmallUnroll; ++u)
+      if (s0 + u * kMxSmallWaves < steps)
+        acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(frag(a[u]), frag(b[u]), acc, 4, 4, 0, (int)(sa[u] >> sh), 0,
+                                                               (int)(sb[u] >> sh));
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) part[wave][lane][r] = acc[r];
+  __syncthreads();
+  if (wave != 0) return;
+  const float alpha = p.alpha_host * (p.alpha_dev ? *p.alpha_dev : 1.0f);
+  const int n = n0 + r16;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float t = part[0][lane][r];
+#pragma unroll
+    for (int w = 1; w < kMxSmallWaves; ++w) t += part[w][lane][r];
+    const int m = m0 + 4 * q + r;
+    if (m < p.M) mx_store(p, alpha, m, n, t);
+  }
+}
+
+int gemm_mx(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t Kp,
+            float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, hipStream_t stream) {
+  MxArgs p;
+  p.A = A; p.B = B; p.SFA = SFA; p.SFB = SFB; p.D = D;
+  p.M = (int)M; p.N = (int)N; p.Kp = (int)Kp;
+  p.alpha_host = alpha_host; p.alpha_dev = alpha_dev;
+  p.bias = (const uint16_t*)bias; p.residual = (const uint16_t*)residual; p.out_dtype = out_dtype;
+  if (M <= kMxSmallM)
+    hipLaunchKernelGGL(mx_small_kernel, dim3((unsigned)(N / 16), (unsigned)((M + 15) / 16)), dim3(64 * kMxSmallWaves), 0, stream, p);
+  else
+    hipLaunchKernelGGL(mx_tile_kernel, dim3((unsigned)((N + kMxTile - 1) / kMxTile), (unsigned)((M + kMxTile - 1) / kMxTile)), dim3(256), 0,
+                       stream, p);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_mxfp4: launch failed: %s", hipGetErrorString(e));
+  return ARCQ_OK;
+}
+
+}  // namespace arcq

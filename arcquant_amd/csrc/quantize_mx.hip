@@ -1,0 +1,179 @@
+// Reorder + MXFP4 quantise kernels for gfx950 (activation with ARC residual / weight with duplicate).
+//
+// Format (include/arcq.h, DESIGN.md "MXFP4"): blocks of 32 elements, one E8M0 scale byte each, e2m1 codes packed two per
+// byte (low nibble = even element).  Augmented K is the fake path's concatenation: positions [0, KQ) hold the reordered row,
+// [KQ, K) the residual (x) or a copy (w) of reordered channels [KQ-KE, KQ), [K, Kp) padding (code 0, scale byte 127),
+// Kp = round_up(K, 128) so that every K step of the scaled MFMA is full.
+//
+// Work decomposition: the row structure of quantize.hip -- one workgroup per row (grid-strided), the row staged in LDS with
+// the padded layout of quantize_device.hpp (one pad dword per 16 elements, conflict-free gathers for any permutation),
+// decode-sized inputs additionally split along the row over blockIdx.y.  Thread t owns 32-element blocks t, t + 256, ...
+// of the reordered row: gather 32 values, exponent from the bits, codes, 16-byte store + 1 scale byte; blocks in the
+// outlier tail also emit the residual / duplicate block at KQ/32 + (b - (KQ-KE)/32).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "arcq_device.hpp"
+#include "arcq_internal.hpp"
+#include "quantize_device.hpp"
+
+namespace arcq {
+
+constexpr int kMxThreads = 256;
+
+// Smallest e with amax <= 6 * 2^e, clamped to [-127, 127]; 0 for amax == 0.  Exact, from the fp32 bits of amax (a widened
+// bf16): amax = m * 2^E with m in [1, 2) -> 6 * 2^e = 1.5 * 2^(e+2) >= m * 2^E  <=>  e >= E - 2 when m <= 1.5, else E - 1.
+// Subnormal amax (< 2^-126) always lands on the clamp.
+__device__ __forceinline__ int mx_block_exponent(float amax) {
+  const uint32_t u = __float_as_uint(amax);
+  const int ef = (int)(u >> 23);
+  if (u == 0) return 0;
+  if (ef == 0) return -127;
+  const int E = ef - 127;
+  const int e = (u & 0x7fffffu) <= 0x400000u ? E - 2 : E - 1;
+  return e < -127 ? -127 : (e > 127 ? 127 : e);
+}
+
+struct MxBlock {
+  uint4 packed;   // 32 codes
+  uint32_t s8;    // E8M0 byte = e + 127
+};
+
+// 32 values -> codes.  v * 2^-e is exact (ldexp) and |v * 2^-e| <= 6, so the saturating RNE conversion of
+// quantize_device.hpp never saturates.  kResid: v[] is overwritten with the residual v - deq(code) * 2^e, exact in bf16.
+template <bool kResid>
+__device__ __forceinline__ MxBlock mx_quantize_block(float (&v)[32]) {
+  float amax = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
+  const int e = mx_block_exponent(amax);
+  uint32_t w[4];
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    uint32_t x = 0;
+    x = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(x, __builtin_ldexpf(v[8 * d + 0], -e), __builtin_ldexpf(v[8 * d + 1], -e), 1.0f, 0);
+    x = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(x, __builtin_ldexpf(v[8 * d + 2], -e), __builtin_ldexpf(v[8 * d + 3], -e), 1.0f, 1);
+    x = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(x, __builtin_ldexpf(v[8 * d + 4], -e), __builtin_ldexpf(v[8 * d + 5], -e), 1.0f, 2);
+    x = __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(x, __builtin_ldexpf(v[8 * d + 6], -e), __builtin_ldexpf(v[8 * d + 7], -e), 1.0f, 3);
+    w[d] = x;
+  }
+  if (kResid) {
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      const float q = e2m1_to_f32((w[i >> 3] >> (4 * (i & 7))) & 0xfu);
+      v[i] = v[i] - __builtin_ldexpf(q, e);      // exact: a multiple of ulp_bf16(v) with |res| <= |v|
+    }
+  }
+  MxBlock b;
+  b.packed = make_uint4(w[0], w[1], w[2], w[3]);
+  b.s8 = (uint32_t)(e + 127);
+  return b;
+}
+
+template <bool kModeW>
+__global__ __launch_bounds__(kMxThreads) void mx_quantize_rows_kernel(const uint16_t* __restrict__ X, const int16_t* __restrict__ idx,
+                                                                      uint8_t* __restrict__ Q, uint8_t* __restrict__ SF, int rows, int KQ,
+                                                                      int KE) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint16_t* row_lds = reinterpret_cast<uint16_t*>(smem);
+  const int tid = threadIdx.x;
+  const int K = KQ + KE;
+  const int Kp = (K + 127) & ~127;
+  const int B = KQ >> 5;                 // source blocks of the reordered row
+  const int P = (KQ - KE) >> 5;          // first block of the outlier tail
+  const int Bp = Kp >> 5;                // scale bytes per row
+  const int chunks = KQ >> 3;
+  // blockIdx.y owns a range of the row's blocks (every workgroup stages the whole row: the gather may touch any channel)
+  const int b_per = (B + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int b_begin = (int)blockIdx.y * b_per;
+  const int b_end = min(B, b_begin + b_per);
+  for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+    const uint16_t* xrow = X + (size_t)row * KQ;
+    for (int c = tid; c < chunks; c += kMxThreads) lds_put_chunk(row_lds, c, *reinterpret_cast<const uint4*>(xrow + (size_t)c * 8));
+    __syncthreads();
+    uint8_t* qrow = Q + (size_t)row * (Kp >> 1);
+    uint8_t* srow = SF + (size_t)row * Bp;
+    for (int b = b_begin + tid; b < b_end; b += kMxThreads) {
+      float v[32];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {        // two 16-index loads per half block
+        const uint4 i0 = *reinterpret_cast<const uint4*>(idx + (size_t)b * 32 + h * 16);
+        const uint4 i1 = *reinterpret_cast<const uint4*>(idx + (size_t)b * 32 + h * 16 + 8);
+        const uint32_t iw[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint32_t pw = lds_pad_pair(iw[j]);
+          v[16 * h + 2 * j] = bf16_bits_to_f32(row_lds[pw & 0xffffu]);
+          v[16 * h + 2 * j + 1] = bf16_bits_to_f32(row_lds[pw >> 16]);
+        }
+      }
+      const bool tail = b >= P;
+      const int br = B + (b - P);          // residual / duplicate block
+      if (kModeW) {
+        const MxBlock q = mx_quantize_block<false>(v);
+        *reinterpret_cast<uint4*>(qrow + (size_t)b * 16) = q.packed;
+        srow[b] = (uint8_t)q.s8;
+        if (tail) {
+          *reinterpret_cast<uint4*>(qrow + (size_t)br * 16) = q.packed;
+          srow[br] = (uint8_t)q.s8;
+        }
+      } else if (!tail) {
+        const MxBlock q = mx_quantize_block<false>(v);
+        *reinterpret_cast<uint4*>(qrow + (size_t)b * 16) = q.packed;
+        srow[b] = (uint8_t)q.s8;
+      } else {
+        const MxBlock q = mx_quantize_block<true>(v);
+        *reinterpret_cast<uint4*>(qrow + (size_t)b * 16) = q.packed;
+        srow[b] = (uint8_t)q.s8;
+        const MxBlock r = mx_quantize_block<false>(v);
+        *reinterpret_cast<uint4*>(qrow + (size_t)br * 16) = r.packed;
+        srow[br] = (uint8_t)r.s8;
+      }
+    }
+    // padding blocks [K/32, Kp/32): code 0, scale 2^0 (at most two blocks; written by the workgroup of the row's first range)
+    if (blockIdx.y == 0) {
+      const int pb = (K >> 5) + tid;
+      if (pb < Bp) {
+        *reinterpret_cast<uint4*>(qrow + (size_t)pb * 16) = make_uint4(0, 0, 0, 0);
+        srow[pb] = 127;
+      }
+    }
+    __syncthreads();   // row_lds is rewritten by the next row
+  }
+}
+
+constexpr int kMxMaxBlocks = 2048;
+
+template <bool kModeW>
+static int mx_launch(const void* X, const int16_t* idx, uint8_t* Q, uint8_t* SF, int64_t rows, int64_t KQ, int64_t KE, hipStream_t stream,
+                     const char* who) {
+  if (rows < 0 || KQ <= 0 || (KQ % 64) || (KE % 64) || KE < 0 || KE > KQ || KQ > 32767)
+    return fail(ARCQ_ERR_SHAPE, "%s: need KQ%%64==0, KE%%64==0, 0<=KE<=KQ<=32767 (rows=%lld KQ=%lld KE=%lld)", who, (long long)rows,
+                (long long)KQ, (long long)KE);
+  if (rows == 0) return ARCQ_OK;
+  if (!X || !idx || !Q || !SF) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
+  if (rows > INT32_MAX) return fail(ARCQ_ERR_UNSUPPORTED, "%s: too many rows", who);
+  // 16-byte row / index loads and code stores (Kp/2 is a multiple of 64); scale bytes need no alignment
+  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(Q)) & 15)
+    return fail(ARCQ_ERR_SHAPE, "%s: X, reorder_index and the packed output must be 16-byte aligned", who);
+  const size_t lds = lds_row_bytes((size_t)KQ);
+  const int grid = (int)(rows < kMxMaxBlocks ? rows : kMxMaxBlocks);
+  int split = 1;       // decode: split the row's blocks over up to 16 workgroups of >= 32 blocks each
+  while (grid * split < 256 && split < 16 && (KQ / 32) / (split * 2) >= 32) split *= 2;
+  static LdsOptIn opt;
+  auto kern = mx_quantize_rows_kernel<kModeW>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), opt, (int)lds, who)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid, split), dim3(kMxThreads), lds, stream, (const uint16_t*)X, idx, Q, SF, (int)rows, (int)KQ, (int)KE);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return ARCQ_OK;
+}
+
+int mx_quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, hipStream_t stream) {
+  return mx_launch<false>(X, idx, QX, SFX, M, KQ, KE, stream, "arcq_mx_quantize_x");
+}
+int mx_quantize_w(const void* W, const int16_t* idx, uint8_t* QW, uint8_t* SFW, int64_t N, int64_t KQ, int64_t KE, hipStream_t stream) {
+  return mx_launch<true>(W, idx, QW, SFW, N, KQ, KE, stream, "arcq_mx_quantize_w");
+}
+
+}  // namespace arcq

@@ -4,12 +4,15 @@ Mirrors, with the same names, argument meaning and tuple protocol:
   * ``NVFP4_reorder_quantize_w``  model/qLinearLayer.py:25-28
   * ``NVFP4_reorder_quantize_x``  model/qLlamaLayer.py:73-77 == model/qQwenLayer.py:72-75
   * ``QLinearLayer``              model/qLinearLayer.py:30-78  (forward takes ``(qx, scale_x, scale, bsz, q_len)``)
+  * ``MXFP4_reorder_quantize_{w,x}``  the packed form of the reference's MXFP4 branch (model/quantize.py:219-268 as called by
+    the commented-out model/qLinearLayer.py:58 and model/qQwenLayer.py:81-83), on the block-scaled fp4 MFMA
 
 so that the decoder-layer wrappers of the reference (qLlamaLayer.py / qQwenLayer.py) run unchanged on
 top of ``arcquant_amd.agemm``.  What differs from the reference, deliberately:
   * no ``torch.cuda.synchronize()`` after every op and no ``.item()`` on the scale: the per-tensor scales
     stay on the device (0-dim fp32 tensors) and everything is ordered on torch's current stream;
-  * only ``quant_type='NVFP4'`` is built (the other types are the reference's fake-quant study paths).
+  * ``quant_type`` 'NVFP4' and 'MXFP4' are built; 'INT4' (a fake-quant study path of the reference) is not.
+    MXFP4 is real packed e2m1 + E8M0 data here, where the reference dequantises it in place (DESIGN.md "MXFP4").
 """
 from __future__ import annotations
 
@@ -36,11 +39,32 @@ def NVFP4_reorder_quantize_x(x: torch.Tensor, reorder_index: torch.Tensor, selec
     return qx, scale_x, scale
 
 
+def _unit_scale(t: torch.Tensor) -> torch.Tensor:
+    # the reference's MXFP4 branch uses scale = 1.0 (model/quantize.py:225-227,251-253): E8M0 covers the bf16 range
+    return torch.ones((), dtype=torch.float32, device=t.device)
+
+
+def MXFP4_reorder_quantize_w(w: torch.Tensor, reorder_index: torch.Tensor, select_num: int):
+    """(qw [N, Kp/2], scale_w [N, Kp/32] E8M0, scale = 1): the weight reordered, with copies of its last ``select_num``
+    reordered channels (the form of model/qLinearLayer.py:58)."""
+    qw, scale_w = agemm.mx_reorder_quantize_w(w.contiguous(), reorder_index, select_num)
+    return qw, scale_w, _unit_scale(w)
+
+
+def MXFP4_reorder_quantize_x(x: torch.Tensor, reorder_index: torch.Tensor, select_num: int):
+    """(qx [M, Kp/2], scale_x [M, Kp/32] E8M0, scale = 1): the activation reordered, with the quantised residual of its last
+    ``select_num`` reordered channels (model/qQwenLayer.py:81-83)."""
+    qx, scale_x = agemm.mx_reorder_quantize_x(x.contiguous(), reorder_index, select_num)
+    return qx, scale_x, _unit_scale(x)
+
+
 def reorder_quantize_x(x, reorder_index, select_num, quant_type="NVFP4"):
-    """model/qLlamaLayer.py:79-86 (NVFP4 branch)."""
-    if quant_type != "NVFP4":
-        raise NotImplementedError("only the NVFP4 path is part of the MI355X hot path")
-    return NVFP4_reorder_quantize_x(x, reorder_index, select_num)
+    """model/qLlamaLayer.py:79-86."""
+    if quant_type == "NVFP4":
+        return NVFP4_reorder_quantize_x(x, reorder_index, select_num)
+    if quant_type == "MXFP4":
+        return MXFP4_reorder_quantize_x(x, reorder_index, select_num)
+    raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4 and MXFP4 are)")
 
 
 def find_qlinear_layers(module, name=""):
@@ -65,8 +89,10 @@ class QLinearLayer(nn.Module):
         an LDS-transposing kernel: there up to fp32 summation order); ``agemm.unrepack_w(RW, RSF, ...)`` rebuilds the
         reference-layout pair."""
         super().__init__()
-        if quant_type != "NVFP4":
-            raise NotImplementedError("only quant_type='NVFP4' is supported")
+        if quant_type not in ("NVFP4", "MXFP4"):
+            raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4 and MXFP4 are)")
+        if quant_type == "MXFP4" and (repack_for_decode or repacked_only):
+            raise ValueError("repack_for_decode / repacked_only apply to the NVFP4 weight layout only, not to quant_type='MXFP4'")
         self.in_features = originalLayer.in_features
         self.out_features = originalLayer.out_features
         if originalLayer.bias is not None:
@@ -80,7 +106,8 @@ class QLinearLayer(nn.Module):
             raise RuntimeError("QLinearLayer: the weight must be on the GPU (quantisation runs there)")
         idx = reorder_index.to(device=dev, dtype=torch.int16)
         w = originalLayer.weight.data.to(torch.bfloat16)
-        W, scale_w, scale = NVFP4_reorder_quantize_w(w, idx, self.select_num)
+        quantize_w = MXFP4_reorder_quantize_w if quant_type == "MXFP4" else NVFP4_reorder_quantize_w
+        W, scale_w, scale = quantize_w(w, idx, self.select_num)
         RW, RSF = agemm.repack_w(W, scale_w) if (repack_for_decode or repacked_only) else (None, None)
         if repacked_only:
             W = scale_w = None
@@ -96,7 +123,9 @@ class QLinearLayer(nn.Module):
         # `y = matmul(...); y = y + bias` (model/qLinearLayer.py:74-76): the bias add runs in the GEMM epilogue with the same
         # two roundings (the bf16 product, then the bf16 sum), so the result is bit-identical to the two torch steps
         bias = self.bias if self.bias is None or self.bias.dtype == torch.bfloat16 else None
-        if self.W is None:
+        if self.quant_type == "MXFP4":
+            y = agemm.mx_matmul(qx, self.W, scale_x, self.scale_w, scale * self.scale, bias=bias)
+        elif self.W is None:
             y = agemm.matmul_rw(qx, self.RW, scale_x, self.RSF, scale * self.scale, self.out_features, bias=bias)
         elif getattr(self, "RW", None) is not None and agemm.repacked_supported(qx.shape[0], self.out_features, qx.shape[1] * 2):
             y = agemm.matmul_repacked(qx, self.RW, scale_x, self.RSF, scale * self.scale, self.out_features, bias=bias)

@@ -264,6 +264,40 @@ int arcq_linear_dynamic_repacked(const void *X, const int16_t *reorder_index, co
                                  int64_t KE, int variant, float alpha_host, const void *bias, const void *residual, int out_dtype,
                                  void *stream);
 
+/* ---- MXFP4 (quant_type='MXFP4' of the reference, model/quantize.py:94-122,219-268) ----------------------------------------
+ * MXFP4-ARC, the packed form of the reference's fake MXFP4 path (DESIGN.md "MXFP4"):
+ *   shape      KQ % 64 == 0, KE % 64 == 0, 0 <= KE <= KQ <= 32767, reorder_index an int16 permutation of 0..KQ-1;
+ *              K = KQ + KE, Kp = arcq_mx_k_padded(K) = round_up(K, 128) (every K step of the scaled MFMA is full)
+ *   augmented K concatenation: [0, KQ) the reordered row xr[c] = X[row, idx[c]]; [KQ, K) for activations the residual of
+ *              reordered channels [KQ-KE, KQ), for weights a copy of those channels' codes and scales; [K, Kp) padding,
+ *              code 0 and scale byte 127
+ *   codes      [rows, Kp/2] u8, low nibble = even element
+ *   scales     [rows, Kp/32] u8 E8M0, row-major: byte b means 2^(b-127); 255 is never written.  No swizzle, no per-tensor scale
+ *   block      32 elements v (bf16 widened to fp32), amax = max|v|: e = clamp(ceil(log2(amax/6)), -127, 127) computed exactly
+ *              (the smallest integer with amax <= 6 * 2^e; 0 for an all-zero block); code = e2m1_RNE(v * 2^-e), ties to the
+ *              even code, sign of zero kept, never saturating
+ *   residual   res = v - deq(code) * 2^e, exact in bf16; its blocks are quantised like any other block */
+int64_t arcq_mx_k_padded(int64_t K);                /* round_up(K, 128) (0 for K <= 0) */
+int64_t arcq_mx_sf_bytes(int64_t rows, int64_t K);  /* rows * arcq_mx_k_padded(K) / 32 */
+
+/* X [M,KQ] bf16, reorder_index [KQ] int16, QX [M, Kp/2] u8, SFX [M, Kp/32] u8.  X, reorder_index and QX 16-byte aligned.
+ * Status: ARCQ_ERR_SHAPE for a shape outside the contract or a misaligned pointer, ARCQ_ERR_NULL for a NULL pointer (M > 0). */
+int arcq_mx_quantize_x(const void *X, const int16_t *reorder_index, uint8_t *QX, uint8_t *SFX, int64_t M, int64_t KQ, int64_t KE,
+                       void *stream);
+/* as above; the slots [KQ, K) are copies of the codes and scales of reordered channels [KQ-KE, KQ) */
+int arcq_mx_quantize_w(const void *W, const int16_t *reorder_index, uint8_t *QW, uint8_t *SFW, int64_t N, int64_t KQ, int64_t KE,
+                       void *stream);
+
+/* D[m,n] = alpha * sum_{k<K} deq(A[m,k]) * deq(B[n,k]), fp32 accumulation, on the block-scaled fp4 MFMA.
+ *   A [M, K/2], B [N, K/2] codes and SFA [M, K/32], SFB [N, K/32] scales as written by the quantisers; K = Kp (K % 128 == 0);
+ *   any M >= 0; N % 16 == 0.  alpha, bias, residual (may alias D) and out_dtype: arcq_gemm_nvfp4's contract and roundings.
+ *   workspace / workspace_bytes: unused (no configuration needs scratch), may be NULL / 0.
+ *   Status: ARCQ_ERR_SHAPE for K % 128, N % 16, a bad out_dtype or a misaligned pointer (A, B, D 16 bytes; SFA, SFB 4 bytes;
+ *   bias, residual 2 bytes), ARCQ_ERR_NULL for a NULL operand; M == 0 or N == 0 returns ARCQ_OK; all before any HIP call. */
+int arcq_gemm_mxfp4(const uint8_t *A, const uint8_t *B, const uint8_t *SFA, const uint8_t *SFB, void *D, int64_t M, int64_t N,
+                    int64_t K, float alpha_host, const float *alpha_dev, const void *bias, const void *residual, int out_dtype,
+                    void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
