@@ -17,13 +17,12 @@ Differences a caller can observe, all deliberate (DESIGN.md "deviations"):
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 
 from . import _lib
 from ._lib import VARIANT_G16, VARIANT_G32, OUT_BF16, OUT_F32, ArcqError  # noqa: F401  (re-exported)
-
-
-import functools
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
@@ -33,7 +32,7 @@ def _stream(t: torch.Tensor) -> int:
     # saves ~1.5 us per call over building a torch.cuda.Stream object; an eager decode step makes ~170 of these calls and is
     # host-paced (tools/host_overhead.py)
     if _raw_stream is not None:
-        return _raw_stream(t.device.index if t.device.index is not None else torch.cuda.current_device())
+        return _raw_stream(t.get_device())             # (a GPU tensor always knows its index)
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
@@ -55,16 +54,81 @@ class _on:
         return False
 
 
+# Every function validates in one order: dtype / rank / contiguity of its tensors (_need), the shape and size relations between them, out_dtype,
+# the optional tensors (_out, _opt, _slots: dtype, rank, contiguity and shape at once), and LAST where everything lives (_same_device).  So
+# every rejection but the last is reachable with CPU tensors, and a call built from CPU tensors cannot get as far as a launch.  Shape rules
+# of the kernels themselves (K % 64, alignment, size limits) are the C-ABI's.
+
 def _need(t: torch.Tensor, dtype, name: str, ndim=None):
     # the reference's data_ptr<T>() throws c10::Error on a dtype mismatch; we raise RuntimeError
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+    if getattr(t, "dtype", None) is not dtype:            # (dtypes are singletons; whatever is not a tensor has none of them)
         raise RuntimeError(f"agemm: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
-    if not t.is_cuda:
-        raise RuntimeError(f"agemm: {name} must live on the GPU (there is no CPU path)")
     if ndim is not None and t.dim() != ndim:
         raise RuntimeError(f"agemm: {name} must be {ndim}-D, got shape {tuple(t.shape)}")
     if not t.is_contiguous():
         raise RuntimeError(f"agemm: {name} must be contiguous")
+
+
+def _opt(t, dtype, name, shape):
+    if t is None:
+        return None
+    _need(t, dtype, name, len(shape))
+    if t.shape != shape:
+        raise RuntimeError(f"agemm: {name} must have shape {shape}")
+    return t.data_ptr()
+
+
+def _slots(t, who):
+    # abs-max words left by a producing kernel -> (pointer, count)
+    if t is None:
+        return None, 0
+    _need(t, torch.int32, "absmax_slots", 1)
+    if t.numel() == 0:
+        raise RuntimeError(f"agemm.{who}: absmax_slots must not be empty")
+    return t.data_ptr(), t.numel()
+
+
+def _alpha(scale, scale_host):
+    # the reference's ``scale`` -> (host factor, device tensor or None, its address): a 1-element fp32 device tensor is read on the device,
+    # anything else is a host float
+    if isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1:
+        return float(scale_host), scale, scale.data_ptr()
+    return float(scale_host) * float(scale), None, None   # CPU tensor or other dtype: same as the reference's __float__
+
+
+def _alpha_as_f32(scale, scale_host):
+    # the SiLU-epilogue GEMMs read ANY device ``scale`` tensor on the device, as fp32
+    if isinstance(scale, torch.Tensor) and scale.is_cuda:
+        scale = scale.reshape(-1)[:1].to(torch.float32)
+        return float(scale_host), scale, scale.data_ptr()
+    return float(scale_host) * float(scale), None, None
+
+
+_OUT_CODES = {torch.bfloat16: OUT_BF16, torch.float32: OUT_F32}
+
+
+def _out(out, M, N, out_dtype, like, who):
+    # -> (the caller's ``out`` if it is [M, N] of out_dtype, else a new tensor next to ``like``; the C-ABI's code of out_dtype)
+    code = _OUT_CODES.get(out_dtype)
+    if code is None:
+        raise RuntimeError(f"agemm.{who}: out_dtype must be bfloat16 or float32")
+    if out is None:
+        return torch.empty((M, N), dtype=out_dtype, device=like.device), code
+    _need(out, out_dtype, "out", 2)
+    if out.shape != (M, N):
+        raise RuntimeError(f"agemm.{who}: out has the wrong shape, expected ({M}, {N})")
+    return out, code
+
+
+def _same_device(who: str, A: torch.Tensor, *ts):
+    # the device guard and the stream of a call are those of its first operand: a tensor elsewhere would hand the kernel a pointer it cannot read
+    # (get_device(): the GPU's index, -1 on the CPU; it costs half of comparing torch.device objects, and a decode step makes ~170 calls)
+    idx = A.get_device()
+    if idx < 0:
+        raise RuntimeError(f"agemm.{who}: the operands must live on the GPU (there is no CPU path)")
+    for t in ts:
+        if t is not None and t.get_device() != idx:
+            raise RuntimeError(f"agemm.{who}: every operand must live on the GPU of the first one ({A.device}), got {t.device}")
 
 
 @functools.lru_cache(maxsize=None)
@@ -90,6 +154,16 @@ def _repacked_bytes(N: int, K: int):
     return int(L.arcq_repacked_w_bytes(N, K)), int(L.arcq_repacked_sf_bytes(N, K))
 
 
+def _need_repacked(RW, RSF, SFA, M, N, K, who, n_mult=1):
+    # (RW, RSF) is the repacked weight of N rows over this K (n_mult > 1: whose rows interleave gate and up), SFA the scales of A [M, K] or None
+    _need(RW, torch.uint8, "RW", 1)
+    _need(RSF, torch.uint8, "RSF", 1)
+    if K % 64 or N % n_mult or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
+        raise RuntimeError(f"Value error in {who}: RW / RSF do not belong to a [{N}, {K}] weight" + (f", or N % {n_mult} != 0" if n_mult > 1 else ""))
+    if SFA is not None and SFA.numel() < _sf_used(M, K):
+        raise RuntimeError(f"Value error in {who}: SFA smaller than the swizzled layout of A")
+
+
 def _quantize(fn_name: str, X: torch.Tensor, reorder_index: torch.Tensor, KE: int, variant):
     _need(X, torch.bfloat16, "X" if fn_name.endswith("_x") else "W", 2)
     _need(reorder_index, torch.int16, "reorder_index", 1)
@@ -102,6 +176,7 @@ def _quantize(fn_name: str, X: torch.Tensor, reorder_index: torch.Tensor, KE: in
         variant = variant_for_kq(KQ)
     if KQ % 64 or KE % 64 or KE < 0 or KE > KQ:
         raise RuntimeError(f"Value error in {fn_name}: KQ={KQ}, KE={KE} is not valid")
+    _same_device(fn_name, X, reorder_index)
     Q = torch.empty((rows, K // 2), dtype=torch.uint8, device=X.device)
     SF = torch.empty((sf_buffer_bytes(rows, K),), dtype=torch.uint8, device=X.device)
     L = _lib.lib()
@@ -137,6 +212,7 @@ def rmsnorm_quantize_x(X: torch.Tensor, W: torch.Tensor, eps: float, reorder_ind
         variant = variant_for_kq(KQ)
     if KQ % 64 or KE % 64 or KE < 0 or KE > KQ or not (2048 <= KQ <= 8192):
         raise RuntimeError(f"Value error in run_rmsnorm_x_bf16_nvfp4: K value is not valid: {KQ}")
+    _same_device("rmsnorm_quantize_x", X, W, reorder_index)
     QX = torch.empty((M, K // 2), dtype=torch.uint8, device=X.device)
     SFX = torch.empty((sf_buffer_bytes(M, K),), dtype=torch.uint8, device=X.device)
     with _on(X.device):
@@ -163,45 +239,20 @@ def matmul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: torch.Tenso
     M, N, K = A.shape[0], B.shape[0], A.shape[1] * 2       # bindings.cpp:107-109
     if B.shape[1] * 2 != K:
         raise RuntimeError(f"agemm.matmul: A has K={K}, B has K={B.shape[1] * 2}")
-    L = _lib.lib()
     if SFA.numel() < _sf_used(M, K) or SFB.numel() < _sf_used(N, K):
-        raise RuntimeError("agemm.matmul: scale-factor buffer smaller than the swizzled layout of its operand")
-    alpha_host, alpha_dev = float(scale_host), None
-    if isinstance(scale, torch.Tensor):
-        if scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1:
-            alpha_dev = scale
-        else:
-            alpha_host *= float(scale)         # CPU tensor or other dtype: same as the reference's __float__
-    else:
-        alpha_host *= float(scale)
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise RuntimeError("agemm.matmul: out_dtype must be bfloat16 or float32")
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=A.device)
-    else:
-        _need(out, out_dtype, "out", 2)
-        if tuple(out.shape) != (M, N):
-            raise RuntimeError("agemm.matmul: out has the wrong shape")
-    if bias is not None:
-        _need(bias, torch.bfloat16, "bias", 1)
-        if bias.numel() != N:
-            raise RuntimeError("agemm.matmul: bias must have N entries")
-    if residual is not None:
-        _need(residual, torch.bfloat16, "residual", 2)
-        if tuple(residual.shape) != (M, N):
-            raise RuntimeError("agemm.matmul: residual must be [M, N]")
+        raise RuntimeError("agemm.matmul: SFA / SFB smaller than the swizzled layout of its operand")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, A, "matmul")
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device("matmul", A, B, SFA, SFB, alpha_dev, out, bias, residual)
+    L = _lib.lib()
     ws_bytes = int(L.arcq_gemm_workspace_bytes(M, N, K))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=A.device) if ws_bytes else None
     with _on(A.device):
         st = L.arcq_gemm_nvfp4(A.data_ptr(), B.data_ptr(), SFA.data_ptr(), SFB.data_ptr(), out.data_ptr(), M, N, K,
-                               alpha_host, alpha_dev.data_ptr() if alpha_dev is not None else None,
-                               bias.data_ptr() if bias is not None else None,
-                               residual.data_ptr() if residual is not None else None,
-                               OUT_BF16 if out_dtype == torch.bfloat16 else OUT_F32,
-                               ws.data_ptr() if ws is not None else None, ws_bytes, _stream(A))
+                               alpha_host, alpha_p, bias_p, residual_p, oc, ws.data_ptr() if ws_bytes else None, ws_bytes, _stream(A))
     _lib.check(st, "matmul")
     return out
-
 
 
 # ---- MXFP4 (quant_type='MXFP4'; include/arcq.h "MXFP4", DESIGN.md "MXFP4") ----------------------------------------------------
@@ -212,28 +263,17 @@ def mx_k_padded(K: int) -> int:
     return int(_lib.lib().arcq_mx_k_padded(int(K)))
 
 
-def _mx_shape_first(*named):
-    # dtype and shape are checked before the device, so that a CPU tensor of the wrong dtype or shape is told what is wrong with it
-    for t, dtype, name, ndim in named:
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-            raise RuntimeError(f"agemm: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
-        if t.dim() != ndim:
-            raise RuntimeError(f"agemm: {name} must be {ndim}-D, got shape {tuple(t.shape)}")
-
-
 def _mx_quantize(fn_name: str, X: torch.Tensor, reorder_index: torch.Tensor, KE: int):
     xname = "X" if fn_name.endswith("_x") else "W"
-    _mx_shape_first((X, torch.bfloat16, xname, 2), (reorder_index, torch.int16, "reorder_index", 1))
+    _need(X, torch.bfloat16, xname, 2)
+    _need(reorder_index, torch.int16, "reorder_index", 1)
     rows, KQ = X.shape
     KE = int(KE)
     if reorder_index.numel() != KQ:
         raise RuntimeError(f"agemm: reorder_index has {reorder_index.numel()} entries, expected {KQ}")
     if KQ % 64 or KE % 64 or KE < 0 or KE > KQ or KQ > 32767:
         raise RuntimeError(f"Value error in {fn_name}: KQ={KQ}, KE={KE} is not valid")
-    _need(X, torch.bfloat16, xname, 2)
-    _need(reorder_index, torch.int16, "reorder_index", 1)
-    if reorder_index.device != X.device:
-        raise RuntimeError(f"agemm.{fn_name}: reorder_index must live on {X.device}, got {reorder_index.device}")
+    _same_device(fn_name, X, reorder_index)
     Kp = mx_k_padded(KQ + KE)
     Q = torch.empty((rows, Kp // 2), dtype=torch.uint8, device=X.device)
     SF = torch.empty((rows, Kp // 32), dtype=torch.uint8, device=X.device)
@@ -261,7 +301,8 @@ def mx_matmul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: torch.Te
     """D = scale * deq(A) . deq(B)^T on the block-scaled fp4 MFMA -> [M, N] (bf16, or fp32 with ``out_dtype``).
     ``matmul``'s semantics for ``scale`` (float or 0-dim fp32 device tensor), ``bias``, ``residual`` (may alias ``out``),
     ``out`` and ``scale_host``.  N % 16 == 0."""
-    _mx_shape_first((A, torch.uint8, "A", 2), (B, torch.uint8, "B", 2), (SFA, torch.uint8, "SFA", 2), (SFB, torch.uint8, "SFB", 2))
+    for t, name in ((A, "A"), (B, "B"), (SFA, "SFA"), (SFB, "SFB")):
+        _need(t, torch.uint8, name, 2)
     M, N, K = A.shape[0], B.shape[0], A.shape[1] * 2
     if B.shape[1] * 2 != K:
         raise RuntimeError(f"agemm.mx_matmul: A has K={K}, B has K={B.shape[1] * 2}")
@@ -271,40 +312,23 @@ def mx_matmul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: torch.Te
         raise RuntimeError(f"agemm.mx_matmul: N={N} must be a multiple of 16")
     if tuple(SFA.shape) != (M, K // 32) or tuple(SFB.shape) != (N, K // 32):
         raise RuntimeError("agemm.mx_matmul: SFA / SFB must be [rows, K/32]")
-    for t, name in ((A, "A"), (B, "B"), (SFA, "SFA"), (SFB, "SFB")):
-        _need(t, torch.uint8, name, 2)
-    _same_device("mx_matmul", A, B, SFA, SFB, scale if isinstance(scale, torch.Tensor) and scale.is_cuda else None, bias, residual, out)
-    alpha_host, alpha_dev = _alpha(scale, scale_host)
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise RuntimeError("agemm.mx_matmul: out_dtype must be bfloat16 or float32")
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=A.device)
-    else:
-        _need(out, out_dtype, "out", 2)
-        if tuple(out.shape) != (M, N):
-            raise RuntimeError("agemm.mx_matmul: out has the wrong shape")
-    if bias is not None:
-        _need(bias, torch.bfloat16, "bias", 1)
-        if bias.numel() != N:
-            raise RuntimeError("agemm.mx_matmul: bias must have N entries")
-    if residual is not None:
-        _need(residual, torch.bfloat16, "residual", 2)
-        if tuple(residual.shape) != (M, N):
-            raise RuntimeError("agemm.mx_matmul: residual must be [M, N]")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, A, "mx_matmul")
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device("mx_matmul", A, B, SFA, SFB, alpha_dev, out, bias, residual)
     with _on(A.device):
         st = _lib.lib().arcq_gemm_mxfp4(A.data_ptr(), B.data_ptr(), SFA.data_ptr(), SFB.data_ptr(), out.data_ptr(), M, N, K,
-                                        alpha_host, alpha_dev.data_ptr() if alpha_dev is not None else None,
-                                        bias.data_ptr() if bias is not None else None,
-                                        residual.data_ptr() if residual is not None else None,
-                                        OUT_BF16 if out_dtype == torch.bfloat16 else OUT_F32, None, 0, _stream(A))
+                                        alpha_host, alpha_p, bias_p, residual_p, oc, None, 0, _stream(A))
     _lib.check(st, "mx_matmul")
     return out
+
 
 def absmax_scale(X: torch.Tensor) -> torch.Tensor:
     """Extension: ``max|X| / (448*6)`` as a 0-dim fp32 device tensor, no host sync.
     Equals ``torch.max(x.abs()).float() / (448.0*6.0)`` of model/qLlamaLayer.py:74 bit for bit (0-dim, so that
     ``x / scale`` keeps x's dtype exactly as with the reference's scalar tensor)."""
     _need(X, torch.bfloat16, "X")
+    _same_device("absmax_scale", X)
     out = torch.empty((1,), dtype=torch.float32, device=X.device)
     with _on(X.device):
         st = _lib.lib().arcq_absmax_scale(X.data_ptr(), X.numel(), out.data_ptr(), _stream(X))
@@ -315,91 +339,41 @@ def absmax_scale(X: torch.Tensor) -> torch.Tensor:
 _dyn_state = {}
 
 
-class _NoIndex:
-    # reorder_index=None (arcq_quantize_x_dyn_slots only): X is already in reordered channel order, NULL at the C-ABI
-    @staticmethod
-    def data_ptr():
-        return None
-
-
 def _quantize_dynamic(entry: str, who: str, X: torch.Tensor, KQ: int, reorder_index, KE: int, variant, slots=None, layout=None):
     M = X.shape[0]
     KE = int(KE)
     K = KQ + KE
     if variant is None:
         variant = variant_for_kq(KQ)
-    if reorder_index is None:
+    if reorder_index is None:          # X is already in reordered channel order: NULL at the C-ABI (arcq_quantize_x_dyn_slots only)
         if entry != "arcq_quantize_x_dyn_slots":
             raise RuntimeError(f"Value error in {who}: reorder_index=None needs absmax_slots")
-        if not X.is_contiguous():
-            raise RuntimeError(f"Value error in {who}: X must be contiguous")
-        reorder_index = _NoIndex
     else:
         _need(reorder_index, torch.int16, "reorder_index", 1)
-    if KQ % 64 or KE % 64 or KE < 0 or KE > KQ or (reorder_index is not _NoIndex and reorder_index.numel() != KQ):
-        raise RuntimeError(f"Value error in {who}: KQ={KQ}, KE={KE} is not valid")
+    if KQ % 64 or KE % 64 or KE < 0 or KE > KQ or (reorder_index is not None and reorder_index.numel() != KQ):
+        raise RuntimeError(f"Value error in {who}: KQ={KQ}, KE={KE} or the length of reorder_index is not valid")
+    slots_p, nslots = _slots(slots, who)
+    _same_device(who, X, reorder_index, slots)
     dev = X.device
-    key = (dev, _stream(X))                # scratch of the abs-max pass: one per device and stream (include/arcq.h)
-    state = _dyn_state.get(key)
-    if state is None:
-        state = _dyn_state[key] = torch.empty(256, dtype=torch.int32, device=dev)
     QX = torch.empty((M, K // 2), dtype=torch.uint8, device=dev)
     SFX = torch.empty((sf_buffer_bytes(M, K),), dtype=torch.uint8, device=dev)
     scale = torch.empty((1,), dtype=torch.float32, device=dev)
+    args = [X.data_ptr(), reorder_index.data_ptr() if reorder_index is not None else None, QX.data_ptr(), SFX.data_ptr(), scale.data_ptr()]
+    if slots is not None:
+        args += [slots_p, nslots]
+    else:
+        key = (dev, _stream(X))            # scratch of the abs-max pass: one per device and stream (include/arcq.h)
+        state = _dyn_state.get(key)
+        if state is None:
+            state = _dyn_state[key] = torch.empty(256, dtype=torch.int32, device=dev)
+        args.append(state.data_ptr())
+    args += [M, KQ, KE, int(variant)]
+    if layout is not None:
+        args.append(int(layout))
     with _on(dev):
-        if slots is not None and layout is not None:
-            st = getattr(_lib.lib(), entry)(X.data_ptr(), reorder_index.data_ptr(), QX.data_ptr(), SFX.data_ptr(), scale.data_ptr(),
-                                            slots.data_ptr(), slots.numel(), M, KQ, KE, int(variant), int(layout), _stream(X))
-        elif slots is not None:
-            st = getattr(_lib.lib(), entry)(X.data_ptr(), reorder_index.data_ptr(), QX.data_ptr(), SFX.data_ptr(), scale.data_ptr(),
-                                            slots.data_ptr(), slots.numel(), M, KQ, KE, int(variant), _stream(X))
-        elif layout is not None:
-            st = getattr(_lib.lib(), entry)(X.data_ptr(), reorder_index.data_ptr(), QX.data_ptr(), SFX.data_ptr(), scale.data_ptr(),
-                                            state.data_ptr(), M, KQ, KE, int(variant), int(layout), _stream(X))
-        else:
-            st = getattr(_lib.lib(), entry)(X.data_ptr(), reorder_index.data_ptr(), QX.data_ptr(), SFX.data_ptr(), scale.data_ptr(),
-                                            state.data_ptr(), M, KQ, KE, int(variant), _stream(X))
+        st = getattr(_lib.lib(), entry)(*args, _stream(X))
     _lib.check(st, who)
     return QX, SFX, scale.reshape(())
-
-
-def _need_bytes(t: torch.Tensor, name: str, ndim: int):
-    # repack_w / unrepack_w: pure data movement, on whatever device the tensors live
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-        raise RuntimeError(f"agemm: {name} must be a torch.uint8 tensor, got {getattr(t, 'dtype', type(t))}")
-    if t.dim() != ndim or not t.is_contiguous():
-        raise RuntimeError(f"agemm: {name} must be a contiguous {ndim}-D tensor, got shape {tuple(t.shape)}")
-
-
-def repack_w(QW: torch.Tensor, SFW: torch.Tensor):
-    """One-time re-layout of a quantised weight for the decode fast path (include/arcq.h, "REPACKED weight"): returns
-    ``(RW, RSF)``.  Pure data movement with torch ops -- codes and scale bytes are those of ``reorder_quantize_w``:
-    RW  = [row blocks of 16][tiles of 128 K][lane = 16*q + r][16 bytes], K padded to a multiple of 256, N to 16;
-    RSF = [row blocks][tile pairs][lane][4 bytes: the lane's two scale bytes in each tile of the pair].
-    ``unrepack_w`` is its inverse; both also run on CPU tensors."""
-    _need_bytes(QW, "QW", 2)
-    _need_bytes(SFW, "SFW", 1)
-    N, K = QW.shape[0], QW.shape[1] * 2
-    if K % 64 or SFW.numel() < _sf_used(N, K):
-        raise RuntimeError("Value error in repack_w: K % 64 != 0 or the scale buffer is too small")
-    dev = QW.device
-    Np, Kp = (N + 15) // 16 * 16, (K + 255) // 256 * 256
-    q = torch.zeros((Np, Kp // 2), dtype=torch.uint8, device=dev)
-    q[:N, : K // 2] = QW
-    # natural [N, K/16] scale matrix out of the swizzled buffer
-    r = torch.arange(N, device=dev).unsqueeze(1)
-    g = torch.arange(K // 16, device=dev).unsqueeze(0)
-    off = ((r // 128) * (K // 64) + g // 4) * 512 + (r % 32) * 16 + ((r // 32) % 4) * 4 + g % 4
-    sf = torch.zeros((Np, Kp // 16), dtype=torch.uint8, device=dev)
-    sf[:N, : K // 16] = SFW[off]
-    RB, T = Np // 16, Kp // 128
-    # codes: [RB, r, T, q, 16 B] -> [RB, T, q, r, 16 B]
-    RW = q.view(RB, 16, T, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(-1)
-    # scales: a tile has 8 groups per row, lane (r, q) owns groups 2q and 2q + 1: [RB, r, T/2, 2 tiles, q, 2] -> [RB, T/2, q, r, tile, 2]
-    RSF = sf.view(RB, 16, T // 2, 2, 4, 2).permute(0, 2, 4, 1, 3, 5).contiguous().view(-1)
-    L = _lib.lib()
-    assert RW.numel() == L.arcq_repacked_w_bytes(N, K) and RSF.numel() == L.arcq_repacked_sf_bytes(N, K)
-    return RW, RSF
 
 
 def _sf_swizzle_offsets(N: int, K: int, dev):
@@ -409,12 +383,39 @@ def _sf_swizzle_offsets(N: int, K: int, dev):
     return ((r // 128) * (K // 64) + g // 4) * 512 + (r % 32) * 16 + ((r // 32) % 4) * 4 + g % 4
 
 
+def repack_w(QW: torch.Tensor, SFW: torch.Tensor):
+    """One-time re-layout of a quantised weight for the decode fast path (include/arcq.h, "REPACKED weight"): returns
+    ``(RW, RSF)``.  Pure data movement with torch ops -- codes and scale bytes are those of ``reorder_quantize_w``:
+    RW  = [row blocks of 16][tiles of 128 K][lane = 16*q + r][16 bytes], K padded to a multiple of 256, N to 16;
+    RSF = [row blocks][tile pairs][lane][4 bytes: the lane's two scale bytes in each tile of the pair].
+    ``unrepack_w`` is its inverse; both also run on CPU tensors."""
+    _need(QW, torch.uint8, "QW", 2)            # (pure data movement: no device rule)
+    _need(SFW, torch.uint8, "SFW", 1)
+    N, K = QW.shape[0], QW.shape[1] * 2
+    if K % 64 or SFW.numel() < _sf_used(N, K):
+        raise RuntimeError("Value error in repack_w: K % 64 != 0 or the scale buffer is too small")
+    dev = QW.device
+    Np, Kp = (N + 15) // 16 * 16, (K + 255) // 256 * 256
+    q = torch.zeros((Np, Kp // 2), dtype=torch.uint8, device=dev)
+    q[:N, : K // 2] = QW
+    # natural [N, K/16] scale matrix out of the swizzled buffer
+    sf = torch.zeros((Np, Kp // 16), dtype=torch.uint8, device=dev)
+    sf[:N, : K // 16] = SFW[_sf_swizzle_offsets(N, K, dev)]
+    RB, T = Np // 16, Kp // 128
+    # codes: [RB, r, T, q, 16 B] -> [RB, T, q, r, 16 B]
+    RW = q.view(RB, 16, T, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+    # scales: a tile has 8 groups per row, lane (r, q) owns groups 2q and 2q + 1: [RB, r, T/2, 2 tiles, q, 2] -> [RB, T/2, q, r, tile, 2]
+    RSF = sf.view(RB, 16, T // 2, 2, 4, 2).permute(0, 2, 4, 1, 3, 5).contiguous().view(-1)
+    assert (RW.numel(), RSF.numel()) == _repacked_bytes(N, K)
+    return RW, RSF
+
+
 def unrepack_w(RW: torch.Tensor, RSF: torch.Tensor, N: int, K: int):
     """The exact inverse of ``repack_w`` (pure data movement with torch ops, on RW's device): returns ``(QW, SFW)`` in the reference
     layout -- QW u8 [N, K/2], SFW u8 [sf_buffer_bytes(N, K)] with every byte outside the swizzled image of N rows zero -- so that a
     layer that keeps only the repacked weight can still export the reference's checkpoint format."""
-    _need_bytes(RW, "RW", 1)
-    _need_bytes(RSF, "RSF", 1)
+    _need(RW, torch.uint8, "RW", 1)
+    _need(RSF, torch.uint8, "RSF", 1)
     N, K = int(N), int(K)
     if N <= 0 or K <= 0 or K % 64 or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
         raise RuntimeError(f"Value error in unrepack_w: RW / RSF do not belong to a [{N}, {K}] weight")
@@ -440,21 +441,6 @@ def rw_route(M: int, N: int, K: int) -> int:
     return int(_lib.lib().arcq_gemm_rw_route(int(M), int(N), int(K)))
 
 
-def _alpha(scale, scale_host):
-    alpha_host, alpha_dev = float(scale_host), None
-    if isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1:
-        alpha_dev = scale
-    else:
-        alpha_host *= float(scale)
-    return alpha_host, alpha_dev
-
-
-def _same_device(who: str, A: torch.Tensor, *ts):
-    for t in ts:
-        if t is not None and t.device != A.device:
-            raise RuntimeError(f"agemm.{who}: every operand must live on A's device ({A.device}), got {t.device}")
-
-
 def matmul_rw(A: torch.Tensor, RW: torch.Tensor, SFA: torch.Tensor, RSF: torch.Tensor, scale, N: int, *, bias=None, residual=None,
               out_dtype=torch.bfloat16, out=None, scale_host: float = 1.0):
     """``matmul`` for EVERY M over the weight as ``repack_w`` left it (one weight copy per layer): same arguments and result as
@@ -462,42 +448,19 @@ def matmul_rw(A: torch.Tensor, RW: torch.Tensor, SFA: torch.Tensor, RSF: torch.T
     ``rw_route`` is 1 and to ``matmul`` where it is 2 or 3 -- but the decode shapes ``matmul`` serves with an LDS-transposing kernel
     (M <= 16 on very long K or very wide N), which agree up to fp32 summation order."""
     _need(A, torch.uint8, "A", 2)
-    _need(RW, torch.uint8, "RW", 1)
     _need(SFA, torch.uint8, "SFA")
-    _need(RSF, torch.uint8, "RSF", 1)
     M, K, N = A.shape[0], A.shape[1] * 2, int(N)
-    if K % 64 or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
-        raise RuntimeError(f"Value error in matmul_rw: RW / RSF do not belong to a [{N}, {K}] weight")
-    if SFA.numel() < _sf_used(M, K):
-        raise RuntimeError("Value error in matmul_rw: SFA smaller than the swizzled layout of A")
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise RuntimeError("agemm.matmul_rw: out_dtype must be bfloat16 or float32")
-    alpha_host, alpha_dev = _alpha(scale, scale_host)
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=A.device)
-    else:
-        _need(out, out_dtype, "out", 2)
-        if tuple(out.shape) != (M, N):
-            raise RuntimeError("agemm.matmul_rw: out has the wrong shape")
-    if bias is not None:
-        _need(bias, torch.bfloat16, "bias", 1)
-        if bias.numel() != N:
-            raise RuntimeError("agemm.matmul_rw: bias must have N entries")
-    if residual is not None:
-        _need(residual, torch.bfloat16, "residual", 2)
-        if tuple(residual.shape) != (M, N):
-            raise RuntimeError("agemm.matmul_rw: residual must be [M, N]")
-    _same_device("matmul_rw", A, RW, SFA, RSF, out, bias, residual, alpha_dev)
+    _need_repacked(RW, RSF, SFA, M, N, K, "matmul_rw")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, A, "matmul_rw")
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device("matmul_rw", A, RW, SFA, RSF, alpha_dev, out, bias, residual)
     L = _lib.lib()
     ws_bytes = int(L.arcq_gemm_rw_workspace_bytes(M, N, K))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=A.device) if ws_bytes else None
     with _on(A.device):
         st = L.arcq_gemm_nvfp4_rw(A.data_ptr(), RW.data_ptr(), SFA.data_ptr(), RSF.data_ptr(), out.data_ptr(), M, N, K, alpha_host,
-                                  alpha_dev.data_ptr() if alpha_dev is not None else None,
-                                  bias.data_ptr() if bias is not None else None,
-                                  residual.data_ptr() if residual is not None else None,
-                                  OUT_BF16 if out_dtype == torch.bfloat16 else OUT_F32,
-                                  ws.data_ptr() if ws is not None else None, ws_bytes, _stream(A))
+                                  alpha_p, bias_p, residual_p, oc, ws.data_ptr() if ws_bytes else None, ws_bytes, _stream(A))
     _lib.check(st, "matmul_rw")
     return out
 
@@ -515,45 +478,22 @@ def matmul_repacked(A: torch.Tensor, RW: torch.Tensor, SFA: torch.Tensor, RSF: t
     ``N`` of the weight): the kernel streams the weight in MFMA operand order with no LDS transpose and no barrier in its
     K loop.  Equals ``matmul`` on the un-repacked operands up to fp32 accumulation order."""
     _need(A, torch.uint8, "A", 2)
-    _need(RW, torch.uint8, "RW", 1)
     _need(SFA, torch.uint8, "SFA")
-    _need(RSF, torch.uint8, "RSF", 1)
     M, K, N = A.shape[0], A.shape[1] * 2, int(N)
-    L = _lib.lib()
-    if K % 64 or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
-        raise RuntimeError(f"Value error in matmul_repacked: RW / RSF do not belong to a [{N}, {K}] weight")
-    if SFA.numel() < _sf_used(M, K):
-        raise RuntimeError("Value error in matmul_repacked: SFA smaller than the swizzled layout of A")
+    _need_repacked(RW, RSF, SFA, M, N, K, "matmul_repacked")
     if not repacked_supported(M, N, K):
         raise RuntimeError(f"matmul_repacked: M={M}, K={K} is outside the repacked path (see repacked_supported)")
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise RuntimeError("agemm.matmul_repacked: out_dtype must be bfloat16 or float32")
-    alpha_host, alpha_dev = float(scale_host), None
-    if isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1:
-        alpha_dev = scale
-    else:
-        alpha_host *= float(scale)
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=A.device)
-    elif tuple(out.shape) != (M, N) or out.dtype != out_dtype or not out.is_contiguous():
-        raise RuntimeError("agemm.matmul_repacked: out has the wrong shape / dtype")
-    if bias is not None:
-        _need(bias, torch.bfloat16, "bias", 1)
-        if bias.numel() != N:
-            raise RuntimeError("agemm.matmul_repacked: bias must have N entries")
-    if residual is not None:
-        _need(residual, torch.bfloat16, "residual", 2)
-        if tuple(residual.shape) != (M, N):
-            raise RuntimeError("agemm.matmul_repacked: residual must be [M, N]")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, A, "matmul_repacked")
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device("matmul_repacked", A, RW, SFA, RSF, alpha_dev, out, bias, residual)
+    L = _lib.lib()
     # kernel="stream": the kernel body of the fused decode linears (rmsnorm_matmul_repacked, dynamic_matmul_repacked), so that
     # quantiser + this call is their bit-exact two-launch equivalent; "auto" = the fastest kernel for plain packed activations
     fn = L.arcq_gemm_nvfp4_repacked_stream if kernel == "stream" else L.arcq_gemm_nvfp4_repacked
     with _on(A.device):
-        st = fn(A.data_ptr(), RW.data_ptr(), SFA.data_ptr(), RSF.data_ptr(), out.data_ptr(), M, N, K, alpha_host,
-                                        alpha_dev.data_ptr() if alpha_dev is not None else None,
-                                        bias.data_ptr() if bias is not None else None,
-                                        residual.data_ptr() if residual is not None else None,
-                                        OUT_BF16 if out_dtype == torch.bfloat16 else OUT_F32, _stream(A))
+        st = fn(A.data_ptr(), RW.data_ptr(), SFA.data_ptr(), RSF.data_ptr(), out.data_ptr(), M, N, K, alpha_host, alpha_p, bias_p, residual_p, oc,
+                _stream(A))
     _lib.check(st, "matmul_repacked")
     return out
 
@@ -571,19 +511,16 @@ def matmul_silu_mul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: to
     if B.shape[1] != A.shape[1] or K % 64 or N % 8:
         raise RuntimeError(f"Value error in matmul_silu_mul: A {tuple(A.shape)} / B {tuple(B.shape)} need equal K, K % 64 == 0, N % 8 == 0")
     if SFA.numel() < _sf_used(M, K) or SFB.numel() < _sf_used(N, K):
-        raise RuntimeError("Value error in matmul_silu_mul: scale buffer too small")
-    alpha_host, alpha_dev = float(scale_host), None
-    if isinstance(scale, torch.Tensor) and scale.is_cuda:
-        alpha_dev = scale.reshape(-1)[:1].to(torch.float32)
-    else:
-        alpha_host *= float(scale)
+        raise RuntimeError("Value error in matmul_silu_mul: SFA / SFB smaller than the swizzled layout of its operand")
+    alpha_host, alpha_dev, alpha_p = _alpha_as_f32(scale, scale_host)
+    bias_p = _opt(bias, torch.bfloat16, "bias", (N,))
+    _same_device("matmul_silu_mul", A, B, SFA, SFB, alpha_dev, bias)
     L = _lib.lib()
     act = torch.empty((M, N // 2), dtype=torch.bfloat16, device=A.device)
     slots = torch.empty((max(1, int(L.arcq_gemm_silu_mul_slots(M, N, K))),), dtype=torch.int32, device=A.device)
     with _on(A.device):
         st = L.arcq_gemm_nvfp4_silu_mul(A.data_ptr(), B.data_ptr(), SFA.data_ptr(), SFB.data_ptr(), act.data_ptr(), slots.data_ptr(), M, N, K,
-                                        alpha_host, alpha_dev.data_ptr() if alpha_dev is not None else None,
-                                        _opt(bias, torch.bfloat16, "bias", (N,)), _stream(A))
+                                        alpha_host, alpha_p, bias_p, _stream(A))
     _lib.check(st, "matmul_silu_mul")
     return act, slots
 
@@ -594,27 +531,18 @@ def matmul_rw_silu_mul(A: torch.Tensor, RW: torch.Tensor, SFA: torch.Tensor, RSF
     ``(act, absmax_slots)`` bit-identical to ``matmul_silu_mul`` on the reference-layout weight.  Decode (M <= 16) has its own
     repacked SiLU paths (``matmul_repacked_silu_absmax``, ``rmsnorm_matmul_repacked_silu``) and raises here."""
     _need(A, torch.uint8, "A", 2)
-    _need(RW, torch.uint8, "RW", 1)
     _need(SFA, torch.uint8, "SFA")
-    _need(RSF, torch.uint8, "RSF", 1)
     M, K, N = A.shape[0], A.shape[1] * 2, int(N)
-    if K % 64 or N % 8 or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
-        raise RuntimeError(f"Value error in matmul_rw_silu_mul: RW / RSF do not belong to a [{N}, {K}] weight, or N % 8 != 0")
-    if SFA.numel() < _sf_used(M, K):
-        raise RuntimeError("Value error in matmul_rw_silu_mul: SFA smaller than the swizzled layout of A")
-    alpha_host, alpha_dev = float(scale_host), None
-    if isinstance(scale, torch.Tensor) and scale.is_cuda:
-        alpha_dev = scale.reshape(-1)[:1].to(torch.float32)
-    else:
-        alpha_host *= float(scale)
+    _need_repacked(RW, RSF, SFA, M, N, K, "matmul_rw_silu_mul", n_mult=8)
+    alpha_host, alpha_dev, alpha_p = _alpha_as_f32(scale, scale_host)
     bias_p = _opt(bias, torch.bfloat16, "bias", (N,))
-    _same_device("matmul_rw_silu_mul", A, RW, SFA, RSF, bias, alpha_dev)
+    _same_device("matmul_rw_silu_mul", A, RW, SFA, RSF, alpha_dev, bias)
     L = _lib.lib()
     act = torch.empty((M, N // 2), dtype=torch.bfloat16, device=A.device)
     slots = torch.empty((max(1, int(L.arcq_gemm_rw_silu_mul_slots(M, N, K))),), dtype=torch.int32, device=A.device)
     with _on(A.device):
         st = L.arcq_gemm_nvfp4_rw_silu_mul(A.data_ptr(), RW.data_ptr(), SFA.data_ptr(), RSF.data_ptr(), act.data_ptr(), slots.data_ptr(), M, N, K,
-                                           alpha_host, alpha_dev.data_ptr() if alpha_dev is not None else None, bias_p, _stream(A))
+                                           alpha_host, alpha_p, bias_p, _stream(A))
     _lib.check(st, "matmul_rw_silu_mul")
     return act, slots
 
@@ -627,7 +555,6 @@ def reorder_quantize_x_dynamic(X: torch.Tensor, reorder_index: torch.Tensor, KE:
     act_scatter_index=)`` stored it so) -- same bytes as the natural-order tensor with the index, without the gather."""
     _need(X, torch.bfloat16, "X", 2)
     if absmax_slots is not None:           # max|X| already known per workgroup (matmul_silu_mul): one launch for any size
-        _need(absmax_slots, torch.int32, "absmax_slots", 1)
         return _quantize_dynamic("arcq_quantize_x_dyn_slots", "reorder_quantize_x_dynamic", X, X.shape[1], reorder_index, KE, variant,
                                  slots=absmax_slots)
     return _quantize_dynamic("arcq_quantize_x_dyn", "reorder_quantize_x_dynamic", X, X.shape[1], reorder_index, KE, variant)
@@ -648,8 +575,6 @@ def silu_mul_quantize_x_dynamic(GU: torch.Tensor, reorder_index: torch.Tensor, K
     if layout not in (GU_HALVES, GU_PAIRS):
         raise RuntimeError("Value error in silu_mul_quantize_x_dynamic: layout must be GU_HALVES or GU_PAIRS")
     if absmax_slots is not None:           # max |silu(gate) * up| words left by matmul_repacked_silu_absmax: ONE launch
-        if absmax_slots.dtype != torch.int32 or not absmax_slots.is_cuda or not absmax_slots.is_contiguous() or absmax_slots.numel() == 0:
-            raise RuntimeError("agemm.silu_mul_quantize_x_dynamic: absmax_slots must be a non-empty contiguous int32 GPU tensor")
         return _quantize_dynamic("arcq_silu_mul_quantize_x_dyn_slots", "silu_mul_quantize_x_dynamic", GU, GU.shape[1] // 2, reorder_index, KE,
                                  variant, slots=absmax_slots, layout=layout)
     return _quantize_dynamic("arcq_silu_mul_quantize_x_dyn", "silu_mul_quantize_x_dynamic", GU, GU.shape[1] // 2, reorder_index, KE,
@@ -663,31 +588,18 @@ def matmul_repacked_silu_absmax(A: torch.Tensor, RW: torch.Tensor, SFA: torch.Te
     16 weight rows holding max |silu(g) * u| of that block's outputs -- what ``silu_mul_quantize_x_dynamic(y, ...,
     layout=GU_PAIRS, absmax_slots=...)`` needs to quantise ``act_fn(gate) * up`` (model/qLlamaLayer.py:417) in ONE launch."""
     _need(A, torch.uint8, "A", 2)
-    _need(RW, torch.uint8, "RW", 1)
     _need(SFA, torch.uint8, "SFA")
-    _need(RSF, torch.uint8, "RSF", 1)
     M, K, N = A.shape[0], A.shape[1] * 2, int(N)
-    L = _lib.lib()
-    if K % 64 or N % 4 or (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
-        raise RuntimeError(f"Value error in matmul_repacked_silu_absmax: RW / RSF do not belong to a [{N}, {K}] weight, or N % 4 != 0")
-    if SFA.numel() < _sf_used(M, K):
-        raise RuntimeError("Value error in matmul_repacked_silu_absmax: SFA smaller than the swizzled layout of A")
+    _need_repacked(RW, RSF, SFA, M, N, K, "matmul_repacked_silu_absmax", n_mult=4)
     if not repacked_supported(M, N, K):
         raise RuntimeError(f"matmul_repacked_silu_absmax: M={M}, K={K} is outside the repacked path (see repacked_supported)")
-    alpha_host, alpha_dev = float(scale_host), None
-    if isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1:
-        alpha_dev = scale
-    else:
-        alpha_host *= float(scale)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=A.device)
-    elif tuple(out.shape) != (M, N) or out.dtype != torch.bfloat16 or not out.is_contiguous():
-        raise RuntimeError("agemm.matmul_repacked_silu_absmax: out has the wrong shape / dtype")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, _ = _out(out, M, N, torch.bfloat16, A, "matmul_repacked_silu_absmax")
+    _same_device("matmul_repacked_silu_absmax", A, RW, SFA, RSF, alpha_dev, out)
     slots = torch.empty(((N + 15) // 16,), dtype=torch.int32, device=A.device)
     with _on(A.device):
-        st = L.arcq_gemm_nvfp4_repacked_silu_absmax(A.data_ptr(), RW.data_ptr(), SFA.data_ptr(), RSF.data_ptr(), out.data_ptr(),
-                                                    slots.data_ptr(), M, N, K, alpha_host,
-                                                    alpha_dev.data_ptr() if alpha_dev is not None else None, _stream(A))
+        st = _lib.lib().arcq_gemm_nvfp4_repacked_silu_absmax(A.data_ptr(), RW.data_ptr(), SFA.data_ptr(), RSF.data_ptr(), out.data_ptr(),
+                                                    slots.data_ptr(), M, N, K, alpha_host, alpha_p, _stream(A))
     _lib.check(st, "matmul_repacked_silu_absmax")
     return out, slots
 
@@ -705,28 +617,14 @@ def fused_supported(kind: int, M: int, N: int, KQ: int, KE: int) -> bool:
 def _fused_common(who, X, reorder_index, RW, RSF, N, KE, variant):
     _need(X, torch.bfloat16, "X", 2)
     _need(reorder_index, torch.int16, "reorder_index", 1)
-    _need(RW, torch.uint8, "RW", 1)
-    _need(RSF, torch.uint8, "RSF", 1)
     M, KQ = X.shape
     KE, N = int(KE), int(N)
-    K = KQ + KE
-    L = _lib.lib()
     if KQ % 64 or KE % 64 or KE < 0 or KE > KQ or reorder_index.numel() != KQ:
-        raise RuntimeError(f"Value error in {who}: KQ={KQ}, KE={KE} is not valid")
-    if (RW.numel(), RSF.numel()) != _repacked_bytes(N, K):
-        raise RuntimeError(f"Value error in {who}: RW / RSF do not belong to a [{N}, {K}] weight")
+        raise RuntimeError(f"Value error in {who}: KQ={KQ}, KE={KE} or the length of reorder_index is not valid")
+    _need_repacked(RW, RSF, None, M, N, KQ + KE, who)
     if variant is None:
         variant = variant_for_kq(KQ)
     return M, KQ, KE, N, int(variant)
-
-
-def _opt(t, dtype, name, shape):
-    if t is None:
-        return None
-    _need(t, dtype, name, len(shape))
-    if tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"agemm: {name} must have shape {tuple(shape)}")
-    return t.data_ptr()
 
 
 def rmsnorm_matmul_repacked(X: torch.Tensor, W: torch.Tensor, eps: float, reorder_index: torch.Tensor, KE: int, RW: torch.Tensor,
@@ -736,26 +634,17 @@ def rmsnorm_matmul_repacked(X: torch.Tensor, W: torch.Tensor, eps: float, reorde
     RMSNorm + quantiser (benchmarks/modeling_arc.py:211-228) runs as the GEMM's prologue, once per CU.  Bit-identical to the
     two calls.  ``W`` is the norm weight, ``scale`` the per-tensor weight scale (float or 0-dim device tensor)."""
     M, KQ, KE, N, variant = _fused_common("rmsnorm_matmul_repacked", X, reorder_index, RW, RSF, N, KE, variant)
-    _need(W, torch.bfloat16, "W", 1)
-    if W.numel() != KQ or not fused_supported(SRC_RMSNORM, M, N, KQ, KE):
+    W_p = _opt(W, torch.bfloat16, "W", (KQ,))
+    if not fused_supported(SRC_RMSNORM, M, N, KQ, KE):
         raise RuntimeError(f"rmsnorm_matmul_repacked: M={M}, KQ={KQ} outside the fused path (see fused_supported)")
-    alpha_host, alpha_dev = float(scale_host), None
-    if isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1:
-        alpha_dev = scale
-    else:
-        alpha_host *= float(scale)
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise RuntimeError("agemm.rmsnorm_matmul_repacked: out_dtype must be bfloat16 or float32")
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=X.device)
-    elif tuple(out.shape) != (M, N) or out.dtype != out_dtype or not out.is_contiguous():
-        raise RuntimeError("agemm.rmsnorm_matmul_repacked: out has the wrong shape / dtype")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, X, "rmsnorm_matmul_repacked")
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device("rmsnorm_matmul_repacked", X, W, reorder_index, RW, RSF, alpha_dev, out, bias, residual)
     with _on(X.device):
-        st = _lib.lib().arcq_linear_rmsnorm_repacked(X.data_ptr(), W.data_ptr(), float(eps), reorder_index.data_ptr(), RW.data_ptr(), RSF.data_ptr(),
-                                                     out.data_ptr(), M, N, KQ, KE, variant, alpha_host,
-                                                     alpha_dev.data_ptr() if alpha_dev is not None else None,
-                                                     _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N)),
-                                                     OUT_BF16 if out_dtype == torch.bfloat16 else OUT_F32, _stream(X))
+        st = _lib.lib().arcq_linear_rmsnorm_repacked(X.data_ptr(), W_p, float(eps), reorder_index.data_ptr(), RW.data_ptr(), RSF.data_ptr(),
+                                                     out.data_ptr(), M, N, KQ, KE, variant, alpha_host, alpha_p, bias_p, residual_p, oc,
+                                                     _stream(X))
     _lib.check(st, "rmsnorm_matmul_repacked")
     return out
 
@@ -789,25 +678,20 @@ def rmsnorm_matmul_repacked_silu(X: torch.Tensor, W: torch.Tensor, eps: float, r
     the down projection's reorder_index the result is ``act[:, reorder_index]`` and the consumer quantises it with
     ``reorder_quantize_x_dynamic(act, None, KE, absmax_slots=slots)``."""
     M, KQ, KE, N, variant = _fused_common("rmsnorm_matmul_repacked_silu", X, reorder_index, RW, RSF, N, KE, variant)
-    _need(W, torch.bfloat16, "W", 1)
-    if W.numel() != KQ or N % 4 or not fused_supported(SRC_RMSNORM, M, N, KQ, KE):
+    W_p = _opt(W, torch.bfloat16, "W", (KQ,))
+    if N % 4 or not fused_supported(SRC_RMSNORM, M, N, KQ, KE):
         raise RuntimeError(f"rmsnorm_matmul_repacked_silu: M={M}, N={N}, KQ={KQ} outside the fused path (see fused_supported; N % 4 == 0)")
-    alpha_host, alpha_dev = float(scale_host), None
-    if isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == 1:
-        alpha_dev = scale
-    else:
-        alpha_host *= float(scale)
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    bias_p, scatter_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(act_scatter_index, torch.int16, "act_scatter_index", (N // 2,))
     if act_scatter_index is not None:
-        _need(act_scatter_index, torch.int16, "act_scatter_index", 1)
         _check_scatter_index(act_scatter_index, N // 2)
+    _same_device("rmsnorm_matmul_repacked_silu", X, W, reorder_index, RW, RSF, alpha_dev, bias, act_scatter_index)
     act = torch.empty((M, N // 2), dtype=torch.bfloat16, device=X.device)
     slots = torch.empty(((N + 15) // 16,), dtype=torch.int32, device=X.device)
     with _on(X.device):
-        st = _lib.lib().arcq_linear_rmsnorm_silu_repacked(X.data_ptr(), W.data_ptr(), float(eps), reorder_index.data_ptr(), RW.data_ptr(),
+        st = _lib.lib().arcq_linear_rmsnorm_silu_repacked(X.data_ptr(), W_p, float(eps), reorder_index.data_ptr(), RW.data_ptr(),
                                                           RSF.data_ptr(), act.data_ptr(), slots.data_ptr(), M, N, KQ, KE, variant, alpha_host,
-                                                          alpha_dev.data_ptr() if alpha_dev is not None else None,
-                                                          _opt(bias, torch.bfloat16, "bias", (N,)),
-                                                          _opt(act_scatter_index, torch.int16, "act_scatter_index", (N // 2,)), _stream(X))
+                                                          alpha_p, bias_p, scatter_p, _stream(X))
     _lib.check(st, "rmsnorm_matmul_repacked_silu")
     return act, slots
 
@@ -821,23 +705,15 @@ def dynamic_matmul_repacked(X: torch.Tensor, reorder_index: torch.Tensor, KE: in
     M, KQ, KE, N, variant = _fused_common("dynamic_matmul_repacked", X, reorder_index, RW, RSF, N, KE, variant)
     if not fused_supported(SRC_DYNAMIC, M, N, KQ, KE):
         raise RuntimeError(f"dynamic_matmul_repacked: M={M}, KQ={KQ} outside the fused path (see fused_supported)")
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise RuntimeError("agemm.dynamic_matmul_repacked: out_dtype must be bfloat16 or float32")
-    if absmax_slots is not None and (absmax_slots.dtype != torch.int32 or not absmax_slots.is_cuda or not absmax_slots.is_contiguous()
-                                     or absmax_slots.numel() == 0):
-        raise RuntimeError("agemm.dynamic_matmul_repacked: absmax_slots must be a non-empty contiguous int32 GPU tensor")
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=X.device)
-    elif tuple(out.shape) != (M, N) or out.dtype != out_dtype or not out.is_contiguous():
-        raise RuntimeError("agemm.dynamic_matmul_repacked: out has the wrong shape / dtype")
+    slots_p, nslots = _slots(absmax_slots, "dynamic_matmul_repacked")
+    out, oc = _out(out, M, N, out_dtype, X, "dynamic_matmul_repacked")
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device("dynamic_matmul_repacked", X, reorder_index, RW, RSF, absmax_slots, out, bias, residual)
     scale = torch.empty((1,), dtype=torch.float32, device=X.device)
     with _on(X.device):
         st = _lib.lib().arcq_linear_dynamic_repacked(X.data_ptr(), reorder_index.data_ptr(), RW.data_ptr(), RSF.data_ptr(), out.data_ptr(),
-                                                     scale.data_ptr(), absmax_slots.data_ptr() if absmax_slots is not None else None,
-                                                     absmax_slots.numel() if absmax_slots is not None else 0, M, N, KQ, KE, variant,
-                                                     float(scale_w), _opt(bias, torch.bfloat16, "bias", (N,)),
-                                                     _opt(residual, torch.bfloat16, "residual", (M, N)),
-                                                     OUT_BF16 if out_dtype == torch.bfloat16 else OUT_F32, _stream(X))
+                                                     scale.data_ptr(), slots_p, nslots, M, N, KQ, KE, variant, float(scale_w), bias_p, residual_p, oc,
+                                                     _stream(X))
     _lib.check(st, "dynamic_matmul_repacked")
     return out, scale.reshape(())
 

@@ -22,18 +22,103 @@
 
 namespace {
 
+// Every function validates in one order (the ctypes mirror's): dtype / rank / contiguity of its tensors (need), the shape and size relations
+// between them, out_dtype, the optional tensors (out_of, opt_ptr: dtype, rank, contiguity and shape at once), and LAST where everything lives
+// (same_device).  So every rejection but the last is reachable with CPU tensors, and a call built from CPU tensors cannot reach a launch.
 void need(const torch::Tensor& t, c10::ScalarType dt, const char* name, int64_t ndim = -1) {
   if (t.scalar_type() != dt) throw std::runtime_error(std::string("agemm: ") + name + " has the wrong dtype");   // reference: data_ptr<T>() throws
-  if (!t.is_cuda()) throw std::runtime_error(std::string("agemm: ") + name + " must live on the GPU (there is no CPU path)");
   if (ndim >= 0 && t.dim() != ndim) throw std::runtime_error(std::string("agemm: ") + name + " has the wrong rank");
   if (!t.is_contiguous()) throw std::runtime_error(std::string("agemm: ") + name + " must be contiguous");
 }
+
+// the device guard and the stream of a call are those of its first operand: a tensor elsewhere would hand the kernel a pointer it cannot read
+void same_device(const char* who, const torch::Tensor& A, std::initializer_list<const torch::Tensor*> ts) {
+  if (!A.is_cuda()) throw std::runtime_error(std::string("agemm.") + who + ": the operands must live on the GPU (there is no CPU path)");
+  for (const torch::Tensor* t : ts)
+    if (t && t->defined() && t->device() != A.device())
+      throw std::runtime_error(std::string("agemm.") + who + ": every operand must live on the GPU of the first one");
+}
+const torch::Tensor* opt_t(const c10::optional<torch::Tensor>& t) { return t.has_value() ? &*t : nullptr; }
 
 void check(int status, const char* what) {
   if (status != ARCQ_OK) throw std::runtime_error(std::string(what) + ": " + arcq_last_error());
 }
 
 void* stream_of(const torch::Tensor& t) { return (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream(); }
+
+// The reference's `scale`: a Python float, or a tensor.  A 1-element fp32 CUDA tensor is consumed on the device (no .item() sync), any other
+// tensor through the reference's implicit __float__.  any_as_f32 (the SiLU-epilogue GEMMs, as the mirror): ANY CUDA tensor is read on the
+// device, as fp32.
+struct Alpha {
+  float host = 1.0f;
+  const float* dev = nullptr;
+  torch::Tensor keep;
+  const torch::Tensor* tensor() const { return keep.defined() ? &keep : nullptr; }
+};
+Alpha alpha_of(const py::object& scale, double scale_host, bool any_as_f32 = false) {
+  Alpha a;
+  a.host = (float)scale_host;
+  if (!THPVariable_Check(scale.ptr())) {
+    a.host *= scale.cast<float>();
+    return a;
+  }
+  const torch::Tensor& t = THPVariable_Unpack(scale.ptr());
+  if (t.is_cuda() && any_as_f32) {
+    a.keep = t.reshape({-1}).slice(0, 0, 1).to(torch::kFloat32);
+  } else if (t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.numel() == 1) {
+    a.keep = t;
+  } else {
+    a.host *= t.item<float>();
+    return a;
+  }
+  a.dev = a.keep.data_ptr<float>();
+  return a;
+}
+const void* opt_ptr(const c10::optional<torch::Tensor>& t, c10::ScalarType dt, const char* name, std::initializer_list<int64_t> shape) {
+  if (!t.has_value()) return nullptr;
+  need(*t, dt, name, (int64_t)shape.size());
+  int i = 0;
+  for (int64_t d : shape)
+    if (t->size(i++) != d) throw std::runtime_error(std::string("agemm: ") + name + " has the wrong shape");
+  return t->data_ptr();
+}
+struct OutDtype {
+  c10::ScalarType dt;
+  int code;
+};
+OutDtype out_dtype_of(const py::object& out_dtype, const char* who) {
+  const auto dt = out_dtype.is_none() ? torch::kBFloat16 : torch::python::detail::py_object_to_dtype(out_dtype);
+  if (dt == torch::kBFloat16) return {dt, ARCQ_OUT_BF16};
+  if (dt == torch::kFloat32) return {dt, ARCQ_OUT_F32};
+  throw std::runtime_error(std::string("agemm.") + who + ": out_dtype must be bfloat16 or float32");
+}
+// the caller's `out` if it is [M, N] of this dtype, else a new tensor next to `like`; same_device then takes it with the other operands
+torch::Tensor out_of(const c10::optional<torch::Tensor>& out, int64_t M, int64_t N, c10::ScalarType dt, const torch::Tensor& like, const char* who) {
+  if (!out.has_value()) return torch::empty({M, N}, like.options().dtype(dt));
+  if (out->dim() != 2 || out->size(0) != M || out->size(1) != N || out->scalar_type() != dt || !out->is_contiguous())
+    throw std::runtime_error(std::string("agemm.") + who + ": out has the wrong shape / dtype");
+  return *out;
+}
+void need_repacked(const torch::Tensor& RW, const torch::Tensor& RSF, int64_t N, int64_t K, const char* who, int64_t n_mult = 1) {
+  need(RW, torch::kUInt8, "RW", 1);
+  need(RSF, torch::kUInt8, "RSF", 1);
+  if (K % 64 || N % n_mult || RW.numel() != arcq_repacked_w_bytes(N, K) || RSF.numel() != arcq_repacked_sf_bytes(N, K))
+    throw std::runtime_error(std::string("Value error in ") + who + ": RW / RSF do not belong to a [N, K] weight of this shape" +
+                             (n_mult > 1 ? ", or N % " + std::to_string(n_mult) + " != 0" : ""));
+}
+// the opening of a GEMM over a repacked weight: A [M, K/2], its scales SFA, and (RW, RSF) of N rows over the same K
+struct GemmShape {
+  int64_t M, K;
+};
+GemmShape open_repacked(const char* who, const torch::Tensor& A, const torch::Tensor& RW, const torch::Tensor& SFA, const torch::Tensor& RSF, int64_t N,
+                        int64_t n_mult = 1) {
+  need(A, torch::kUInt8, "A", 2);
+  need(SFA, torch::kUInt8, "SFA");
+  const GemmShape g{A.size(0), A.size(1) * 2};
+  need_repacked(RW, RSF, N, g.K, who, n_mult);
+  if (SFA.numel() < arcq_sf_used_bytes(g.M, g.K)) throw std::runtime_error(std::string("Value error in ") + who + ": SFA smaller than the swizzled layout of A");
+  return g;
+}
 
 // agemm.matmul(A, B, SFA, SFB, scale) -> bf16 [M, N]   (bindings.cpp:99-120)
 torch::Tensor matmul(const torch::Tensor& A, const torch::Tensor& B, const torch::Tensor& SFA, const torch::Tensor& SFB, const py::object& scale) {
@@ -44,28 +129,16 @@ torch::Tensor matmul(const torch::Tensor& A, const torch::Tensor& B, const torch
   const int64_t M = A.size(0), N = B.size(0), K = A.size(1) * 2;      // bindings.cpp:107-109
   if (B.size(1) * 2 != K) throw std::runtime_error("agemm.matmul: A and B disagree on K");
   if (SFA.numel() < arcq_sf_used_bytes(M, K) || SFB.numel() < arcq_sf_used_bytes(N, K))
-    throw std::runtime_error("agemm.matmul: scale-factor buffer smaller than the swizzled layout of its operand");
-  float alpha_host = 1.0f;
-  const float* alpha_dev = nullptr;
-  torch::Tensor keep;
-  if (THPVariable_Check(scale.ptr())) {
-    const torch::Tensor& s = THPVariable_Unpack(scale.ptr());
-    if (s.is_cuda() && s.scalar_type() == torch::kFloat32 && s.numel() == 1) {
-      keep = s;
-      alpha_dev = s.data_ptr<float>();                    // consumed on the device: no .item() sync
-    } else {
-      alpha_host = s.item<float>();                       // the reference's implicit __float__
-    }
-  } else {
-    alpha_host = scale.cast<float>();
-  }
+    throw std::runtime_error("agemm.matmul: SFA / SFB smaller than the swizzled layout of its operand");
+  const Alpha al = alpha_of(scale, 1.0);
+  same_device("matmul", A, {&B, &SFA, &SFB, al.tensor()});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
   auto D = torch::empty({M, N}, A.options().dtype(torch::kBFloat16));
   const int64_t ws_bytes = arcq_gemm_workspace_bytes(M, N, K);
   torch::Tensor ws;
   if (ws_bytes) ws = torch::empty({ws_bytes}, A.options());
-  check(arcq_gemm_nvfp4(A.data_ptr<uint8_t>(), B.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), SFB.data_ptr<uint8_t>(), D.data_ptr(), M, N, K, alpha_host,
-                        alpha_dev, nullptr, nullptr, ARCQ_OUT_BF16, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A)),
+  check(arcq_gemm_nvfp4(A.data_ptr<uint8_t>(), B.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), SFB.data_ptr<uint8_t>(), D.data_ptr(), M, N, K, al.host, al.dev,
+                        nullptr, nullptr, ARCQ_OUT_BF16, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A)),
         "matmul");
   return D;
 }
@@ -77,6 +150,7 @@ std::tuple<torch::Tensor, torch::Tensor> quantize(bool is_x, const torch::Tensor
   const int64_t rows = X.size(0), KQ = X.size(1), K = KQ + KE;
   if (reorder_index.numel() != KQ || KQ % 64 || KE % 64 || KE < 0 || KE > KQ)
     throw std::runtime_error(std::string("Value error in ") + who + ": KQ / KE / reorder_index are not valid");       // bindings.cpp:157-160
+  same_device(who, X, {&reorder_index});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
   auto Q = torch::empty({rows, K / 2}, X.options().dtype(torch::kUInt8));
   auto SF = torch::empty({arcq_sf_alloc_bytes(rows, K)}, X.options().dtype(torch::kUInt8));      // bindings.cpp:83-95
@@ -102,6 +176,7 @@ std::tuple<torch::Tensor, torch::Tensor> rmsnorm_quantize_x(const torch::Tensor&
   const int64_t M = X.size(0), KQ = X.size(1), K = KQ + KE;
   if (W.numel() != KQ || reorder_index.numel() != KQ || KQ % 64 || KE % 64 || KE < 0 || KE > KQ || KQ < 2048 || KQ > 8192)
     throw std::runtime_error("Value error in run_rmsnorm_x_bf16_nvfp4: K value is not valid: " + std::to_string(KQ));   // bindings.cpp:248-251
+  same_device("rmsnorm_quantize_x", X, {&W, &reorder_index});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
   auto Q = torch::empty({M, K / 2}, X.options().dtype(torch::kUInt8));
   auto SF = torch::empty({arcq_sf_alloc_bytes(M, K)}, X.options().dtype(torch::kUInt8));
@@ -113,104 +188,43 @@ std::tuple<torch::Tensor, torch::Tensor> rmsnorm_quantize_x(const torch::Tensor&
 
 // ---- the decode extensions of arcquant_amd/agemm.py under the same names and keywords: an eager decode step of
 //      the model harness makes ~170 calls, at the ctypes mirror's 8-12 us each it is host-paced
-struct Alpha {
-  float host = 1.0f;
-  const float* dev = nullptr;
-  torch::Tensor keep;
-};
-Alpha alpha_of(const py::object& scale, double scale_host) {
-  Alpha a;
-  a.host = (float)scale_host;
-  if (THPVariable_Check(scale.ptr())) {
-    const torch::Tensor& t = THPVariable_Unpack(scale.ptr());
-    if (t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.numel() == 1) {
-      a.keep = t;
-      a.dev = t.data_ptr<float>();
-    } else {
-      a.host *= t.item<float>();
-    }
-  } else {
-    a.host *= scale.cast<float>();
-  }
-  return a;
-}
-const void* opt_ptr(const c10::optional<torch::Tensor>& t, c10::ScalarType dt, const char* name, std::initializer_list<int64_t> shape) {
-  if (!t.has_value()) return nullptr;
-  need(*t, dt, name, (int64_t)shape.size());
-  int i = 0;
-  for (int64_t d : shape)
-    if (t->size(i++) != d) throw std::runtime_error(std::string("agemm: ") + name + " has the wrong shape");
-  return t->data_ptr();
-}
-torch::Tensor out_of(const c10::optional<torch::Tensor>& out, int64_t M, int64_t N, c10::ScalarType dt, const torch::Tensor& like, const char* who) {
-  if (!out.has_value()) return torch::empty({M, N}, like.options().dtype(dt));
-  if (out->dim() != 2 || out->size(0) != M || out->size(1) != N || out->scalar_type() != dt || !out->is_contiguous())
-    throw std::runtime_error(std::string("agemm.") + who + ": out has the wrong shape / dtype");
-  return *out;
-}
-int out_code(c10::ScalarType dt, const char* who) {
-  if (dt == torch::kBFloat16) return ARCQ_OUT_BF16;
-  if (dt == torch::kFloat32) return ARCQ_OUT_F32;
-  throw std::runtime_error(std::string("agemm.") + who + ": out_dtype must be bfloat16 or float32");
-}
-void need_repacked(const torch::Tensor& RW, const torch::Tensor& RSF, int64_t N, int64_t K, const char* who) {
-  need(RW, torch::kUInt8, "RW", 1);
-  need(RSF, torch::kUInt8, "RSF", 1);
-  if (K % 64 || RW.numel() != arcq_repacked_w_bytes(N, K) || RSF.numel() != arcq_repacked_sf_bytes(N, K))
-    throw std::runtime_error(std::string("Value error in ") + who + ": RW / RSF do not belong to a [N, K] weight of this shape");
-}
-
 torch::Tensor matmul_repacked(const torch::Tensor& A, const torch::Tensor& RW, const torch::Tensor& SFA, const torch::Tensor& RSF, const py::object& scale,
                               int64_t N, const c10::optional<torch::Tensor>& bias, const c10::optional<torch::Tensor>& residual, py::object out_dtype,
                               const c10::optional<torch::Tensor>& out, double scale_host) {
-  need(A, torch::kUInt8, "A", 2);
-  need(SFA, torch::kUInt8, "SFA");
-  const int64_t M = A.size(0), K = A.size(1) * 2;
-  need_repacked(RW, RSF, N, K, "matmul_repacked");
-  if (SFA.numel() < arcq_sf_used_bytes(M, K)) throw std::runtime_error("Value error in matmul_repacked: SFA smaller than the swizzled layout of A");
+  const char* who = "matmul_repacked";
+  const auto [M, K] = open_repacked(who, A, RW, SFA, RSF, N);
   if (!arcq_gemm_repacked_supported(M, N, K)) throw std::runtime_error("matmul_repacked: this shape is outside the repacked path (see repacked_supported)");
-  const auto dt = out_dtype.is_none() ? torch::kBFloat16 : torch::python::detail::py_object_to_dtype(out_dtype);
-  const int oc = out_code(dt, "matmul_repacked");
+  const OutDtype od = out_dtype_of(out_dtype, who);
   const Alpha al = alpha_of(scale, scale_host);
+  torch::Tensor D = out_of(out, M, N, od.dt, A, who);
+  const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
+  const void* rp = opt_ptr(residual, torch::kBFloat16, "residual", {M, N});
+  same_device(who, A, {&RW, &SFA, &RSF, al.tensor(), &D, opt_t(bias), opt_t(residual)});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-  torch::Tensor D = out_of(out, M, N, dt, A, "matmul_repacked");
   check(arcq_gemm_nvfp4_repacked(A.data_ptr<uint8_t>(), RW.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), RSF.data_ptr<uint8_t>(), D.data_ptr(), M, N, K, al.host,
-                                 al.dev, opt_ptr(bias, torch::kBFloat16, "bias", {N}), opt_ptr(residual, torch::kBFloat16, "residual", {M, N}), oc, stream_of(A)),
-        "matmul_repacked");
+                                 al.dev, bp, rp, od.code, stream_of(A)),
+        who);
   return D;
 }
 
-// ---- one weight copy for every M (include/arcq.h, arcq_gemm_nvfp4_rw): every operand must live on A's device
-void same_device(const char* who, const torch::Tensor& A, std::initializer_list<const torch::Tensor*> ts) {
-  for (const torch::Tensor* t : ts)
-    if (t && t->defined() && t->device() != A.device())
-      throw std::runtime_error(std::string("agemm.") + who + ": every operand must live on A's device");
-}
-const torch::Tensor* opt_t(const c10::optional<torch::Tensor>& t) { return t.has_value() ? &*t : nullptr; }
-
+// ---- one weight copy for every M (include/arcq.h, arcq_gemm_nvfp4_rw)
 torch::Tensor matmul_rw(const torch::Tensor& A, const torch::Tensor& RW, const torch::Tensor& SFA, const torch::Tensor& RSF, const py::object& scale, int64_t N,
                         const c10::optional<torch::Tensor>& bias, const c10::optional<torch::Tensor>& residual, py::object out_dtype,
                         const c10::optional<torch::Tensor>& out, double scale_host) {
   const char* who = "matmul_rw";
-  need(A, torch::kUInt8, "A", 2);
-  need(SFA, torch::kUInt8, "SFA");
-  const int64_t M = A.size(0), K = A.size(1) * 2;
-  need_repacked(RW, RSF, N, K, who);
-  if (SFA.numel() < arcq_sf_used_bytes(M, K)) throw std::runtime_error("Value error in matmul_rw: SFA smaller than the swizzled layout of A");
-  const auto dt = out_dtype.is_none() ? torch::kBFloat16 : torch::python::detail::py_object_to_dtype(out_dtype);
-  const int oc = out_code(dt, who);
+  const auto [M, K] = open_repacked(who, A, RW, SFA, RSF, N);
+  const OutDtype od = out_dtype_of(out_dtype, who);
   const Alpha al = alpha_of(scale, scale_host);
-  if (out.has_value()) need(*out, dt, "out", 2);
-  same_device(who, A, {&RW, &SFA, &RSF, opt_t(bias), opt_t(residual), opt_t(out), al.keep.defined() ? &al.keep : nullptr});
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-  torch::Tensor D = out_of(out, M, N, dt, A, who);
+  torch::Tensor D = out_of(out, M, N, od.dt, A, who);
   const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
   const void* rp = opt_ptr(residual, torch::kBFloat16, "residual", {M, N});
+  same_device(who, A, {&RW, &SFA, &RSF, al.tensor(), &D, opt_t(bias), opt_t(residual)});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
   const int64_t ws_bytes = arcq_gemm_rw_workspace_bytes(M, N, K);
   torch::Tensor ws;
   if (ws_bytes) ws = torch::empty({ws_bytes}, A.options());
   check(arcq_gemm_nvfp4_rw(A.data_ptr<uint8_t>(), RW.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), RSF.data_ptr<uint8_t>(), D.data_ptr(), M, N, K, al.host, al.dev,
-                           bp, rp, oc, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A)),
+                           bp, rp, od.code, ws_bytes ? ws.data_ptr() : nullptr, ws_bytes, stream_of(A)),
         who);
   return D;
 }
@@ -218,33 +232,23 @@ torch::Tensor matmul_rw(const torch::Tensor& A, const torch::Tensor& RW, const t
 std::tuple<torch::Tensor, torch::Tensor> matmul_rw_silu_mul(const torch::Tensor& A, const torch::Tensor& RW, const torch::Tensor& SFA, const torch::Tensor& RSF,
                                                             const py::object& scale, int64_t N, double scale_host, const c10::optional<torch::Tensor>& bias) {
   const char* who = "matmul_rw_silu_mul";
-  need(A, torch::kUInt8, "A", 2);
-  need(SFA, torch::kUInt8, "SFA");
-  const int64_t M = A.size(0), K = A.size(1) * 2;
-  need_repacked(RW, RSF, N, K, who);
-  if (N % 8) throw std::runtime_error("Value error in matmul_rw_silu_mul: N % 8 != 0");
-  if (SFA.numel() < arcq_sf_used_bytes(M, K)) throw std::runtime_error("Value error in matmul_rw_silu_mul: SFA smaller than the swizzled layout of A");
-  // (as the mirror: any CUDA scale tensor is read on the device as fp32)
-  float alpha_host = (float)scale_host;
-  torch::Tensor alpha_dev;
-  if (THPVariable_Check(scale.ptr()) && THPVariable_Unpack(scale.ptr()).is_cuda()) alpha_dev = THPVariable_Unpack(scale.ptr()).reshape({-1}).slice(0, 0, 1).to(torch::kFloat32);
-  else alpha_host *= THPVariable_Check(scale.ptr()) ? THPVariable_Unpack(scale.ptr()).item<float>() : scale.cast<float>();
-  same_device(who, A, {&RW, &SFA, &RSF, opt_t(bias), alpha_dev.defined() ? &alpha_dev : nullptr});
-  c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+  const auto [M, K] = open_repacked(who, A, RW, SFA, RSF, N, 8);
+  const Alpha al = alpha_of(scale, scale_host, true);
   const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
+  same_device(who, A, {&RW, &SFA, &RSF, al.tensor(), opt_t(bias)});
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
   auto act = torch::empty({M, N / 2}, A.options().dtype(torch::kBFloat16));
   auto slots = torch::empty({std::max<int64_t>(1, arcq_gemm_rw_silu_mul_slots(M, N, K))}, A.options().dtype(torch::kInt32));
   check(arcq_gemm_nvfp4_rw_silu_mul(A.data_ptr<uint8_t>(), RW.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), RSF.data_ptr<uint8_t>(), act.data_ptr(),
-                                    (uint32_t*)slots.data_ptr<int32_t>(), M, N, K, alpha_host, alpha_dev.defined() ? alpha_dev.data_ptr<float>() : nullptr, bp,
-                                    stream_of(A)),
+                                    (uint32_t*)slots.data_ptr<int32_t>(), M, N, K, al.host, al.dev, bp, stream_of(A)),
         who);
   return {act, slots};
 }
 
-// the inverse of agemm.repack_w (data movement only): (QW [N, K/2], SFW [arcq_sf_alloc_bytes(N, K)], unused bytes zero)
+// the inverse of agemm.repack_w (data movement only, on RW's device): (QW [N, K/2], SFW [arcq_sf_alloc_bytes(N, K)], unused bytes zero)
 std::tuple<torch::Tensor, torch::Tensor> unrepack_w(const torch::Tensor& RW, const torch::Tensor& RSF, int64_t N, int64_t K) {
-  for (const auto* t : {&RW, &RSF})
-    if (t->scalar_type() != torch::kUInt8 || t->dim() != 1 || !t->is_contiguous()) throw std::runtime_error("agemm.unrepack_w: RW / RSF must be contiguous 1-D uint8 tensors");
+  need(RW, torch::kUInt8, "RW", 1);
+  need(RSF, torch::kUInt8, "RSF", 1);
   if (N <= 0 || K <= 0 || K % 64 || RW.numel() != arcq_repacked_w_bytes(N, K) || RSF.numel() != arcq_repacked_sf_bytes(N, K))
     throw std::runtime_error("Value error in unrepack_w: RW / RSF do not belong to a [N, K] weight of this shape");
   const int64_t Np = (N + 15) / 16 * 16, Kp = (K + 255) / 256 * 256, RB = Np / 16, T = Kp / 128;
@@ -267,7 +271,7 @@ FusedShape fused_common(const char* who, const torch::Tensor& X, const torch::Te
   need(X, torch::kBFloat16, "X", 2);
   need(reorder_index, torch::kInt16, "reorder_index", 1);
   FusedShape f{X.size(0), X.size(1), KE, X.size(1) + KE, 0};
-  if (f.KQ % 64 || KE % 64 || KE < 0 || KE > f.KQ || reorder_index.numel() != f.KQ) throw std::runtime_error(std::string("Value error in ") + who + ": KQ / KE are not valid");
+  if (f.KQ % 64 || KE % 64 || KE < 0 || KE > f.KQ || reorder_index.numel() != f.KQ) throw std::runtime_error(std::string("Value error in ") + who + ": KQ / KE / reorder_index are not valid");
   need_repacked(RW, RSF, N, f.K, who);
   f.variant = variant.is_none() ? arcq_variant_for_kq(f.KQ) : variant.cast<int>();
   return f;
@@ -280,15 +284,17 @@ torch::Tensor rmsnorm_matmul_repacked(const torch::Tensor& X, const torch::Tenso
   const char* who = "rmsnorm_matmul_repacked";
   const FusedShape f = fused_common(who, X, reorder_index, RW, RSF, N, KE, variant);
   need(W, torch::kBFloat16, "W", 1);
-  if (W.numel() != f.KQ || !arcq_linear_fused_supported(ARCQ_SRC_RMSNORM, f.M, N, f.KQ, KE)) throw std::runtime_error("rmsnorm_matmul_repacked: outside the fused path (see fused_supported)");
-  const auto dt = out_dtype.is_none() ? torch::kBFloat16 : torch::python::detail::py_object_to_dtype(out_dtype);
-  const int oc = out_code(dt, who);
+  if (W.numel() != f.KQ) throw std::runtime_error("agemm: W has the wrong shape");
+  if (!arcq_linear_fused_supported(ARCQ_SRC_RMSNORM, f.M, N, f.KQ, KE)) throw std::runtime_error("rmsnorm_matmul_repacked: outside the fused path (see fused_supported)");
+  const OutDtype od = out_dtype_of(out_dtype, who);
   const Alpha al = alpha_of(scale, scale_host);
+  torch::Tensor D = out_of(out, f.M, N, od.dt, X, who);
+  const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
+  const void* rp = opt_ptr(residual, torch::kBFloat16, "residual", {f.M, N});
+  same_device(who, X, {&W, &reorder_index, &RW, &RSF, al.tensor(), &D, opt_t(bias), opt_t(residual)});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-  torch::Tensor D = out_of(out, f.M, N, dt, X, who);
   check(arcq_linear_rmsnorm_repacked(X.data_ptr(), W.data_ptr(), (float)eps, reorder_index.data_ptr<int16_t>(), RW.data_ptr<uint8_t>(), RSF.data_ptr<uint8_t>(), D.data_ptr(),
-                                     f.M, N, f.KQ, KE, f.variant, al.host, al.dev, opt_ptr(bias, torch::kBFloat16, "bias", {N}),
-                                     opt_ptr(residual, torch::kBFloat16, "residual", {f.M, N}), oc, stream_of(X)),
+                                     f.M, N, f.KQ, KE, f.variant, al.host, al.dev, bp, rp, od.code, stream_of(X)),
         who);
   return D;
 }
@@ -300,18 +306,21 @@ std::tuple<torch::Tensor, torch::Tensor> rmsnorm_matmul_repacked_silu(const torc
   const char* who = "rmsnorm_matmul_repacked_silu";
   const FusedShape f = fused_common(who, X, reorder_index, RW, RSF, N, KE, variant);
   need(W, torch::kBFloat16, "W", 1);
-  if (W.numel() != f.KQ || N % 4 || !arcq_linear_fused_supported(ARCQ_SRC_RMSNORM, f.M, N, f.KQ, KE))
+  if (W.numel() != f.KQ) throw std::runtime_error("agemm: W has the wrong shape");
+  if (N % 4 || !arcq_linear_fused_supported(ARCQ_SRC_RMSNORM, f.M, N, f.KQ, KE))
     throw std::runtime_error("rmsnorm_matmul_repacked_silu: outside the fused path (see fused_supported; N % 4 == 0)");
   const Alpha al = alpha_of(scale, scale_host);
+  const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
+  // (act_scatter_index must be a permutation of 0 .. N/2-1: the ctypes mirror checks it once per index tensor; callers of this binding
+  //  pass an index that went through that check or through their own)
+  const void* sp = opt_ptr(act_scatter_index, torch::kInt16, "act_scatter_index", {N / 2});
+  same_device(who, X, {&W, &reorder_index, &RW, &RSF, al.tensor(), opt_t(bias), opt_t(act_scatter_index)});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
   auto act = torch::empty({f.M, N / 2}, X.options());
   auto slots = torch::empty({(N + 15) / 16}, X.options().dtype(torch::kInt32));
-  // (act_scatter_index must be a permutation of 0 .. N/2-1: the ctypes mirror checks it once per index tensor; callers of this binding
-  //  pass an index that went through that check or through their own)
   check(arcq_linear_rmsnorm_silu_repacked(X.data_ptr(), W.data_ptr(), (float)eps, reorder_index.data_ptr<int16_t>(), RW.data_ptr<uint8_t>(), RSF.data_ptr<uint8_t>(),
-                                          act.data_ptr(), (uint32_t*)slots.data_ptr<int32_t>(), f.M, N, f.KQ, KE, f.variant, al.host, al.dev,
-                                          opt_ptr(bias, torch::kBFloat16, "bias", {N}),
-                                          (const int16_t*)opt_ptr(act_scatter_index, torch::kInt16, "act_scatter_index", {N / 2}), stream_of(X)),
+                                          act.data_ptr(), (uint32_t*)slots.data_ptr<int32_t>(), f.M, N, f.KQ, KE, f.variant, al.host, al.dev, bp, (const int16_t*)sp,
+                                          stream_of(X)),
         who);
   return {act, slots};
 }
@@ -323,8 +332,7 @@ std::tuple<torch::Tensor, torch::Tensor> dynamic_matmul_repacked(const torch::Te
   const char* who = "dynamic_matmul_repacked";
   const FusedShape f = fused_common(who, X, reorder_index, RW, RSF, N, KE, variant);
   if (!arcq_linear_fused_supported(ARCQ_SRC_DYNAMIC, f.M, N, f.KQ, KE)) throw std::runtime_error("dynamic_matmul_repacked: outside the fused path (see fused_supported)");
-  const auto dt = out_dtype.is_none() ? torch::kBFloat16 : torch::python::detail::py_object_to_dtype(out_dtype);
-  const int oc = out_code(dt, who);
+  const OutDtype od = out_dtype_of(out_dtype, who);
   const uint32_t* sl = nullptr;
   int64_t nsl = 0;
   if (absmax_slots.has_value()) {
@@ -333,12 +341,14 @@ std::tuple<torch::Tensor, torch::Tensor> dynamic_matmul_repacked(const torch::Te
     sl = (const uint32_t*)absmax_slots->data_ptr<int32_t>();
     nsl = absmax_slots->numel();
   }
+  torch::Tensor D = out_of(out, f.M, N, od.dt, X, who);
+  const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
+  const void* rp = opt_ptr(residual, torch::kBFloat16, "residual", {f.M, N});
+  same_device(who, X, {&reorder_index, &RW, &RSF, opt_t(absmax_slots), &D, opt_t(bias), opt_t(residual)});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
-  torch::Tensor D = out_of(out, f.M, N, dt, X, who);
   auto scale = torch::empty({1}, X.options().dtype(torch::kFloat32));
   check(arcq_linear_dynamic_repacked(X.data_ptr(), reorder_index.data_ptr<int16_t>(), RW.data_ptr<uint8_t>(), RSF.data_ptr<uint8_t>(), D.data_ptr(), scale.data_ptr<float>(), sl,
-                                     nsl, f.M, N, f.KQ, KE, f.variant, (float)scale_w, opt_ptr(bias, torch::kBFloat16, "bias", {N}),
-                                     opt_ptr(residual, torch::kBFloat16, "residual", {f.M, N}), oc, stream_of(X)),
+                                     nsl, f.M, N, f.KQ, KE, f.variant, (float)scale_w, bp, rp, od.code, stream_of(X)),
         who);
   return {D, scale.reshape({})};
 }
@@ -353,6 +363,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> reorder_quantize_x_dynam
   if (KQ % 64 || KE % 64 || KE < 0 || KE > KQ || (reorder_index.has_value() && reorder_index->numel() != KQ) || absmax_slots.numel() == 0)
     throw std::runtime_error("Value error in reorder_quantize_x_dynamic: KQ / KE / reorder_index / absmax_slots are not valid");
   const int var = variant.is_none() ? arcq_variant_for_kq(KQ) : variant.cast<int>();
+  same_device("reorder_quantize_x_dynamic", X, {opt_t(reorder_index), &absmax_slots});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
   auto Q = torch::empty({M, K / 2}, X.options().dtype(torch::kUInt8));
   auto SF = torch::empty({arcq_sf_alloc_bytes(M, K)}, X.options().dtype(torch::kUInt8));
@@ -375,10 +386,10 @@ std::tuple<torch::Tensor, torch::Tensor> mx_quantize(bool is_x, const torch::Ten
   const char* who = is_x ? "mx_reorder_quantize_x" : "mx_reorder_quantize_w";
   need(X, torch::kBFloat16, is_x ? "X" : "W", 2);
   need(reorder_index, torch::kInt16, "reorder_index", 1);
-  same_device(who, X, {&reorder_index});
   const int64_t rows = X.size(0), KQ = X.size(1), Kp = arcq_mx_k_padded(KQ + KE);
   if (reorder_index.numel() != KQ || KQ % 64 || KE % 64 || KE < 0 || KE > KQ || KQ > 32767)
     throw std::runtime_error(std::string("Value error in ") + who + ": KQ / KE / reorder_index are not valid");
+  same_device(who, X, {&reorder_index});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
   auto Q = torch::empty({rows, Kp / 2}, X.options().dtype(torch::kUInt8));
   auto SF = torch::empty({rows, Kp / 32}, X.options().dtype(torch::kUInt8));
@@ -400,14 +411,15 @@ torch::Tensor mx_matmul(const torch::Tensor& A, const torch::Tensor& B, const to
   if (K % 128 || N % 16) throw std::runtime_error("agemm.mx_matmul: K must be a multiple of 128 and N of 16");
   if (SFA.size(0) != M || SFA.size(1) != K / 32 || SFB.size(0) != N || SFB.size(1) != K / 32)
     throw std::runtime_error("agemm.mx_matmul: SFA / SFB must be [rows, K/32]");
-  const auto dt = out_dtype.is_none() ? torch::kBFloat16 : torch::python::detail::py_object_to_dtype(out_dtype);
-  const int oc = out_code(dt, who);
+  const OutDtype od = out_dtype_of(out_dtype, who);
   const Alpha al = alpha_of(scale, scale_host);
-  same_device(who, A, {&B, &SFA, &SFB, opt_t(bias), opt_t(residual), opt_t(out), al.keep.defined() ? &al.keep : nullptr});
+  torch::Tensor D = out_of(out, M, N, od.dt, A, who);
+  const void* bp = opt_ptr(bias, torch::kBFloat16, "bias", {N});
+  const void* rp = opt_ptr(residual, torch::kBFloat16, "residual", {M, N});
+  same_device(who, A, {&B, &SFA, &SFB, al.tensor(), &D, opt_t(bias), opt_t(residual)});
   c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
-  torch::Tensor D = out_of(out, M, N, dt, A, who);
-  check(arcq_gemm_mxfp4(A.data_ptr<uint8_t>(), B.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), SFB.data_ptr<uint8_t>(), D.data_ptr(), M, N, K, al.host, al.dev,
-                        opt_ptr(bias, torch::kBFloat16, "bias", {N}), opt_ptr(residual, torch::kBFloat16, "residual", {M, N}), oc, nullptr, 0, stream_of(A)),
+  check(arcq_gemm_mxfp4(A.data_ptr<uint8_t>(), B.data_ptr<uint8_t>(), SFA.data_ptr<uint8_t>(), SFB.data_ptr<uint8_t>(), D.data_ptr(), M, N, K, al.host, al.dev, bp, rp,
+                        od.code, nullptr, 0, stream_of(A)),
         who);
   return D;
 }

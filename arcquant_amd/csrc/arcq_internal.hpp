@@ -20,6 +20,21 @@ struct LdsOptIn {
 };
 int ensure_dynamic_lds(const void* kernel, LdsOptIn& cache, int bytes, const char* who);
 
+// c_api.hip: the argument checks of a GEMM-shaped entry point (host only), parameterised by what differs between entry points.
+struct GemmRule {
+  const char* who;
+  int k_mult = 64, n_mult = 1;          // K % k_mult == 0 and N % n_mult == 0
+  int64_t max_m = INT32_MAX / 2;        // with M * N <= 2^40; 0: the kernel's `supported` predicate bounds M later
+  const char *b = "B", *sfb = "SFB", *d = "D";   // operand names in the alignment messages
+  bool slots = false;                   // takes absmax_slots (non-NULL, 4-byte aligned)
+  int epi_align = 1;                    // bias and residual alignment in bytes
+  const char* prefill_only = nullptr;   // set: M <= 16 is ARCQ_ERR_UNSUPPORTED with this text, reported before a NULL pointer
+};
+// In the order every entry point reports them: divisibility, out_dtype, empty shape (returns 1: nothing to do), prefill_only, NULL, size
+// limits, 16-byte operands, 4-byte operands, bias / residual.  Returns ARCQ_OK to go on or the recorded failure; no HIP call.
+int gemm_checks(const GemmRule& r, const void* A, const void* B, const void* SFA, const void* SFB, const void* D, const void* absmax_slots, int64_t M,
+                int64_t N, int64_t K, const void* bias, const void* residual, int out_dtype);
+
 // quantize.hip
 int quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, int variant,
                hipStream_t stream);

@@ -36,6 +36,48 @@ int ensure_dynamic_lds(const void* kernel, LdsOptIn& cache, int bytes, const cha
   return ARCQ_OK;
 }
 
+static const int64_t kSkinnyMaxM = 16;
+
+static uintptr_t bits(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+
+// bias / residual views the kernel's epilogue loads cannot take (align = 1: no rule)
+static int check_epi_align(const char* who, const void* bias, const void* residual, int align) {
+  if ((bits(bias) | bits(residual)) & (uintptr_t)(align - 1)) return fail(ARCQ_ERR_SHAPE, "%s: bias and residual must be %d-byte aligned", who, align);
+  return ARCQ_OK;
+}
+// the decode epilogues fetch the four bias / residual values of an output quad with ONE 8-byte load when N % 4 == 0
+static int repacked_epi_align(int64_t N) { return (N % 4) == 0 ? 8 : 1; }
+
+int gemm_checks(const GemmRule& r, const void* A, const void* B, const void* SFA, const void* SFB, const void* D, const void* absmax_slots, int64_t M,
+                int64_t N, int64_t K, const void* bias, const void* residual, int out_dtype) {
+  if (M < 0 || N < 0 || K <= 0 || (K % r.k_mult) || (N % r.n_mult)) {
+    if (r.n_mult == 1)
+      return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0 and K %% %d == 0 (M=%lld N=%lld K=%lld)", r.who, r.k_mult, (long long)M, (long long)N, (long long)K);
+    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0, K %% %d == 0 and N %% %d == 0 (M=%lld N=%lld K=%lld)", r.who, r.k_mult, r.n_mult, (long long)M,
+                (long long)N, (long long)K);
+  }
+  if (out_dtype != ARCQ_OUT_BF16 && out_dtype != ARCQ_OUT_F32) return fail(ARCQ_ERR_SHAPE, "%s: bad out_dtype %d", r.who, out_dtype);
+  if (M == 0 || N == 0) return 1;                              // nothing to do
+  if (r.prefill_only && M <= kSkinnyMaxM) return fail(ARCQ_ERR_UNSUPPORTED, "%s: %s", r.who, r.prefill_only);
+  if (!A || !B || !SFA || !SFB || !D || (r.slots && !absmax_slots)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", r.who);
+  if ((r.max_m && (M > r.max_m || M * N > ((int64_t)1 << 40))) || N > INT32_MAX / 2 || K > INT32_MAX / 2)
+    return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", r.who);
+  if ((bits(A) | bits(B) | bits(D)) & 15) return fail(ARCQ_ERR_SHAPE, "%s: A, %s and %s must be 16-byte aligned", r.who, r.b, r.d);
+  if ((bits(SFA) | bits(SFB) | (r.slots ? bits(absmax_slots) : 0)) & 3)
+    return fail(ARCQ_ERR_SHAPE, r.slots ? "%s: SFA, %s and absmax_slots must be 4-byte aligned" : "%s: SFA and %s must be 4-byte aligned", r.who, r.sfb);
+  return check_epi_align(r.who, bias, residual, r.epi_align);
+}
+
+static GemmArgs gemm_args(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t K, float alpha_host,
+                          const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* workspace, int64_t workspace_bytes) {
+  GemmArgs a;
+  a.A = A; a.B = B; a.SFA = SFA; a.SFB = SFB; a.D = D;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = (const uint16_t*)bias; a.residual = (const uint16_t*)residual; a.out_dtype = out_dtype;
+  a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  return a;
+}
+
 }  // namespace arcq
 
 using namespace arcq;
@@ -98,8 +140,6 @@ int arcq_absmax_scale(const void* X, int64_t n, float* scale_out, void* stream) 
 }
 
 
-static const int64_t kSkinnyMaxM = 16;
-
 // M <= 16: the 32-row-tile kernel needs enough tiles to occupy the chip without split-K (its tiles are twice as
 // tall); below that the 16-row-tile kernel wins.  Measured crossover (tools/decode_bench.py, M=4, K=4160, us):
 // N=4096 7.3 vs 9.3, N=5120 9.2 vs 8.5, N=8192 10.2 vs 9.5, N=14336 16.0 vs 14.6, N=37888 28.7 vs 23.9.
@@ -121,23 +161,10 @@ int64_t arcq_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
 int arcq_gemm_nvfp4(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N,
                     int64_t K, float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* workspace,
                     int64_t workspace_bytes, void* stream) {
-  if (M < 0 || N < 0 || K <= 0 || (K % 64))
-    return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4: need M,N >= 0 and K %% 64 == 0 (M=%lld N=%lld K=%lld)", (long long)M,
-                (long long)N, (long long)K);
-  if (out_dtype != ARCQ_OUT_BF16 && out_dtype != ARCQ_OUT_F32) return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4: bad out_dtype %d", out_dtype);
-  if (M == 0 || N == 0) return ARCQ_OK;
-  if (!A || !B || !SFA || !SFB || !D) return fail(ARCQ_ERR_NULL, "arcq_gemm_nvfp4: NULL pointer");
-  if (M > INT32_MAX / 2 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40))
-    return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4: shape too large");
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(D)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4: A, B and D must be 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(SFB)) & 3)
-    return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4: SFA and SFB must be 4-byte aligned");
-  GemmArgs a;
-  a.A = A; a.B = B; a.SFA = SFA; a.SFB = SFB; a.D = D;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = (const uint16_t*)bias; a.residual = (const uint16_t*)residual; a.out_dtype = out_dtype;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  GemmRule r{"arcq_gemm_nvfp4"};
+  const int rc = gemm_checks(r, A, B, SFA, SFB, D, nullptr, M, N, K, bias, residual, out_dtype);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  const GemmArgs a = gemm_args(A, B, SFA, SFB, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, workspace, workspace_bytes);
   if (const int cfg = gemm_regtile_cfg(M, N, K, kEpiPlain)) return gemm_regtile(a, cfg, (hipStream_t)stream);
   if (M <= kSkinnyMaxM) return use_decode_v2(N) ? gemm_decode(a, (hipStream_t)stream) : gemm_skinny(a, (hipStream_t)stream);
   return gemm_tile(a, (hipStream_t)stream);
@@ -150,25 +177,13 @@ int64_t arcq_gemm_silu_mul_slots(int64_t M, int64_t N, int64_t K) {
 
 int arcq_gemm_nvfp4_silu_mul(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* ACT, uint32_t* absmax_slots,
                              int64_t M, int64_t N, int64_t K, float alpha_host, const float* alpha_dev, const void* bias, void* stream) {
-  const char* who = "arcq_gemm_nvfp4_silu_mul";
-  if (M < 0 || N < 0 || K <= 0 || (K % 64) || (N % 8))
-    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0, K %% 64 == 0 and N %% 8 == 0 (M=%lld N=%lld K=%lld)", who, (long long)M, (long long)N,
-                (long long)K);
-  if (M == 0 || N == 0) return ARCQ_OK;
-  if (!A || !B || !SFA || !SFB || !ACT || !absmax_slots) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (M > INT32_MAX / 2 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40))
-    return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(ACT)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: A, B and ACT must be 16-byte aligned", who);
-  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(SFB) | reinterpret_cast<uintptr_t>(absmax_slots)) & 3)
-    return fail(ARCQ_ERR_SHAPE, "%s: SFA, SFB and absmax_slots must be 4-byte aligned", who);
-  GemmArgs a;
-  a.A = A; a.B = B; a.SFA = SFA; a.SFB = SFB; a.D = ACT;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = (const uint16_t*)bias; a.residual = nullptr; a.out_dtype = ARCQ_OUT_BF16;
-  a.workspace = nullptr; a.workspace_bytes = 0;
+  GemmRule r{"arcq_gemm_nvfp4_silu_mul"};
+  r.n_mult = 8; r.d = "ACT"; r.slots = true;
+  const int rc = gemm_checks(r, A, B, SFA, SFB, ACT, absmax_slots, M, N, K, nullptr, nullptr, ARCQ_OUT_BF16);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  GemmArgs a = gemm_args(A, B, SFA, SFB, ACT, M, N, K, alpha_host, alpha_dev, bias, nullptr, ARCQ_OUT_BF16, nullptr, 0);
   a.epilogue = kEpiSiluMul; a.absmax_slots = absmax_slots;
-  if (bias && M <= kSkinnyMaxM) return fail(ARCQ_ERR_UNSUPPORTED, "%s: bias is supported by the tile kernel only (M > 16); decode uses arcq_linear_rmsnorm_silu_repacked", who);
+  if (bias && M <= kSkinnyMaxM) return fail(ARCQ_ERR_UNSUPPORTED, "%s: bias is supported by the tile kernel only (M > 16); decode uses arcq_linear_rmsnorm_silu_repacked", r.who);
   // the 16-row decode kernel has no fused epilogue: every M <= 16 shape takes the 32-row kernel here
   if (M <= kSkinnyMaxM) return gemm_decode(a, (hipStream_t)stream);
   return gemm_tile(a, (hipStream_t)stream);
@@ -186,23 +201,11 @@ int arcq_gemm_repacked_supported(int64_t M, int64_t N, int64_t K) { return gemm_
 static int gemm_repacked_entry(bool via_stream, const char* who, const uint8_t* A, const uint8_t* RW, const uint8_t* SFA, const uint8_t* RSF, void* D, int64_t M, int64_t N,
                              int64_t K, float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype,
                              void* stream) {
-  if (M < 0 || N < 0 || K <= 0 || (K % 64))
-    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0 and K %% 64 == 0 (M=%lld N=%lld K=%lld)", who, (long long)M, (long long)N, (long long)K);
-  if (out_dtype != ARCQ_OUT_BF16 && out_dtype != ARCQ_OUT_F32) return fail(ARCQ_ERR_SHAPE, "%s: bad out_dtype %d", who, out_dtype);
-  if (M == 0 || N == 0) return ARCQ_OK;
-  if (!A || !RW || !SFA || !RSF || !D) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (N > INT32_MAX / 2 || K > INT32_MAX / 2) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(RW) | reinterpret_cast<uintptr_t>(D)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: A, RW and D must be 16-byte aligned", who);
-  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(RSF)) & 3) return fail(ARCQ_ERR_SHAPE, "%s: SFA and RSF must be 4-byte aligned", who);
-  // the decode epilogues fetch the four bias / residual values of an output quad with ONE 8-byte load when N % 4 == 0
-  if ((N % 4) == 0 && ((reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) & 7))
-    return fail(ARCQ_ERR_SHAPE, "%s: bias and residual must be 8-byte aligned", who);
-  GemmArgs a;
-  a.A = A; a.B = nullptr; a.SFA = SFA; a.SFB = nullptr; a.D = D;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = (const uint16_t*)bias; a.residual = (const uint16_t*)residual; a.out_dtype = out_dtype;
-  a.workspace = nullptr; a.workspace_bytes = 0;
+  GemmRule r{who};
+  r.max_m = 0; r.b = "RW"; r.sfb = "RSF"; r.epi_align = repacked_epi_align(N);
+  const int rc = gemm_checks(r, A, RW, SFA, RSF, D, nullptr, M, N, K, bias, residual, out_dtype);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  const GemmArgs a = gemm_args(A, nullptr, SFA, nullptr, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, nullptr, 0);
   return via_stream ? gemm_repacked_stream(a, RW, RSF, (hipStream_t)stream) : gemm_repacked(a, RW, RSF, (hipStream_t)stream);
 }
 
@@ -220,21 +223,11 @@ int arcq_gemm_nvfp4_repacked_stream(const uint8_t* A, const uint8_t* RW, const u
 int arcq_gemm_nvfp4_repacked_silu_absmax(const uint8_t* A, const uint8_t* RW, const uint8_t* SFA, const uint8_t* RSF, void* D,
                                          uint32_t* absmax_slots, int64_t M, int64_t N, int64_t K, float alpha_host, const float* alpha_dev,
                                          void* stream) {
-  const char* who = "arcq_gemm_nvfp4_repacked_silu_absmax";
-  if (M < 0 || N < 0 || K <= 0 || (K % 64) || (N % 4))
-    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0, K %% 64 == 0 and N %% 4 == 0 (M=%lld N=%lld K=%lld)", who, (long long)M, (long long)N, (long long)K);
-  if (M == 0 || N == 0) return ARCQ_OK;
-  if (!A || !RW || !SFA || !RSF || !D || !absmax_slots) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (N > INT32_MAX / 2 || K > INT32_MAX / 2) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(RW) | reinterpret_cast<uintptr_t>(D)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: A, RW and D must be 16-byte aligned", who);
-  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(RSF) | reinterpret_cast<uintptr_t>(absmax_slots)) & 3)
-    return fail(ARCQ_ERR_SHAPE, "%s: SFA, RSF and absmax_slots must be 4-byte aligned", who);
-  GemmArgs a;
-  a.A = A; a.B = nullptr; a.SFA = SFA; a.SFB = nullptr; a.D = D;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = nullptr; a.residual = nullptr; a.out_dtype = ARCQ_OUT_BF16;
-  a.workspace = nullptr; a.workspace_bytes = 0;
+  GemmRule r{"arcq_gemm_nvfp4_repacked_silu_absmax"};
+  r.n_mult = 4; r.max_m = 0; r.b = "RW"; r.sfb = "RSF"; r.slots = true;
+  const int rc = gemm_checks(r, A, RW, SFA, RSF, D, absmax_slots, M, N, K, nullptr, nullptr, ARCQ_OUT_BF16);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  GemmArgs a = gemm_args(A, nullptr, SFA, nullptr, D, M, N, K, alpha_host, alpha_dev, nullptr, nullptr, ARCQ_OUT_BF16, nullptr, 0);
   a.epilogue = kEpiSiluMul; a.absmax_slots = absmax_slots;
   return gemm_repacked(a, RW, RSF, (hipStream_t)stream);
 }
@@ -268,28 +261,18 @@ int64_t arcq_gemm_rw_workspace_bytes(int64_t M, int64_t N, int64_t K) {
 int arcq_gemm_nvfp4_rw(const uint8_t* A, const uint8_t* RW, const uint8_t* SFA, const uint8_t* RSF, void* D, int64_t M, int64_t N, int64_t K,
                        float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* workspace,
                        int64_t workspace_bytes, void* stream) {
-  const char* who = "arcq_gemm_nvfp4_rw";
-  if (M < 0 || N < 0 || K <= 0 || (K % 64))
-    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0 and K %% 64 == 0 (M=%lld N=%lld K=%lld)", who, (long long)M, (long long)N, (long long)K);
-  if (out_dtype != ARCQ_OUT_BF16 && out_dtype != ARCQ_OUT_F32) return fail(ARCQ_ERR_SHAPE, "%s: bad out_dtype %d", who, out_dtype);
-  if (M == 0 || N == 0) return ARCQ_OK;
-  if (!A || !RW || !SFA || !RSF || !D) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (M > INT32_MAX / 2 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40)) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(RW) | reinterpret_cast<uintptr_t>(D)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: A, RW and D must be 16-byte aligned", who);
-  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(RSF)) & 3) return fail(ARCQ_ERR_SHAPE, "%s: SFA and RSF must be 4-byte aligned", who);
+  GemmRule r{"arcq_gemm_nvfp4_rw"};
+  r.b = "RW"; r.sfb = "RSF";
+  const int rc = gemm_checks(r, A, RW, SFA, RSF, D, nullptr, M, N, K, nullptr, nullptr, out_dtype);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
   // the repacked decode kernels reject bias / residual views that are not 8-byte aligned: those calls take route 2 / 3
-  const bool epi_aligned = ((reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) & 7) == 0;
+  const bool epi_aligned = ((bits(bias) | bits(residual)) & 7) == 0;
   int cfg;
   const int route = rw_route(M, N, K, epi_aligned, &cfg);
   if (route == 1) return arcq_gemm_nvfp4_repacked(A, RW, SFA, RSF, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, stream);
-  if (route == 0) return fail(ARCQ_ERR_UNSUPPORTED, "%s: the repacked weight of N=%lld K=%lld exceeds the register-tiled kernel's 32-bit offsets", who,
+  if (route == 0) return fail(ARCQ_ERR_UNSUPPORTED, "%s: the repacked weight of N=%lld K=%lld exceeds the register-tiled kernel's 32-bit offsets", r.who,
                               (long long)N, (long long)K);
-  GemmArgs a;
-  a.A = A; a.B = RW; a.SFA = SFA; a.SFB = RSF; a.D = D;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = (const uint16_t*)bias; a.residual = (const uint16_t*)residual; a.out_dtype = out_dtype;
-  a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  GemmArgs a = gemm_args(A, RW, SFA, RSF, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, workspace, workspace_bytes);
   a.b_layout = kBRepacked;
   if (route == 2) return gemm_regtile(a, cfg, (hipStream_t)stream);
   return gemm_tile(a, (hipStream_t)stream);
@@ -302,24 +285,12 @@ int64_t arcq_gemm_rw_silu_mul_slots(int64_t M, int64_t N, int64_t K) {
 
 int arcq_gemm_nvfp4_rw_silu_mul(const uint8_t* A, const uint8_t* RW, const uint8_t* SFA, const uint8_t* RSF, void* ACT, uint32_t* absmax_slots,
                                 int64_t M, int64_t N, int64_t K, float alpha_host, const float* alpha_dev, const void* bias, void* stream) {
-  const char* who = "arcq_gemm_nvfp4_rw_silu_mul";
-  if (M < 0 || N < 0 || K <= 0 || (K % 64) || (N % 8))
-    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0, K %% 64 == 0 and N %% 8 == 0 (M=%lld N=%lld K=%lld)", who, (long long)M, (long long)N,
-                (long long)K);
-  if (M == 0 || N == 0) return ARCQ_OK;
-  if (M <= kSkinnyMaxM)
-    return fail(ARCQ_ERR_UNSUPPORTED, "%s: M <= 16 is decode: use arcq_gemm_nvfp4_repacked_silu_absmax or arcq_linear_rmsnorm_silu_repacked", who);
-  if (!A || !RW || !SFA || !RSF || !ACT || !absmax_slots) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (M > INT32_MAX / 2 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40)) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(RW) | reinterpret_cast<uintptr_t>(ACT)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: A, RW and ACT must be 16-byte aligned", who);
-  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(RSF) | reinterpret_cast<uintptr_t>(absmax_slots)) & 3)
-    return fail(ARCQ_ERR_SHAPE, "%s: SFA, RSF and absmax_slots must be 4-byte aligned", who);
-  GemmArgs a;
-  a.A = A; a.B = RW; a.SFA = SFA; a.SFB = RSF; a.D = ACT;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.alpha_host = alpha_host; a.alpha_dev = alpha_dev; a.bias = (const uint16_t*)bias; a.residual = nullptr; a.out_dtype = ARCQ_OUT_BF16;
-  a.workspace = nullptr; a.workspace_bytes = 0;
+  GemmRule r{"arcq_gemm_nvfp4_rw_silu_mul"};
+  r.n_mult = 8; r.b = "RW"; r.sfb = "RSF"; r.d = "ACT"; r.slots = true;
+  r.prefill_only = "M <= 16 is decode: use arcq_gemm_nvfp4_repacked_silu_absmax or arcq_linear_rmsnorm_silu_repacked";
+  const int rc = gemm_checks(r, A, RW, SFA, RSF, ACT, absmax_slots, M, N, K, nullptr, nullptr, ARCQ_OUT_BF16);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  GemmArgs a = gemm_args(A, RW, SFA, RSF, ACT, M, N, K, alpha_host, alpha_dev, bias, nullptr, ARCQ_OUT_BF16, nullptr, 0);
   a.epilogue = kEpiSiluMul; a.absmax_slots = absmax_slots;
   a.b_layout = kBRepacked;
   return gemm_tile(a, (hipStream_t)stream);
@@ -337,9 +308,9 @@ static int fused_common_checks(const char* who, const void* X, const int16_t* id
   if (M == 0 || N == 0) return 1;                              // nothing to do
   if (!X || !idx || !RW || !RSF || !D) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
   if (N > INT32_MAX / 2 || KQ > 32767) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(RW) | reinterpret_cast<uintptr_t>(D)) & 15)
+  if ((bits(X) | bits(idx) | bits(RW) | bits(D)) & 15)
     return fail(ARCQ_ERR_SHAPE, "%s: X, reorder_index, RW and D must be 16-byte aligned", who);
-  if (reinterpret_cast<uintptr_t>(RSF) & 3) return fail(ARCQ_ERR_SHAPE, "%s: RSF must be 4-byte aligned", who);
+  if (bits(RSF) & 3) return fail(ARCQ_ERR_SHAPE, "%s: RSF must be 4-byte aligned", who);
   return ARCQ_OK;
 }
 
@@ -349,9 +320,8 @@ int arcq_linear_rmsnorm_repacked(const void* X, const void* Wn, float eps, const
   const char* who = "arcq_linear_rmsnorm_repacked";
   const int rc = fused_common_checks(who, X, reorder_index, RW, RSF, D, M, N, KQ, KE, variant, out_dtype);
   if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
-  if (!Wn || (reinterpret_cast<uintptr_t>(Wn) & 15)) return fail(Wn ? ARCQ_ERR_SHAPE : ARCQ_ERR_NULL, "%s: the norm weight must be a 16-byte aligned pointer", who);
-  if ((N % 4) == 0 && ((reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) & 7))
-    return fail(ARCQ_ERR_SHAPE, "%s: bias and residual must be 8-byte aligned", who);
+  if (!Wn || (bits(Wn) & 15)) return fail(Wn ? ARCQ_ERR_SHAPE : ARCQ_ERR_NULL, "%s: the norm weight must be a 16-byte aligned pointer", who);
+  if (const int e = check_epi_align(who, bias, residual, repacked_epi_align(N))) return e;
   FusedArgs f{};
   f.kind = ARCQ_SRC_RMSNORM; f.X = (const uint16_t*)X; f.Wn = (const uint16_t*)Wn; f.eps = eps; f.idx = reorder_index;
   f.RW = RW; f.RSF = RSF; f.D = D; f.M = (int)M; f.N = (int)N; f.KQ = (int)KQ; f.KE = (int)KE; f.variant = variant;
@@ -368,9 +338,9 @@ int arcq_linear_rmsnorm_silu_repacked(const void* X, const void* Wn, float eps, 
   if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
   if (N % 4) return fail(ARCQ_ERR_SHAPE, "%s: N %% 4 != 0 (interleaved gate|up rows)", who);
   if (!Wn || !absmax_slots) return fail(ARCQ_ERR_NULL, "%s: NULL norm weight / absmax_slots", who);
-  if ((reinterpret_cast<uintptr_t>(Wn) & 15) || (reinterpret_cast<uintptr_t>(absmax_slots) & 3)) return fail(ARCQ_ERR_SHAPE, "%s: misaligned norm weight / absmax_slots", who);
-  if (reinterpret_cast<uintptr_t>(act_scatter_index) & 3) return fail(ARCQ_ERR_SHAPE, "%s: misaligned act_scatter_index", who);
-  if (reinterpret_cast<uintptr_t>(bias) & 7) return fail(ARCQ_ERR_SHAPE, "%s: bias must be 8-byte aligned", who);
+  if ((bits(Wn) & 15) || (bits(absmax_slots) & 3)) return fail(ARCQ_ERR_SHAPE, "%s: misaligned norm weight / absmax_slots", who);
+  if (bits(act_scatter_index) & 3) return fail(ARCQ_ERR_SHAPE, "%s: misaligned act_scatter_index", who);
+  if (bits(bias) & 7) return fail(ARCQ_ERR_SHAPE, "%s: bias must be 8-byte aligned", who);
   FusedArgs f{};
   f.act_scatter = act_scatter_index;
   f.kind = ARCQ_SRC_RMSNORM; f.silu_act = 1; f.X = (const uint16_t*)X; f.Wn = (const uint16_t*)Wn; f.eps = eps; f.idx = reorder_index;
@@ -385,10 +355,9 @@ int arcq_linear_dynamic_repacked(const void* X, const int16_t* reorder_index, co
   const char* who = "arcq_linear_dynamic_repacked";
   const int rc = fused_common_checks(who, X, reorder_index, RW, RSF, D, M, N, KQ, KE, variant, out_dtype);
   if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
-  if (absmax_slots && (nslots <= 0 || nslots > INT32_MAX || (reinterpret_cast<uintptr_t>(absmax_slots) & 3)))
+  if (absmax_slots && (nslots <= 0 || nslots > INT32_MAX || (bits(absmax_slots) & 3)))
     return fail(ARCQ_ERR_SHAPE, "%s: absmax_slots given but nslots = %lld, or misaligned", who, (long long)nslots);
-  if ((N % 4) == 0 && ((reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) & 7))
-    return fail(ARCQ_ERR_SHAPE, "%s: bias and residual must be 8-byte aligned", who);
+  if (const int e = check_epi_align(who, bias, residual, repacked_epi_align(N))) return e;
   FusedArgs f{};
   f.kind = ARCQ_SRC_DYNAMIC; f.X = (const uint16_t*)X; f.idx = reorder_index; f.in_slots = absmax_slots; f.n_in_slots = absmax_slots ? (int)nslots : 0;
   f.scale_out = scale_out; f.RW = RW; f.RSF = RSF; f.D = D; f.M = (int)M; f.N = (int)N; f.KQ = (int)KQ; f.KE = (int)KE; f.variant = variant;

@@ -24,23 +24,12 @@ int arcq_mx_quantize_w(const void* W, const int16_t* reorder_index, uint8_t* QW,
 int arcq_gemm_mxfp4(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t K,
                     float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* workspace,
                     int64_t workspace_bytes, void* stream) {
-  const char* who = "arcq_gemm_mxfp4";
   (void)workspace;
   (void)workspace_bytes;
-  if (M < 0 || N < 0 || K <= 0 || (K % 128) || (N % 16))
-    return fail(ARCQ_ERR_SHAPE, "%s: need M,N >= 0, K %% 128 == 0 and N %% 16 == 0 (M=%lld N=%lld K=%lld)", who, (long long)M, (long long)N,
-                (long long)K);
-  if (out_dtype != ARCQ_OUT_BF16 && out_dtype != ARCQ_OUT_F32) return fail(ARCQ_ERR_SHAPE, "%s: bad out_dtype %d", who, out_dtype);
-  if (M == 0 || N == 0) return ARCQ_OK;
-  if (!A || !B || !SFA || !SFB || !D) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (M > (int64_t)65535 * 128 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40))
-    return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B) | reinterpret_cast<uintptr_t>(D)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: A, B and D must be 16-byte aligned", who);
-  if ((reinterpret_cast<uintptr_t>(SFA) | reinterpret_cast<uintptr_t>(SFB)) & 3)
-    return fail(ARCQ_ERR_SHAPE, "%s: SFA and SFB must be 4-byte aligned", who);
-  if ((reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(residual)) & 1)
-    return fail(ARCQ_ERR_SHAPE, "%s: bias and residual must be 2-byte aligned", who);
+  GemmRule r{"arcq_gemm_mxfp4"};
+  r.k_mult = 128; r.n_mult = 16; r.max_m = (int64_t)65535 * 128; r.epi_align = 2;
+  const int rc = gemm_checks(r, A, B, SFA, SFB, D, nullptr, M, N, K, bias, residual, out_dtype);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
   return gemm_mx(A, B, SFA, SFB, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, (hipStream_t)stream);
 }
 

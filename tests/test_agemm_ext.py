@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from arcquant_amd import _build_ext
+from arcquant_amd import _build_ext, _lib
 from oracle import oracle as O
 from tests.util import bits, outlier_activations, prescale, random_perm
 
@@ -44,8 +44,9 @@ def test_it_imports_from_its_build_directory_like_the_reference_module(ext):
 
 def test_errors_are_the_references_errors(ext):
     u8 = torch.zeros((1, 32), dtype=torch.uint8)
+    sf = torch.zeros(_lib.lib().arcq_sf_used_bytes(1, 64), dtype=torch.uint8)      # (a valid call but for the device: that is checked last)
     with pytest.raises(RuntimeError, match="GPU"):                   # no CPU path, no silent fallback
-        ext.matmul(u8, u8, torch.zeros(4, dtype=torch.uint8), torch.zeros(4, dtype=torch.uint8), 1.0)
+        ext.matmul(u8, u8, sf, sf, 1.0)
     with pytest.raises(RuntimeError, match="dtype"):                 # data_ptr<T>() of the reference throws on a dtype mismatch
         ext.reorder_quantize_x(X=torch.zeros((1, 64)), reorder_index=torch.zeros(64, dtype=torch.int16), KE=0)
     with pytest.raises(NotImplementedError):                         # KV-cache functions: out of scope, present so that imports succeed

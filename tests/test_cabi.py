@@ -118,3 +118,20 @@ def test_round2_entry_points_reject_bad_arguments_without_a_gpu():
     assert L.arcq_harness_attn_decode(P, P, P, P, P, 4, 28, 1152, 1152, None) == -1                       # pos >= Tmax
     assert L.arcq_harness_rmsnorm(P, 3584, P, P, 4, 3587, 1e-6, None) == -1
     assert L.arcq_harness_rmsnorm(P, 3584, P, P, 0, 3584, 1e-6, None) == 0
+
+
+def test_rejections_are_those_of_the_recorded_table():
+    """tests/golden/cabi_rejections.json (written by tests/golden/make_cabi_rejections.py) pins, for the eleven GEMM / linear entry points,
+    which fault a bad call reports and in which words: status and arcq_last_error() text must be equal, case by case.  No case of the table
+    can launch: each expects a rejection, or ARCQ_OK on an empty shape."""
+    import json
+    L = _lib.lib()
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "cabi_rejections.json")))
+    assert len(table) >= 500 and len({c["fn"] for c in table}) == 11
+    for c in table:
+        assert c["status"] in (-1, -2, -4) or (c["status"] == 0 and (c["M"] == 0 or c["N"] == 0)), c
+    for c in table:
+        st = getattr(L, c["fn"])(*c["args"])
+        assert st == c["status"], (c, st, L.arcq_last_error())
+        if st:
+            assert L.arcq_last_error().decode() == c["error"], c

@@ -79,13 +79,13 @@ def test_mirror_raises_on_dtype_shape_device():
     with pytest.raises(RuntimeError, match="uint8"):
         agemm.mx_matmul(A.float(), B, SA, SB, 1.0)
     with pytest.raises(RuntimeError, match="K=192"):
-        agemm.mx_matmul(A, B[:, :96], SA, SB, 1.0)
+        agemm.mx_matmul(A, B[:, :96].contiguous(), SA, SB, 1.0)
     with pytest.raises(RuntimeError, match="multiple of 128"):
-        agemm.mx_matmul(A[:, :96], B[:, :96], SA, SB, 1.0)
+        agemm.mx_matmul(A[:, :96].contiguous(), B[:, :96].contiguous(), SA, SB, 1.0)
     with pytest.raises(RuntimeError, match="multiple of 16"):
         agemm.mx_matmul(A, B[:24], SA, SB[:24], 1.0)
     with pytest.raises(RuntimeError, match="K/32"):
-        agemm.mx_matmul(A, B, SA[:, :4], SB, 1.0)
+        agemm.mx_matmul(A, B, SA[:, :4].contiguous(), SB, 1.0)
     with pytest.raises(RuntimeError, match="GPU"):
         agemm.mx_matmul(A, B, SA, SB, 1.0)
 
