@@ -25,9 +25,22 @@ __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
 // x rounded to bf16 and widened again, through gfx950's v_cvt_pk_bf16_f32 (what the float -> __bf16 cast compiles to):
 // two instructions where the integer formulation above plus the shift back take eight.  The same function for all 2^32 bit
 // patterns, NaN stays NaN (tools/probe_bf16.hip, checked exhaustively on MI355X).  Used by the quantisers, which round
-// EVERY element (RMSNorm, dynamic scale, residual); the GEMM epilogues keep the integer form (a few conversions per
-// thread, and their register allocation is tuned around it).
+// EVERY element (RMSNorm, dynamic scale, residual) and by the tile GEMM's interior-tile epilogue (128 values per lane); the other
+// GEMM epilogues keep the integer form (a few conversions per thread, and their register allocation is tuned around it).
 __device__ __forceinline__ float round_to_bf16(float f) { return (float)(__bf16)f; }
+// (a, b) rounded to bf16, a in the low half: ONE v_cvt_pk_bf16_f32; the same bits as f32_to_bf16_bits on each
+__device__ __forceinline__ uint32_t pack_bf16x2_hw(float a, float b) {
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  const f32x2_t v = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
+}
+// a and b each rounded to bf16 and widened again, sharing one conversion (three instructions for the pair)
+__device__ __forceinline__ void round2_to_bf16(float& a, float& b) {
+  const uint32_t pk = pack_bf16x2_hw(a, b);
+  a = __uint_as_float(pk << 16);
+  b = __uint_as_float(pk & 0xffff0000u);
+}
 
 // ue4m3 byte -> fp32.  (bits << 20) is the value scaled by 2^-120 (subnormals included); one multiply undoes it.
 __device__ __forceinline__ float ue4m3_to_f32(uint32_t b) { return __uint_as_float((b & 0x7fu) << 20) * 0x1p120f; }

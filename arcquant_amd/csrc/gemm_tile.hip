@@ -28,8 +28,9 @@ namespace arcq {
 
 #ifdef ARCQ_STREAM_STAMPS
 // DIAGNOSTIC build only: the in-kernel clock of the K loop = delta s_memtime / delta s_memrealtime x 100 MHz
-// (MI355X_MICROARCH.md, "DVFS give-back" item 6), stamped once around the loop by wave 0 of every workgroup into a buffer
-// nothing else reads (tools/tile_clock.py).  The product library has no stamps.
+// (MI355X_MICROARCH.md, "DVFS give-back" item 6) and the phases of a tile, stamped by wave 0 of every workgroup into a buffer
+// nothing else reads (tools/tile_clock.py): kTileStamps (s_memtime, s_memrealtime) pairs per workgroup -- 0 kernel entry, 1 K loop
+// starts, 2 K loop ends, 3 first output store issued, 4 last output store issued.  The product library has no stamps.
 static unsigned long long* g_tile_stamps = nullptr;     // (stays NULL in gemm_tile_rw.hip: its kernels are not stamped)
 #ifndef ARCQ_TILE_REPACKED_UNIT
 extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpret_cast<unsigned long long*>(p); }
@@ -39,12 +40,19 @@ extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpre
     if (p.stamps && tid == 0) {                                                                                \
       unsigned long long t0_, t1_;                                                                             \
       asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0_), "=s"(t1_)::"memory"); \
-      p.stamps[(size_t)blockIdx.x * 4 + 2 * (k)] = t0_;                                                        \
-      p.stamps[(size_t)blockIdx.x * 4 + 2 * (k) + 1] = t1_;                                                    \
+      p.stamps[(size_t)blockIdx.x * (2 * kTileStamps) + 2 * (k)] = t0_;                                        \
+      p.stamps[(size_t)blockIdx.x * (2 * kTileStamps) + 2 * (k) + 1] = t1_;                                    \
     }                                                                                                          \
   } while (0)
 #else
 #define ARCQ_TILE_STAMP(k) do { } while (0)
+#endif
+
+// Interior-tile epilogue with 16-byte stores (two column tiles traded through v_permlane16_swap) instead of 8-byte ones: half the
+// store instructions, 64 contiguous bytes per output row and instruction instead of 32.  -DARCQ_TILE_WIDE_STORES=0 builds the 8-byte
+// arm of the A-B recorded in DESIGN.md 3.2 (tools/scripts/build_variant_lib.sh).
+#ifndef ARCQ_TILE_WIDE_STORES
+#define ARCQ_TILE_WIDE_STORES 1
 #endif
 
 // kStagger (8-wave tiles): the two waves of a SIMD (w and w + 4) run half a step apart -- waves 0-3 multiply step k and
@@ -93,11 +101,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
   const int gsz = min(p.tiles_m - first_m, kGroupM);
   const int tm = first_m + (bid % per_group) % gsz;
   const int tn = (bid % per_group) / gsz;
-  const int m0 = tm * BM, n0 = tn * BN;
+  // (workgroup-uniform; pinned to SGPRs: with the tile origin left to the compiler, hipcc moved the whole tile-order arithmetic to the
+  // vector unit in one build of the interior epilogue and kept two more VGPRs through the K loop)
+  const int m0 = __builtin_amdgcn_readfirstlane(tm * BM), n0 = __builtin_amdgcn_readfirstlane(tn * BN);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wr = wave / WAVES_N, wc = wave % WAVES_N;
+  ARCQ_TILE_STAMP(0);
   const int half_k = p.K >> 1, atoms_k = p.K >> 6;
   const int a_begin = split * p.atoms_per_split, a_end = min(atoms_k, a_begin + p.atoms_per_split);   // never empty
 
@@ -324,20 +335,40 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
     __syncthreads();
   };
 
-  // ---- prologue: tile 0 into buffer 0, registers <- step 1
+  // ---- prologue: tile 0 into buffer 0, registers <- step 1.  Both steps are requested together and only step 0 is awaited (a
+  //      counted vmcnt: loads return in order): one memory round trip before the first MFMA, not two dependent ones.  The second
+  //      register set exists only here.
   load_step(a_begin);
-  store_step(lds_a0, lds_b0);
+  Staged sa0[A_UNITS], sb0[B_UNITS];
+#pragma unroll
+  for (int u = 0; u < A_UNITS; ++u) sa0[u] = sa[u];
+#pragma unroll
+  for (int u = 0; u < B_UNITS; ++u) sb0[u] = sb[u];
   load_step(min(a_begin + 1, a_end - 1));
+  __builtin_amdgcn_sched_barrier(0);            // keep the second set of loads above the first wait
+#pragma unroll
+  for (int u = 0; u < A_UNITS; ++u)
+    if (!A_PARTIAL || tid < BM * 2) stage_store(lds_a0, a_slot[u], sa0[u], a_live[u]);
+#pragma unroll
+  for (int u = 0; u < B_UNITS; ++u)
+    if (!B_PARTIAL || tid < BN * 2) stage_store(lds_b0, b_slot[u], sb0[u], b_live[u]);
   if (kStagger && late) {                       // the late group enters the loop with step 1 staged and step 2 in registers
     store_step(lds_a1, lds_b1);
     load_step(min(a_begin + 2, a_end - 1));
   }
   __syncthreads();
   int kt = a_begin;
+  // alpha_dev is workgroup-uniform: a scalar load ahead of the loop, held in one SGPR across it (no tile's epilogue starts with a
+  // vector-memory round trip); the product with alpha_host is formed after the loop, so that no VGPR is live through it
+#ifndef ARCQ_EXPERIMENT_GENERAL_EPILOGUE
+  float alpha_dev = 1.0f;
+  if (p.alpha_dev) alpha_dev = *reinterpret_cast<const __attribute__((address_space(4))) float*>(reinterpret_cast<uintptr_t>(p.alpha_dev));
+  asm volatile("" : "+s"(alpha_dev));
+#endif
   // the second-dispatched half of an 8-wave workgroup loses every issue arbitration against its SIMD partner at equal
   // priority; a static priority for it (never flipped) measured +0.8 % (1192-1203 -> 1209-1212 TFLOP/s)
   if (WAVES_M * WAVES_N == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-  ARCQ_TILE_STAMP(0);
+  ARCQ_TILE_STAMP(1);
   if constexpr (kPipe) {
     for (; kt + 1 < a_end; kt += 2) {
       k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1);
@@ -351,13 +382,118 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
     }
     if (kt < a_end) k_step(kt, lds_a0, lds_b0, lds_a1, lds_b1);
   }
-  ARCQ_TILE_STAMP(1);
+  ARCQ_TILE_STAMP(2);
 
   // ---- epilogue.  16x16 tiles: lane holds D[m = +(lane & 15)][n = +4*(lane >> 4) + r], r = 0..3.
   //      32x32 tiles: lane holds D[m = +(lane & 31)][n = +8*g + 4*(lane >> 5) + r], g = 0..3, r = 0..3.
+#ifdef ARCQ_EXPERIMENT_GENERAL_EPILOGUE       // TIMING EXPERIMENT ONLY (tools/scripts/build_variant_lib.sh): the epilogue as it was before the interior path
   const float alpha = p.alpha_host * (p.alpha_dev ? *p.alpha_dev : 1.0f);
+#else
+  const float alpha = p.alpha_host * alpha_dev;
+#endif
   const bool vec_ok = (p.N & 3) == 0;
   uint32_t act_max = 0;                       // kEpiSiluMul: max |act| of this thread, as bf16 magnitude bits
+  // INTERIOR tiles (every row and column inside the matrix, bf16 output, N % 4 == 0, no split-K, 8-byte-aligned operands): one
+  // workgroup-uniform test selects a straight-line epilogue -- no bounds, dtype or operand test per quad, bf16 rounding through
+  // v_cvt_pk_bf16_f32, one 32-bit row offset per row tile against a uniform tile base (the TN column tiles are immediate offsets).
+  // Bias / residual presence are compile-time parameters of it.  The SAME operations in the same order as store4: identical bits.
+  [[maybe_unused]] auto interior_epilogue = [&](auto has_bias, auto has_res) __attribute__((always_inline)) {
+    constexpr bool kBias = decltype(has_bias)::value, kRes = decltype(has_res)::value;
+    constexpr bool kSilu = kEpi == kEpiSiluMul;                     // D is [M, N / 2]: one dword per quad
+    constexpr uint32_t kElem = kSilu ? 1 : 2;                       // output bytes per GEMM column
+    unsigned char* const tile_d = reinterpret_cast<unsigned char*>(p.D) + ((size_t)m0 * p.N + n0) * kElem;
+    const unsigned char* const tile_r = kRes ? reinterpret_cast<const unsigned char*>(p.residual) + ((size_t)m0 * p.N + n0) * 2 : nullptr;
+    // the lane's place in the tile, from a thread id the compiler cannot tie to the values it keeps through the K loop: nothing of
+    // this path is computed before the loop or carried across it (the loop's register allocation stays the one it was tuned with)
+    uint32_t t = tid;
+    asm volatile("" : "+v"(t));
+    const uint32_t lane_row = (t >> 6) / WAVES_N * WM + (t & 15), lane_col = (t >> 6) % WAVES_N * WN + 4 * ((t >> 4) & 3);
+    uint32_t off = lane_row * (uint32_t)p.N + lane_col;             // in elements of the GEMM's [M, N]; < 2^31 (checked by the caller)
+    const uint32_t row_step = 16u * (uint32_t)p.N;
+    // 16-byte stores: first column of the 8 a lane stores per pair of column tiles (SiLU * up stores one dword per quad and keeps it)
+    constexpr bool kWide = ARCQ_TILE_WIDE_STORES && !kSilu && TN % 2 == 0;
+    typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));       // (rows are 8-byte aligned: N % 4 == 0)
+    [[maybe_unused]] const uint32_t g4 = (t >> 4) & 3;
+    [[maybe_unused]] uint32_t off_w = off - 4 * g4 + ((g4 & 1) ? 16 + 4 * (g4 - 1) : 4 * g4);
+    [[maybe_unused]] uint2 held = make_uint2(0, 0);
+    float bias_f[TN][4];
+    if constexpr (kBias) {
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const uint2 b = *reinterpret_cast<const uint2*>(p.bias + n0 + lane_col + j * 16);
+        bias_f[j][0] = bf16_bits_to_f32(b.x & 0xffffu); bias_f[j][1] = bf16_bits_to_f32(b.x >> 16);
+        bias_f[j][2] = bf16_bits_to_f32(b.y & 0xffffu); bias_f[j][3] = bf16_bits_to_f32(b.y >> 16);
+      }
+    }
+    uint2 res_cur[TN], res_nxt[TN];
+    auto res_load = [&](uint32_t o, uint2 (&r)[TN]) {
+#pragma unroll
+      for (int j = 0; j < TN; ++j) r[j] = *reinterpret_cast<const uint2*>(tile_r + (size_t)o * 2 + j * 32);
+    };
+    if constexpr (kRes) res_load(off, res_cur);
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      if constexpr (kRes) { if (i + 1 < TM) res_load(off + row_step, res_nxt); }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        float d[4] = {alpha * acc[i][j][0], alpha * acc[i][j][1], alpha * acc[i][j][2], alpha * acc[i][j][3]};
+        if constexpr (kSilu) {
+          if constexpr (kBias) {
+#pragma unroll
+            for (int r = 0; r < 4; r += 2) {
+              round2_to_bf16(d[r], d[r + 1]);
+              d[r] += bias_f[j][r];
+              d[r + 1] += bias_f[j][r + 1];
+            }
+          }
+          const uint32_t y01 = pack_bf16x2_hw(d[0], d[1]), y23 = pack_bf16x2_hw(d[2], d[3]);
+          const uint32_t a0 = silu_mul_bf16(y01 & 0xffffu, y01 >> 16), a1 = silu_mul_bf16(y23 & 0xffffu, y23 >> 16);
+          *reinterpret_cast<uint32_t*>(tile_d + (size_t)off + j * 16) = a0 | (a1 << 16);
+          act_max = max(act_max, max(a0 & 0x7fffu, a1 & 0x7fffu));
+        } else {
+          if constexpr (kBias) {
+#pragma unroll
+            for (int r = 0; r < 4; r += 2) {
+              round2_to_bf16(d[r], d[r + 1]);
+              d[r] += bias_f[j][r];
+              d[r + 1] += bias_f[j][r + 1];
+            }
+          }
+          if constexpr (kRes) {
+            const uint32_t rw[2] = {res_cur[j].x, res_cur[j].y};
+#pragma unroll
+            for (int r = 0; r < 4; r += 2) {
+              round2_to_bf16(d[r], d[r + 1]);
+              d[r] += bf16_bits_to_f32(rw[r >> 1] & 0xffffu);
+              d[r + 1] += bf16_bits_to_f32(rw[r >> 1] >> 16);
+            }
+          }
+          const uint2 pk = make_uint2(pack_bf16x2_hw(d[0], d[1]), pack_bf16x2_hw(d[2], d[3]));
+          if constexpr (kWide) {
+            // column tiles j - 1 (held) and j: v_permlane16_swap trades the odd 16-lane rows of the first with the even rows of the
+            // second, after which a lane owns 8 CONSECUTIVE columns -- of tile j - 1 in the even rows, of tile j in the odd ones
+            if (j & 1) {
+              const auto lo = __builtin_amdgcn_permlane16_swap(held.x, pk.x, false, false);
+              const auto hi = __builtin_amdgcn_permlane16_swap(held.y, pk.y, false, false);
+              const u32x4_a8 v = {lo[0], hi[0], lo[1], hi[1]};
+              *reinterpret_cast<u32x4_a8*>(tile_d + (size_t)off_w * 2 + (j >> 1) * 64) = v;
+            } else {
+              held = pk;
+            }
+          } else {
+            *reinterpret_cast<uint2*>(tile_d + (size_t)off * 2 + j * 32) = pk;
+          }
+        }
+        if (i == 0 && j == 0) ARCQ_TILE_STAMP(3);
+      }
+      if constexpr (kRes) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) res_cur[j] = res_nxt[j];
+      }
+      off += row_step;
+      off_w += row_step;
+    }
+  };
   // `pre`: the four bias / residual values of (m, n .. n + 3) already fetched with ONE 8-byte load each (N % 4 == 0), two bf16 per dword;
   // otherwise they are read element by element (ragged N).  Same operations in the same order either way.
   auto store4 = [&](int m, int n, float d0, float d1, float d2, float d3, bool pre, uint2 bias2, uint2 res2) __attribute__((always_inline)) {
@@ -404,7 +540,31 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
       else for (int r = 0; r < 4; ++r) if (n + r < p.N) o[r] = (uint16_t)f32_to_bf16_bits(d[r]);
     }
   };
-  if constexpr (kMfma32) {
+#ifdef ARCQ_EXPERIMENT_GENERAL_EPILOGUE
+  constexpr bool kInteriorPath = false;
+#else
+  constexpr bool kInteriorPath = !kMfma32;
+#endif
+  bool interior = false;
+  if constexpr (kInteriorPath)
+    interior = m0 + BM <= p.M && n0 + BN <= p.N && vec_ok && p.splits <= 1 && p.out_dtype == ARCQ_OUT_BF16 && (int64_t)BM * p.N < (1ll << 31) &&
+               ((reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.residual)) & 7) == 0;
+  if (interior) {
+    if constexpr (kInteriorPath) {
+      using T = std::true_type;
+      using F = std::false_type;
+      if constexpr (kEpi == kEpiSiluMul) {            // (no residual: the silu-mul epilogue has none)
+        if (p.bias) interior_epilogue(T{}, F{});
+        else interior_epilogue(F{}, F{});
+      } else if (p.bias) {
+        if (p.residual) interior_epilogue(T{}, T{});
+        else interior_epilogue(T{}, F{});
+      } else {
+        if (p.residual) interior_epilogue(F{}, T{});
+        else interior_epilogue(F{}, F{});
+      }
+    }
+  } else if constexpr (kMfma32) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -441,7 +601,10 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
       for (int i = 0; i < TM; ++i) {
         if (i + 1 < TM) res_load(i + 1, res_nxt);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) store4(mb + i * 16, nb + j * 16, acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3], true, bias_v[j], res_cur[j]);
+        for (int j = 0; j < TN; ++j) {
+          store4(mb + i * 16, nb + j * 16, acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3], true, bias_v[j], res_cur[j]);
+          if (i == 0 && j == 0) ARCQ_TILE_STAMP(3);
+        }
 #pragma unroll
         for (int j = 0; j < TN; ++j) res_cur[j] = res_nxt[j];
       }
@@ -449,10 +612,13 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
+        for (int j = 0; j < TN; ++j) {
           store4(mb + i * 16, nb + j * 16, acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3], false, make_uint2(0, 0), make_uint2(0, 0));
+          if (i == 0 && j == 0) ARCQ_TILE_STAMP(3);
+        }
     }
   }
+  ARCQ_TILE_STAMP(4);
   if (kEpi == kEpiSiluMul) {
     __shared__ uint32_t wave_max[WAVES_M * WAVES_N];
 #pragma unroll

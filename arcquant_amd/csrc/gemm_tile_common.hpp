@@ -30,10 +30,11 @@ struct TileParams {
   // silu(gate)*up and slots[blockIdx.x] receives this workgroup's max |D| (bit pattern) for the dynamic quantiser
   int epi;
   unsigned int* slots;
-#ifdef ARCQ_STREAM_STAMPS      // DIAGNOSTIC build only (make diag): [workgroup][4] = s_memtime / s_memrealtime before and after the K loop
+#ifdef ARCQ_STREAM_STAMPS      // DIAGNOSTIC build only (make diag): [workgroup][kTileStamps][2] = s_memtime / s_memrealtime at the phase boundaries of a tile
   unsigned long long* stamps;
 #endif
 };
+constexpr int kTileStamps = 5;          // kernel entry, K loop starts, K loop ends, first / last output store issued (gemm_tile.hip)
 
 constexpr int kBK = 64;                 // K elements per step = one scale-factor atom column (4 groups)
 constexpr int kRowBytes = kBK * 2;      // fp16 row of a tile in LDS

@@ -1,16 +1,42 @@
 #!/usr/bin/env python3
-"""A-B of two builds of the library on the tile GEMM (tuning aid): steady-state time per launch, each build in its own subprocess,
-rounds interleaved.  usage: tile_lib_ab.py name=path[:ENV=VAL] ..."""
+"""A-B of two builds of the library on the tile GEMM (tuning aid): steady-state time per launch (bench.py's sustained-clock protocol),
+each build in its own subprocess, rounds interleaved; per shape and build the values of every round, their median and their
+run-to-run band (max - min).  usage: tile_lib_ab.py [--rounds N] name=path[:ENV=VAL] ...     (the comparator first)"""
 import json
 import os
+import statistics
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from tools.tile_persist_ab import CODE  # noqa: E402
 
-SHAPES = [(4096, 4096, 4096, 0), (8192, 8192, 8192, 0), (4096, 3584, 18944, 0), (4096, 37888, 3584, 1)]
+# M, N, KQ, epilogue: "" plain, "silu" SiLU * up, "bias", "residual"      (the model shapes: down, gate|up, q|k|v with its bias, o with its residual)
+SHAPES = [(4096, 4096, 4096, ""), (8192, 8192, 8192, ""), (4096, 3584, 18944, ""), (4096, 37888, 3584, "silu"), (4096, 10752, 3584, "bias"),
+          (4096, 3584, 3584, "residual")]
+
+CODE = """
+import json, sys, torch
+sys.path.insert(0, {root!r})
+import bench
+from arcquant_amd import agemm
+dev = torch.device('cuda:0')
+out = []
+for (M, N, KQ, epi) in {shapes!r}:
+    p = bench.make_problem(M, N, KQ, 64, dev)
+    g = torch.Generator().manual_seed(N)
+    bias = torch.randn(N, generator=g).to(torch.bfloat16).to(dev) if epi == 'bias' else None
+    res = torch.randn(M, N, generator=g).to(torch.bfloat16).to(dev) if epi == 'residual' else None
+    if epi == 'silu':
+        f = lambda: agemm.matmul_silu_mul(p['qx'], p['qw'], p['sfx'], p['sfw'], p['alpha'])
+    else:
+        o = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
+        f = lambda: agemm.matmul(p['qx'], p['qw'], p['sfx'], p['sfw'], p['alpha'], bias=bias, residual=res, out=o)
+    us = bench.time_events_steady(f, 100, warm_ms=60.0)
+    out.append({{"shape": [M, N, KQ], "epilogue": epi, "us": round(us, 2)}})
+    del p
+    torch.cuda.empty_cache()
+print("RESULT " + json.dumps(out))
+"""
 
 
 def run(spec):
@@ -27,10 +53,18 @@ def run(spec):
 
 
 if __name__ == "__main__":
-    specs = dict(a.split("=", 1) for a in sys.argv[1:])
+    args = sys.argv[1:]
+    rounds = 3
+    if args and args[0] == "--rounds":
+        rounds, args = int(args[1]), args[2:]
+    specs = dict(a.split("=", 1) for a in args)
     acc = {n: [] for n in specs}
-    for rnd in range(2):
+    for rnd in range(rounds):
         for n, s in specs.items():
             acc[n].append(run(s))
     for i, shp in enumerate(SHAPES):
-        print(json.dumps({"shape": shp, **{n: [r[i]["us"] for r in acc[n]] for n in specs}}), flush=True)
+        row = {"shape": list(shp[:3]), "epilogue": shp[3] or "plain"}
+        for n in specs:
+            us = [r[i]["us"] for r in acc[n]]
+            row[n] = {"us": us, "median": round(statistics.median(us), 2), "band": round(max(us) - min(us), 2)}
+        print(json.dumps(row), flush=True)
