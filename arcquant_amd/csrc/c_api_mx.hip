@@ -33,4 +33,23 @@ int arcq_gemm_mxfp4(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, cons
   return gemm_mx(A, B, SFA, SFB, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, (hipStream_t)stream);
 }
 
+int arcq_mx_rmsnorm_quantize_x(const void* X, const void* Wn, float eps, const int16_t* reorder_index, uint8_t* QX, uint8_t* SFX, int64_t M,
+                               int64_t KQ, int64_t KE, void* stream) {
+  return mx_rmsnorm_quantize_x(X, Wn, eps, reorder_index, QX, SFX, M, KQ, KE, (hipStream_t)stream);
+}
+
+int arcq_mx_silu_mul_quantize_x(const void* GU, const int16_t* reorder_index, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE,
+                                int layout, void* stream) {
+  return mx_silu_mul_quantize_x(GU, reorder_index, QX, SFX, M, KQ, KE, layout, (hipStream_t)stream);
+}
+
+int arcq_gemm_mxfp4_silu_mul(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* ACT, int64_t M, int64_t N, int64_t K,
+                             float alpha_host, const float* alpha_dev, const void* bias, void* stream) {
+  GemmRule r{"arcq_gemm_mxfp4_silu_mul"};
+  r.k_mult = 128; r.n_mult = 16; r.max_m = (int64_t)65535 * 128; r.epi_align = 2; r.d = "ACT";
+  const int rc = gemm_checks(r, A, B, SFA, SFB, ACT, nullptr, M, N, K, bias, nullptr, ARCQ_OUT_BF16);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_silu_mul(A, B, SFA, SFB, ACT, M, N, K, alpha_host, alpha_dev, bias, (hipStream_t)stream);
+}
+
 }  // extern "C"

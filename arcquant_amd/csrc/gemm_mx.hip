@@ -19,6 +19,11 @@
 //   mx_small_kernel  M <= kMxSmallM: one 16-column slice of B per workgroup (each weight byte is read by ONE workgroup
 //                    when M <= 16), 8 waves splitting K, four K steps of loads in flight per wave, 16x16x128 MFMA, partial
 //                    sums added in LDS in a fixed order.
+//
+// Both kernels take the epilogue as a template parameter.  kEpiSiluMul (arcq_gemm_mxfp4_silu_mul): B's rows interleave gate and up
+// (g0, u0, g1, u1, ...), D = bf16 [M, N/2] receives silu(y_gate) * y_up with torch's roundings, y being the bf16 value the plain epilogue
+// would store (never written).  A lane holds ONE output column, so gate and up of a pair sit in neighbouring lanes of a DPP quad (N % 16
+// == 0: a quad of lanes is inside or outside n < N as a whole); see mx_silu_pair.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -65,6 +70,31 @@ __device__ __forceinline__ void mx_store(const MxArgs& p, float alpha, int m, in
   else reinterpret_cast<uint16_t*>(p.D)[o] = (uint16_t)f32_to_bf16_bits(d);
 }
 
+// bf16 bits of the value mx_store writes for a bf16 output without residual: bf16(alpha * acc), then + bias -> bf16
+__device__ __forceinline__ uint32_t mx_y_bits(float alpha, float acc, bool has_bias, float bias) {
+  const uint32_t y = f32_to_bf16_bits(alpha * acc);
+  return has_bias ? f32_to_bf16_bits(bf16_bits_to_f32(y) + bias) : y;
+}
+
+// lane <- the lane of its DPP quad at position kPerm[lane & 3] (quad_perm; every lane of the quad must be active)
+template <int kCtrl>
+__device__ __forceinline__ uint32_t dpp_quad(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, 0xf, 0xf, true);
+}
+constexpr int kQuadSwap1 = 0xB1;   // quad_perm:[1,0,3,2]: the gate / up partner
+constexpr int kQuadSwap2 = 0x4E;   // quad_perm:[2,3,0,1]: the neighbouring pair
+
+// SiLU*up of TWO output rows r0, r1 held by a (gate, up) lane pair: y0 / y1 = this lane's bf16 outputs (its own column) in those rows.
+// The even lane (gate column) computes row r0 and the odd lane (up column) row r1 -- one activation per lane, none computed twice:
+// each sends the value the other needs in ONE exchange.  A second exchange brings in the activation of the next column pair, so that
+// lanes 0 and 1 of a quad each hold two adjacent activations of their row: returns them packed (valid where (lane & 2) == 0, for
+// row r0 in even lanes and r1 in odd lanes, columns n/2 and n/2 + 1 of lane 0's n).
+__device__ __forceinline__ uint32_t mx_silu_pair(uint32_t y0, uint32_t y1, bool odd) {
+  const uint32_t got = dpp_quad<kQuadSwap1>(odd ? y0 : y1);
+  const uint32_t act = silu_mul_bf16(odd ? got : y0, odd ? y1 : got);
+  return act | (dpp_quad<kQuadSwap2>(act) << 16);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- tiled
 constexpr int kMxTile = 128;
 constexpr int kMxOpBytes = kMxTile * 64;                     // one operand tile of one K step: 128 rows x 64 bytes
@@ -75,6 +105,7 @@ constexpr int kMxBufBytes = 2 * kMxOpBytes + 2 * kMxTile * 4;   // A, B, then on
 // layout, the swizzle gives them four different chunks (conflict-free, and no padding: 4 workgroups fit a CU's LDS).
 __device__ __forceinline__ int mx_lds_off(int r, int c) { return r * 64 + ((c ^ (r >> 2)) & 3) * 16; }
 
+template <int kEpi>
 __global__ __launch_bounds__(256) void mx_tile_kernel(MxArgs p) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kMxBufBytes];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -170,10 +201,22 @@ __global__ __launch_bounds__(256) void mx_tile_kernel(MxArgs p) {
     for (int j = 0; j < 2; ++j) {
       const int n = n0 + wn * 64 + j * 32 + r32;
       if (n >= p.N) continue;
+      if constexpr (kEpi == kEpiSiluMul) {
+        const bool odd = lane & 1;
+        const float bias = p.bias ? bf16_bits_to_f32(p.bias[n]) : 0.0f;
+        uint16_t* act = reinterpret_cast<uint16_t*>(p.D) + (n >> 1);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (m < p.M) mx_store(p, alpha, m, n, acc[i][j][r]);
+        for (int r = 0; r < 16; r += 2) {                    // rows r and r + 1 of the register tile are adjacent rows of D
+          const uint32_t pk = mx_silu_pair(mx_y_bits(alpha, acc[i][j][r], p.bias, bias), mx_y_bits(alpha, acc[i][j][r + 1], p.bias, bias), odd);
+          const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h + (odd ? 1 : 0);
+          if (!(lane & 2) && m < p.M) *reinterpret_cast<uint32_t*>(act + (size_t)m * (size_t)(p.N >> 1)) = pk;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+          if (m < p.M) mx_store(p, alpha, m, n, acc[i][j][r]);
+        }
       }
     }
 }
@@ -183,6 +226,7 @@ constexpr int kMxSmallM = 64;
 constexpr int kMxSmallWaves = 8;
 constexpr int kMxSmallUnroll = 4;
 
+template <int kEpi>
 __global__ __launch_bounds__(64 * kMxSmallWaves) void mx_small_kernel(MxArgs p) {
   __shared__ float part[kMxSmallWaves][64][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -219,14 +263,42 @@ __global__ __launch_bounds__(64 * kMxSmallWaves) void mx_small_kernel(MxArgs p) 
   if (wave != 0) return;
   const float alpha = p.alpha_host * (p.alpha_dev ? *p.alpha_dev : 1.0f);
   const int n = n0 + r16;
+  float t[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    float t = part[0][lane][r];
+    t[r] = part[0][lane][r];
 #pragma unroll
-    for (int w = 1; w < kMxSmallWaves; ++w) t += part[w][lane][r];
-    const int m = m0 + 4 * q + r;
-    if (m < p.M) mx_store(p, alpha, m, n, t);
+    for (int w = 1; w < kMxSmallWaves; ++w) t[r] += part[w][lane][r];
   }
+  if constexpr (kEpi == kEpiSiluMul) {
+    const bool odd = lane & 1;
+    const float bias = p.bias ? bf16_bits_to_f32(p.bias[n]) : 0.0f;
+    uint16_t* act = reinterpret_cast<uint16_t*>(p.D) + (n >> 1);
+#pragma unroll
+    for (int r = 0; r < 4; r += 2) {
+      const uint32_t pk = mx_silu_pair(mx_y_bits(alpha, t[r], p.bias, bias), mx_y_bits(alpha, t[r + 1], p.bias, bias), odd);
+      const int m = m0 + 4 * q + r + (odd ? 1 : 0);
+      if (!(lane & 2) && m < p.M) *reinterpret_cast<uint32_t*>(act + (size_t)m * (size_t)(p.N >> 1)) = pk;
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = m0 + 4 * q + r;
+      if (m < p.M) mx_store(p, alpha, m, n, t[r]);
+    }
+  }
+}
+
+template <int kEpi>
+static int mx_launch_gemm(const MxArgs& p, const char* who, hipStream_t stream) {
+  if (p.M <= kMxSmallM)
+    hipLaunchKernelGGL(mx_small_kernel<kEpi>, dim3((unsigned)(p.N / 16), (unsigned)((p.M + 15) / 16)), dim3(64 * kMxSmallWaves), 0, stream, p);
+  else
+    hipLaunchKernelGGL(mx_tile_kernel<kEpi>, dim3((unsigned)((p.N + kMxTile - 1) / kMxTile), (unsigned)((p.M + kMxTile - 1) / kMxTile)), dim3(256), 0,
+                       stream, p);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return ARCQ_OK;
 }
 
 int gemm_mx(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t Kp,
@@ -236,14 +308,18 @@ int gemm_mx(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_
   p.M = (int)M; p.N = (int)N; p.Kp = (int)Kp;
   p.alpha_host = alpha_host; p.alpha_dev = alpha_dev;
   p.bias = (const uint16_t*)bias; p.residual = (const uint16_t*)residual; p.out_dtype = out_dtype;
-  if (M <= kMxSmallM)
-    hipLaunchKernelGGL(mx_small_kernel, dim3((unsigned)(N / 16), (unsigned)((M + 15) / 16)), dim3(64 * kMxSmallWaves), 0, stream, p);
-  else
-    hipLaunchKernelGGL(mx_tile_kernel, dim3((unsigned)((N + kMxTile - 1) / kMxTile), (unsigned)((M + kMxTile - 1) / kMxTile)), dim3(256), 0,
-                       stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_mxfp4: launch failed: %s", hipGetErrorString(e));
-  return ARCQ_OK;
+  return mx_launch_gemm<kEpiPlain>(p, "arcq_gemm_mxfp4", stream);
+}
+
+// ACT = bf16 [M, N/2]; the same contraction, kernel choice and accumulation order as gemm_mx
+int gemm_mx_silu_mul(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* ACT, int64_t M, int64_t N, int64_t Kp,
+                     float alpha_host, const float* alpha_dev, const void* bias, hipStream_t stream) {
+  MxArgs p;
+  p.A = A; p.B = B; p.SFA = SFA; p.SFB = SFB; p.D = ACT;
+  p.M = (int)M; p.N = (int)N; p.Kp = (int)Kp;
+  p.alpha_host = alpha_host; p.alpha_dev = alpha_dev;
+  p.bias = (const uint16_t*)bias; p.residual = nullptr; p.out_dtype = ARCQ_OUT_BF16;
+  return mx_launch_gemm<kEpiSiluMul>(p, "arcq_gemm_mxfp4_silu_mul", stream);
 }
 
 }  // namespace arcq

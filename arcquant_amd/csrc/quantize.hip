@@ -23,6 +23,7 @@
 #include "arcq_device.hpp"
 #include "arcq_internal.hpp"
 #include "quantize_device.hpp"
+#include "quantize_source_device.hpp"
 
 namespace arcq {
 
@@ -30,75 +31,7 @@ enum : int { kModeX = 0, kModeW = 1, kModeRms = 2 };
 
 constexpr int kQuantThreads = 256;
 
-__device__ __forceinline__ uint4 silu_mul_chunk(const uint4 g, const uint4 u) {
-  const uint32_t gw[4] = {g.x, g.y, g.z, g.w}, uw[4] = {u.x, u.y, u.z, u.w};
-  uint32_t o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    o[j] = silu_mul_bf16(gw[j] & 0xffffu, uw[j] & 0xffffu) | (silu_mul_bf16(gw[j] >> 16, uw[j] >> 16) << 16);
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
-// eight activations from sixteen interleaved values (g0, u0, g1, u1, ...): every dword is one (gate, up) pair
-__device__ __forceinline__ uint4 silu_mul_pairs(const uint4 lo, const uint4 hi) {
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  uint32_t o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    o[j] = silu_mul_bf16(w[2 * j] & 0xffffu, w[2 * j] >> 16) | (silu_mul_bf16(w[2 * j + 1] & 0xffffu, w[2 * j + 1] >> 16) << 16);
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
-// chunk c (8 activations) of a row: kSiluHalves: gate at g[8c..], up at u[8c..]; kSiluPairs: pairs at g[16c..]
-enum : int { kSiluNone = 0, kSiluHalves = 1, kSiluPairs = 2 };
-template <int kSilu>
-__device__ __forceinline__ uint4 silu_act_chunk(const uint16_t* g, const uint16_t* u, int64_t c) {
-  if (kSilu == kSiluPairs)
-    return silu_mul_pairs(*reinterpret_cast<const uint4*>(g + c * 16), *reinterpret_cast<const uint4*>(g + c * 16 + 8));
-  return silu_mul_chunk(*reinterpret_cast<const uint4*>(g + c * 8), *reinterpret_cast<const uint4*>(u + c * 8));
-}
-template <int kSilu>
-__device__ __forceinline__ uint32_t silu_act_elem(const uint16_t* g, const uint16_t* u, uint32_t i) {
-  if (kSilu == kSiluPairs) {
-    const uint32_t w = *reinterpret_cast<const uint32_t*>(g + 2 * i);
-    return silu_mul_bf16(w & 0xffffu, w >> 16);
-  }
-  return silu_mul_bf16(g[i], u[i]);
-}
-
-// Sum of squares of one row in the reference's association order (rmsnorm.cu:113-154), so that the
-// fp32 result is bit-identical to the oracle's: virtual thread v in [0, bdx = KQ/16) owns the 16-byte
-// chunks v and bdx + v and accumulates their 16 squares sequentially (the caller passes the partial sums of
-// v = tid and v = tid + 256); then the fixed tree s[v] += s[v + stride], stride = 256 ... 32, and a 32-lane shuffle.
-// The same tree with TWO barriers instead of seven: the stride-256 step adds two values this thread computed itself;
-// strides 128 and 64 only ever feed s[0..63], so wave 0 evaluates them for its 64 columns from four LDS reads;
-// stride 32 and below are shuffles.  `s` is an LDS array of >= 512 floats.  Returns rstd = 1 / sqrt(total / KQ + eps) in every
-// thread: thread 0 forms it (the correctly rounded double-precision evaluation is ~35 half-rate instructions -- done by all 256
-// threads of all resident workgroups it was ~2 us of the 18.5 us launch at 4096 x 4096) and publishes it with the second barrier.
-__device__ __forceinline__ float rms_rstd_tree(float* s, int bdx, float p_lo, float p_hi, int KQ, float eps) {
-  const int tid = threadIdx.x;
-  const float s256 = (tid + 256 < bdx) ? p_lo + p_hi : p_lo;           // stride 256
-  if (tid < bdx) s[tid] = s256;
-  __syncthreads();                                                     // (also publishes the staged row)
-  if (tid < 64) {
-    const float x0 = s[tid], x1 = s[tid + 64], x2 = s[tid + 128], x3 = s[tid + 192];
-    const float y0 = (tid + 128 < bdx) ? x0 + x2 : x0;                 // stride 128: columns tid and tid + 64
-    const float y1 = (tid + 192 < bdx) ? x1 + x3 : x1;
-    float z = (tid + 64 < bdx) ? y0 + y1 : y0;                         // stride 64
-    const float up = __shfl_down(z, 32, 64);
-    if (tid < 32 && tid + 32 < bdx) z = z + up;                        // stride 32
-    float val = tid < 32 ? z : 0.0f;
-    val += __shfl_down(val, 16, 64);                                       // lane 0's cone = reference's
-    val += dpp_row_shl<8>(val);                                            // strides 8 .. 1 stay inside lane 0's row of 16 (DPP)
-    val += dpp_row_shl<4>(val);
-    val += dpp_row_shl<2>(val);
-    val += dpp_row_shl<1>(val);
-    if (tid == 0) {
-      const float var = val / (float)KQ + eps;                             // rmsnorm.cu:157
-      s[256] = (float)(1.0 / sqrt((double)var));                           // oracle assumption A4
-    }
-  }
-  __syncthreads();
-  return s[256];
-}
+// silu(gate) * up on the fly, the RMSNorm row staging and rms_rstd_tree: quantize_source_device.hpp (shared with quantize_mx.hip)
 
 // Per-tensor dynamic scale (kModeX only, arcq_quantize_x_dyn / arcq_silu_mul_quantize_x_dyn), selected by kDyn:
 //   kDynState: `dyn` = one abs-max word per workgroup of a preceding abs-max kernel (`nslots` of them, plain stores:
@@ -189,28 +122,8 @@ __global__ __launch_bounds__(kQuantThreads) void quantize_rows_kernel(
     const uint16_t* xrow = X + (size_t)row * ldx;
     float rstd = 1.0f;
     if (kMode == kModeRms) {
-      float part[2] = {0.0f, 0.0f};
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {                              // bdx <= 512: virtual threads tid and tid + 256
-        const int v = tid + k * kQuantThreads;
-        if (v < bdx) {
-          float acc = 0.0f;
-#pragma unroll
-          for (int it = 0; it < 2; ++it) {
-            const int c = it * bdx + v;
-            uint4 d = *reinterpret_cast<const uint4*>(xrow + (size_t)c * 8);
-            lds_put_chunk(row_lds, c, d);
-            const uint32_t w4[4] = {d.x, d.y, d.z, d.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              float a = bf16_bits_to_f32(w4[j] & 0xffffu), b = bf16_bits_to_f32(w4[j] >> 16);
-              acc = acc + a * a;
-              acc = acc + b * b;
-            }
-          }
-          part[k] = acc;
-        }
-      }
+      float part[2];
+      rms_stage_row(row_lds, xrow, bdx, part);
       rstd = rms_rstd_tree(red, bdx, part[0], part[1], KQ, eps);
     } else {
       if (kSilu && gridDim.y > 1) {

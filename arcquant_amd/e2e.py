@@ -13,6 +13,9 @@ weights are random-init and quantised once with ``agemm.reorder_quantize_w`` (th
 ``select_num`` is 64 for every linear (the calibration artefact is not in the repo); the decode step is captured
 in a HIP graph, so host launch overhead does not pace the GPU (every arcquant_amd launch is stream-ordered and
 allocation-free apart from torch's caching allocator).
+
+``quant_type="MXFP4"`` runs the same layer structure on the block-scaled fp4 MFMA (``DecoderModel._forward_mx``): weights quantised with
+``agemm.mx_reorder_quantize_w`` (no per-tensor scale, alpha = 1), activations with the one-launch operators of ``arcquant_amd.mx``.
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ import time
 import torch
 import torch.nn.functional as F
 
-from . import agemm
+from . import agemm, mx
 
 
 @dataclasses.dataclass
@@ -54,17 +57,22 @@ class QLinear:
     ``out_f`` may be the concatenation of several projections that share their input (q|k|v, gate|up): they are
     then quantised as ONE tensor (one per-tensor scale) and computed by one GEMM launch."""
 
-    def __init__(self, in_f, out_f, select_num, device, gen, bias=False):
+    def __init__(self, in_f, out_f, select_num, device, gen, bias=False, quant_type="NVFP4"):
         w = (torch.randn(out_f, in_f, generator=gen, device=device, dtype=torch.float32) * 0.02).to(torch.bfloat16)
         # modeling_arc.py:37-40: QLinearLayer(bias=config.attention_bias | mlp_bias); added after the GEMM (`y = y + self.bias`)
         self.bias = (torch.randn(out_f, generator=gen, device=device, dtype=torch.float32) * 0.02).to(torch.bfloat16) if bias else None
         self.idx = torch.arange(in_f, dtype=torch.int16, device=device)
+        self.in_f, self.out_f, self.KE = in_f, out_f, select_num
+        self.RW = self.RSF = None
+        self.quant_type = quant_type
+        if quant_type == "MXFP4":            # codes [out_f, Kp/2] + E8M0 bytes [out_f, Kp/32]; no per-tensor scale: alpha = 1
+            self.W, self.SFW = agemm.mx_reorder_quantize_w(w, self.idx, select_num)
+            self.scale, self.scale_f = torch.ones(1, dtype=torch.float32, device=device), 1.0
+            return
         scale = torch.max(w).float() / (448.0 * 6.0)
         self.W, self.SFW = agemm.reorder_quantize_w((w / scale).contiguous(), self.idx, select_num)
         self.scale = scale.reshape(1)
         self.scale_f = float(scale)          # one sync at load time; lets alpha = scale_f * (device activation scale)
-        self.in_f, self.out_f, self.KE = in_f, out_f, select_num
-        self.RW = self.RSF = None
 
     def repack(self, release_reference=False):
         """Second copy of the weight in MFMA-operand-order tiles for the decode path (agemm.repack_w).  release_reference: keep
@@ -77,6 +85,8 @@ class QLinear:
         """GEMM against this weight (+ its bias, in the epilogue): the repacked kernel for decode-sized token counts where available.
         ``ops``: the module whose ``matmul_repacked`` / ``matmul_rw`` is called (the ctypes mirror or the extension module)."""
         kw.setdefault("bias", self.bias)
+        if self.quant_type == "MXFP4":
+            return agemm.mx_matmul(A, self.W, SFA, self.SFW, scale, **kw)
         if self.W is None:           # repacked only: one copy for every M (the repacked kernels where matmul_repacked would run)
             return ops.matmul_rw(A, self.RW, SFA, self.RSF, scale, self.out_f, **kw)
         if self.RW is not None and agemm.repacked_supported(A.shape[0], self.out_f, self.in_f + self.KE):
@@ -84,6 +94,8 @@ class QLinear:
         return agemm.matmul(A, self.W, SFA, self.SFW, scale, **kw)
 
     def bytes(self):
+        if self.quant_type == "MXFP4":   # Kp/2 code bytes + Kp/32 scale bytes per row
+            return self.W.numel() + self.SFW.numel()
         if self.W is None:           # repacked only: the padded RW / RSF it holds
             return self.RW.numel() + self.RSF.numel()
         return self.W.numel() + self.out_f * (self.in_f + self.KE) // 16
@@ -93,16 +105,28 @@ class DecoderModel:
     """fused=False: the reference's call structure (model/qLlamaLayer.py: separate q/k/v and gate/up GEMMs, torch
     abs/max/div before each activation quantise, torch residual adds).  fused=True: q|k|v and gate|up as one GEMM each,
     `reorder_quantize_x_dynamic` (1-2 launches instead of 5), SiLU*up in the gate|up GEMM epilogue (`matmul_silu_mul`),
-    residual add in the GEMM epilogue, one strided K|V cache append."""
+    residual add in the GEMM epilogue, one strided K|V cache append.
+    quant_type="MXFP4": the same two call structures on the MXFP4 operators (_forward_mx)."""
+
+    # MXFP4, fused=True: how a decode step (T <= 64 tokens, where mx_small_kernel runs) forms the down projection's input:
+    # "epilogue" = mx.matmul_silu_mul + mx_reorder_quantize_x (as prefill), "quantiser" = mx_matmul + mx.silu_mul_quantize_x(GU_PAIRS).
+    # Chosen by measurement (tools/mx_fused_bench.py, DESIGN.md 3.6): at the Qwen2.5-7B gate|up shape the epilogue route takes 34.3 us
+    # against 35.5 at M = 4 and 134 against 140 at M = 64.
+    mx_decode_route = "epilogue"
 
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
-                 repacked_only: bool = False):
+                 repacked_only: bool = False, quant_type: str = "NVFP4"):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
         the repack and every GEMM the repacked kernels do not serve runs through agemm.matmul_rw / matmul_rw_silu_mul."""
         if repacked_only and not fused:
             raise ValueError("DecoderModel: repacked_only=True needs fused=True (the unfused model is the reference's call structure)")
+        if quant_type not in ("NVFP4", "MXFP4"):
+            raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4 and MXFP4 are)")
+        if quant_type == "MXFP4" and repacked_only:
+            raise ValueError("DecoderModel: repacked_only applies to the NVFP4 weight layout only, not to quant_type='MXFP4'")
+        self.quant_type = quant_type
         self.cfg, self.device, self.batch, self.max_len, self.fused = cfg, device, batch, max_len, fused
         self.repacked_only = repacked_only
         self.attention = attention
@@ -128,18 +152,18 @@ class DecoderModel:
                 pass
         g = torch.Generator(device=device).manual_seed(0)
         h, it, ke = cfg.hidden_size, cfg.intermediate_size, cfg.select_num
-        ab, mb = cfg.attention_bias, cfg.mlp_bias
+        ab, mb, qt = cfg.attention_bias, cfg.mlp_bias, quant_type
         self.layers = []
         for _ in range(cfg.num_layers):
             self.layers.append(dict(
                 ln1=torch.ones(h, dtype=torch.bfloat16, device=device), ln2=torch.ones(h, dtype=torch.bfloat16, device=device),
-                **(dict(qkv=QLinear(h, 3 * h, ke, device, g, ab), gateup=QLinear(h, 2 * it, ke, device, g, mb)) if fused else
-                   dict(q=QLinear(h, h, ke, device, g, ab), k=QLinear(h, h, ke, device, g, ab), v=QLinear(h, h, ke, device, g, ab),
-                        gate=QLinear(h, it, ke, device, g, mb), up=QLinear(h, it, ke, device, g, mb))),
-                o=QLinear(h, h, ke, device, g, ab), down=QLinear(it, h, ke, device, g, mb),
+                **(dict(qkv=QLinear(h, 3 * h, ke, device, g, ab, qt), gateup=QLinear(h, 2 * it, ke, device, g, mb, qt)) if fused else
+                   dict(q=QLinear(h, h, ke, device, g, ab, qt), k=QLinear(h, h, ke, device, g, ab, qt), v=QLinear(h, h, ke, device, g, ab, qt),
+                        gate=QLinear(h, it, ke, device, g, mb, qt), up=QLinear(h, it, ke, device, g, mb, qt))),
+                o=QLinear(h, h, ke, device, g, ab, qt), down=QLinear(it, h, ke, device, g, mb, qt),
                 kv=torch.zeros(2, batch, cfg.num_heads, max_len, h // cfg.num_heads, dtype=torch.bfloat16, device=device)))
             self.layers[-1]["kc"], self.layers[-1]["vc"] = self.layers[-1]["kv"][0], self.layers[-1]["kv"][1]
-        if fused:
+        if fused and quant_type == "NVFP4":
             for L in self.layers:
                 for name in ("qkv", "o", "gateup", "down"):
                     L[name].repack(release_reference=repacked_only)
@@ -166,6 +190,8 @@ class DecoderModel:
 
     def forward(self, tokens: torch.Tensor, pos: int):
         """tokens [batch, q_len] int64; appends K/V at [pos, pos+q_len) and attends over [0, pos+q_len)."""
+        if self.quant_type == "MXFP4":
+            return self._forward_mx(tokens, pos)
         cfg = self.cfg
         bsz, q_len = tokens.shape
         nh, hd = cfg.num_heads, cfg.hidden_size // cfg.num_heads
@@ -246,6 +272,11 @@ class DecoderModel:
                 act = F.silu(gate) * up
                 qa, sfa, sa = self._quant_x(act, self.idx_i, ke)
                 hcur = hcur + self._ref_linear(L["down"], qa, sfa, sa * L["down"].scale)
+        return self._logits(hcur, bsz, q_len)
+
+    def _logits(self, hcur, bsz, q_len):
+        """Final norm of each sequence's last token and the lm_head product."""
+        cfg = self.cfg
         last = hcur.view(bsz, q_len, -1)[:, -1]                 # [bsz, hidden], row stride q_len * hidden
         if self.fused:
             # the final norm as one launch (include/arcq_harness.h; torch's F.rms_norm is ~15 small kernels on this stack)
@@ -258,6 +289,53 @@ class DecoderModel:
         else:
             hn = F.rms_norm(last, (cfg.hidden_size,), self.norm, cfg.eps)
         return hn @ self.lm_head.t()
+
+    def _forward_mx(self, tokens: torch.Tensor, pos: int):
+        """forward() for quant_type="MXFP4".  Per layer, fused=True:
+            mx.rmsnorm_quantize_x -> q|k|v mx_matmul (+bias) -> attention -> mx_reorder_quantize_x -> o mx_matmul (+bias, +residual)
+            mx.rmsnorm_quantize_x -> mx.matmul_silu_mul (+bias) -> mx_reorder_quantize_x -> down mx_matmul (+bias, +residual)
+        (a decode step may take mx_matmul + mx.silu_mul_quantize_x instead of the middle two: mx_decode_route); fused=False, the
+        reference's call structure (model/qQwenLayer.py): separate q, k, v and gate, up GEMMs, bias / SiLU*up / residual as torch ops.
+        Every activation quantiser is one launch either way -- MXFP4 has no per-tensor scale to find first."""
+        cfg = self.cfg
+        bsz, q_len = tokens.shape
+        h, ke, hd = cfg.hidden_size, cfg.select_num, cfg.hidden_size // cfg.num_heads
+        T = bsz * q_len
+        hcur = F.embedding(tokens, self.embed).reshape(T, h)
+        for L in self.layers:
+            A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln1"], cfg.eps, self.idx_h, ke)
+            if self.fused:
+                qkv = L["qkv"].matmul(A, SFA, 1.0)
+                if q_len == 1 and hd == 128 and self.decode_attention == "stream":
+                    att = self._attn_decode_stream(qkv, L, pos)
+                else:
+                    att = self._attention_torch(L, qkv[:, :h], qkv[:, h:2 * h], qkv[:, 2 * h:], qkv, pos, bsz, q_len)
+                qa, sfa = agemm.mx_reorder_quantize_x(att, self.idx_h, ke)
+                hcur = L["o"].matmul(qa, sfa, 1.0, residual=hcur)
+                A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln2"], cfg.eps, self.idx_h, ke)
+                Gt = L["gateup"]                            # one weight with gate and up rows interleaved (g0, u0, g1, u1, ...)
+                if T <= 64 and self.mx_decode_route == "quantiser":
+                    qa, sfa = mx.silu_mul_quantize_x(Gt.matmul(A, SFA, 1.0), self.idx_i, ke, layout=agemm.GU_PAIRS)
+                else:
+                    act = mx.matmul_silu_mul(A, Gt.W, SFA, Gt.SFW, 1.0, bias=Gt.bias)
+                    qa, sfa = agemm.mx_reorder_quantize_x(act, self.idx_i, ke)
+                hcur = L["down"].matmul(qa, sfa, 1.0, residual=hcur)
+            else:
+                q, k, v = (self._ref_linear_mx(L[n], A, SFA) for n in ("q", "k", "v"))
+                att = self._attention_torch(L, q, k, v, None, pos, bsz, q_len)
+                qa, sfa = agemm.mx_reorder_quantize_x(att, self.idx_h, ke)
+                hcur = hcur + self._ref_linear_mx(L["o"], qa, sfa)
+                A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln2"], cfg.eps, self.idx_h, ke)
+                act = F.silu(self._ref_linear_mx(L["gate"], A, SFA)) * self._ref_linear_mx(L["up"], A, SFA)
+                qa, sfa = agemm.mx_reorder_quantize_x(act, self.idx_i, ke)
+                hcur = hcur + self._ref_linear_mx(L["down"], qa, sfa)
+        return self._logits(hcur, bsz, q_len)
+
+    @staticmethod
+    def _ref_linear_mx(lin, A, SFA):
+        """QLinearLayer.forward's MXFP4 branch the way the reference writes it: GEMM, then `y = y + self.bias` as its own op."""
+        y = agemm.mx_matmul(A, lin.W, SFA, lin.SFW, 1.0)
+        return y if lin.bias is None else y + lin.bias
 
     def _attention_torch(self, L, q, k, v, qkv, pos, bsz, q_len):
         """KV append + attention with torch ops (prefill always; decode when the streaming kernel is switched off)."""
@@ -307,7 +385,7 @@ class DecoderModel:
 
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
-                 attention="current", repacked_only=False):
+                 attention="current", repacked_only=False, quant_type="NVFP4"):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
     weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
@@ -316,7 +394,8 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
     device = torch.device(device)
     with torch.no_grad():
         mem0 = torch.cuda.memory_allocated(device)
-        model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only)
+        model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
+                             quant_type=quant_type)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -369,11 +448,13 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
            "hbm_floor_ms_at_8TBps": round((wb + kv) / 8e12 * 1e3, 4)}
     if repacked_only:
         res.update(repacked_only=True, model_resident_bytes=int(model_bytes))
+    if quant_type != "NVFP4":
+        res["quant_type"] = quant_type
     return res
 
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
-                   fused=True, attention="cache", graph=True, layers=None, repacked_only=False):
+                   fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4"):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -402,7 +483,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         return round(float(t.mean()), 3), round(1.96 * float(t.std(unbiased=False)), 3), max(peaks)
 
     with torch.no_grad():
-        model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only)
+        model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
+                             quant_type=quant_type)
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -441,6 +523,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
            "peak_memory_gb": round(max(p_mem, d_mem, e_mem) / 2 ** 30, 3)}
     if repacked_only:
         res["repacked_only"] = True
+    if quant_type != "NVFP4":
+        res["quant_type"] = quant_type
     return res
 
 
@@ -569,16 +653,24 @@ if __name__ == "__main__":
     if "--tp" in sys.argv:
         _tp_main(sys.argv[1:])
         sys.exit(0)
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv = sys.argv[1:]
+    qt = "NVFP4"
+    if "--quant-type" in argv:        # --quant-type {NVFP4,MXFP4}
+        i = argv.index("--quant-type")
+        qt = argv[i + 1] if i + 1 < len(argv) else ""
+        if qt not in ("NVFP4", "MXFP4"):
+            sys.exit("--quant-type takes NVFP4 or MXFP4")
+        del argv[i:i + 2]
+    args = [a for a in argv if not a.startswith("--")]
     name = args[0] if args else "qwen2.5-7b"
     ro = "--repacked-only" in sys.argv       # one weight copy per linear (the fused model only)
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
-            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro)), flush=True)
+            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
             if ro and not fused:
                 continue
-            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro)))
+            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt)), flush=True)
             torch.cuda.empty_cache()

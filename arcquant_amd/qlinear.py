@@ -4,6 +4,7 @@ Mirrors, with the same names, argument meaning and tuple protocol:
   * ``NVFP4_reorder_quantize_w``  model/qLinearLayer.py:25-28
   * ``NVFP4_reorder_quantize_x``  model/qLlamaLayer.py:73-77 == model/qQwenLayer.py:72-75
   * ``QLinearLayer``              model/qLinearLayer.py:30-78  (forward takes ``(qx, scale_x, scale, bsz, q_len)``)
+  * ``MXFP4_rmsnorm_quantize_x``  RMSNorm + ``MXFP4_reorder_quantize_x`` in one launch (arcquant_amd/mx.py)
   * ``MXFP4_reorder_quantize_{w,x}``  the packed form of the reference's MXFP4 branch (model/quantize.py:219-268 as called by
     the commented-out model/qLinearLayer.py:58 and model/qQwenLayer.py:81-83), on the block-scaled fp4 MFMA
 
@@ -19,7 +20,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import agemm
+from . import agemm, mx
 
 FP8_MAX = 448.0
 FP4_MAX = 6.0
@@ -55,6 +56,13 @@ def MXFP4_reorder_quantize_x(x: torch.Tensor, reorder_index: torch.Tensor, selec
     """(qx [M, Kp/2], scale_x [M, Kp/32] E8M0, scale = 1): the activation reordered, with the quantised residual of its last
     ``select_num`` reordered channels (model/qQwenLayer.py:81-83)."""
     qx, scale_x = agemm.mx_reorder_quantize_x(x.contiguous(), reorder_index, select_num)
+    return qx, scale_x, _unit_scale(x)
+
+
+def MXFP4_rmsnorm_quantize_x(x: torch.Tensor, norm_weight: torch.Tensor, eps: float, reorder_index: torch.Tensor, select_num: int):
+    """(qx, scale_x, scale = 1): RMSNorm fused into ``MXFP4_reorder_quantize_x`` (one launch, ``mx.rmsnorm_quantize_x``); the same tuple
+    protocol, so the result feeds ``QLinearLayer.forward`` directly."""
+    qx, scale_x = mx.rmsnorm_quantize_x(x.contiguous(), norm_weight, eps, reorder_index, select_num)
     return qx, scale_x, _unit_scale(x)
 
 

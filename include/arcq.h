@@ -298,6 +298,29 @@ int arcq_gemm_mxfp4(const uint8_t *A, const uint8_t *B, const uint8_t *SFA, cons
                     int64_t K, float alpha_host, const float *alpha_dev, const void *bias, const void *residual, int out_dtype,
                     void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- MXFP4 decoder-layer operators: the fused quantisers and the SiLU*up GEMM epilogue ------------------------------------------
+ * MXFP4 has no per-tensor scale, so none of them needs an abs-max pass, a `state` buffer or abs-max slots: each is ONE launch.
+ *
+ * arcq_mx_rmsnorm_quantize_x: (QX, SFX) = arcq_mx_quantize_x(xn, ...) of the normalised row arcq_rmsnorm_quantize_x forms,
+ *   xn[c] = bf16(float(X[m, i]) * float(Wn[i]) * rstd), i = reorder_index[c], the product left to right in fp32,
+ *   rstd = (float)(1 / sqrt((double)(sumsq / (float)KQ + eps))), sumsq in that entry's association order: the two quant types
+ *   normalise identically.  2048 <= KQ <= 8192 (the range of the reduction tree), KQ % 64 == 0, KE % 64 == 0, 0 <= KE <= KQ;
+ *   X, Wn, reorder_index and QX 16-byte aligned.  Status as arcq_mx_quantize_x (M == 0 returns ARCQ_OK), before any HIP call. */
+int arcq_mx_rmsnorm_quantize_x(const void *X, const void *Wn, float eps, const int16_t *reorder_index, uint8_t *QX, uint8_t *SFX,
+                               int64_t M, int64_t KQ, int64_t KE, void *stream);
+/* arcq_mx_silu_mul_quantize_x: GU = bf16 [M, 2*KQ] in layout ARCQ_GU_HALVES or ARCQ_GU_PAIRS; (QX, SFX) = arcq_mx_quantize_x of the
+ *   bf16 tensor torch computes as silu(gate) * up (two roundings), which is never materialised.  KQ as arcq_mx_quantize_x; GU,
+ *   reorder_index and QX 16-byte aligned; ARCQ_ERR_SHAPE for a layout outside {0, 1}. */
+int arcq_mx_silu_mul_quantize_x(const void *GU, const int16_t *reorder_index, uint8_t *QX, uint8_t *SFX, int64_t M, int64_t KQ,
+                                int64_t KE, int layout, void *stream);
+/* arcq_gemm_mxfp4_silu_mul: arcq_gemm_mxfp4 for a weight whose ROWS INTERLEAVE gate and up (g0, u0, g1, u1, ...) with the MLP's
+ *   act_fn(gate) * up in its epilogue: ACT = bf16 [M, N/2], ACT[m, j] = silu(y[m, 2j]) * y[m, 2j+1] with torch's roundings, y being
+ *   the bf16 value arcq_gemm_mxfp4 would store (bf16(alpha * acc), then + bias -> bf16; same kernels, same accumulation order); y
+ *   is never written.  K % 128 == 0, N % 16 == 0; A, B, ACT 16-byte, SFA, SFB 4-byte, bias (optional bf16 [N], interleaved as the
+ *   rows) 2-byte aligned.  Status as arcq_gemm_mxfp4; M == 0 or N == 0 returns ARCQ_OK; all before any HIP call. */
+int arcq_gemm_mxfp4_silu_mul(const uint8_t *A, const uint8_t *B, const uint8_t *SFA, const uint8_t *SFB, void *ACT, int64_t M,
+                             int64_t N, int64_t K, float alpha_host, const float *alpha_dev, const void *bias, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
