@@ -63,6 +63,8 @@ int mx_silu_mul_quantize_x(const void* GU, const int16_t* idx, uint8_t* QX, uint
                            hipStream_t stream);
 int gemm_mx_silu_mul(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* ACT, int64_t M, int64_t N, int64_t Kp,
                      float alpha_host, const float* alpha_dev, const void* bias, hipStream_t stream);
+int gemm_mx_silu_mul_quantize(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, uint8_t* QACT, uint8_t* SFACT, int64_t M,
+                              int64_t N, int64_t Kp, float alpha_host, const float* alpha_dev, const void* bias, int64_t KE, hipStream_t stream);
 
 // gemm_skinny.hip / gemm_tile.hip
 struct GemmArgs {

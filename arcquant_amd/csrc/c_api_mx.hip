@@ -52,4 +52,18 @@ int arcq_gemm_mxfp4_silu_mul(const uint8_t* A, const uint8_t* B, const uint8_t* 
   return gemm_mx_silu_mul(A, B, SFA, SFB, ACT, M, N, K, alpha_host, alpha_dev, bias, (hipStream_t)stream);
 }
 
+int arcq_gemm_mxfp4_silu_mul_quantize(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, uint8_t* QACT, uint8_t* SFACT,
+                                      int64_t M, int64_t N, int64_t K, float alpha_host, const float* alpha_dev, const void* bias, int64_t KE,
+                                      void* stream) {
+  GemmRule r{"arcq_gemm_mxfp4_silu_mul_quantize"};
+  r.k_mult = 128; r.n_mult = 128; r.max_m = (int64_t)65535 * 128; r.epi_align = 2; r.d = "QACT";
+  // the quantiser's own shape rules on KQ2 = N / 2 (arcq_mx_quantize_x), reported with the divisibility rules
+  if (N >= 0 && (N % 128 == 0) && (KE < 0 || (KE % 64) || KE > N / 2 || N / 2 > 32767))
+    return fail(ARCQ_ERR_SHAPE, "%s: need KE %% 64 == 0 and 0 <= KE <= N/2 <= 32767 (N=%lld KE=%lld)", r.who, (long long)N, (long long)KE);
+  // a NULL SFACT is reported where gemm_checks reports a NULL output; the scale bytes need no alignment
+  const int rc = gemm_checks(r, A, B, SFA, SFB, SFACT ? QACT : nullptr, nullptr, M, N, K, bias, nullptr, ARCQ_OUT_BF16);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_silu_mul_quantize(A, B, SFA, SFB, QACT, SFACT, M, N, K, alpha_host, alpha_dev, bias, KE, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -24,12 +24,21 @@
 // (g0, u0, g1, u1, ...), D = bf16 [M, N/2] receives silu(y_gate) * y_up with torch's roundings, y being the bf16 value the plain epilogue
 // would store (never written).  A lane holds ONE output column, so gate and up of a pair sit in neighbouring lanes of a DPP quad (N % 16
 // == 0: a quad of lanes is inside or outside n < N as a whole); see mx_silu_pair.
+//
+// kEpiSiluMulQuant (arcq_gemm_mxfp4_silu_mul_quantize): the same activations are not stored but quantised where they are, to the
+// MXFP4-ARC operand of the next GEMM (QACT, SFACT = arcq_mx_quantize_x of ACT with the identity reorder_index).  A block's E8M0 scale
+// needs the 32 values of the block and nothing else, and 32 adjacent activations are 64 adjacent y-columns: a 128-column tile holds two
+// whole blocks per row (N % 128 == 0: no ragged column tile).  The activations of a tile go through the LDS the K loop has finished
+// with, one thread then quantises one (row, block) with the quantisers' own mx_store_x_block -- residual blocks of the outlier tail
+// and the row's padding blocks included.  M <= kMxSmallM: mx_slice_quant_kernel, mx_small_kernel's K split and sum order over a
+// 64-column slice (one block per row) instead of a 16-column one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "arcq_device.hpp"
 #include "arcq_internal.hpp"
 #include "gemm_common.hpp"
+#include "quantize_mx_device.hpp"
 
 namespace arcq {
 
@@ -48,7 +57,11 @@ struct MxArgs {
   const uint16_t* bias;
   const uint16_t* residual;
   int out_dtype;
+  uint8_t* QACT;      // kEpiSiluMulQuant: codes [M, Kp2/2] and scale bytes [M, Kp2/32] of the quantised activation, KQ2 = N/2, K2 = KQ2 + KE
+  uint8_t* SFACT;
+  int KE;
 };
+constexpr int kEpiSiluMulQuant = 2;
 
 __device__ __forceinline__ i32x8 frag(uint4 u) {
   i32x8 f = {(int)u.x, (int)u.y, (int)u.z, (int)u.w, 0, 0, 0, 0};     // fp4: the instruction reads the first four dwords only
@@ -95,10 +108,41 @@ __device__ __forceinline__ uint32_t mx_silu_pair(uint32_t y0, uint32_t y1, bool 
   return act | (dpp_quad<kQuadSwap2>(act) << 16);
 }
 
+// One (row, block) of the quantised activation: the block's 32 bf16 activations at `src` (LDS, 16-byte aligned) -> codes and scale byte at
+// block b of row m, the residual block when b is in the outlier tail, and, from the owner of the row's last block, the padding blocks.
+__device__ __forceinline__ void mx_quantize_act_block(const MxArgs& p, const uint8_t* src, int m, int b) {
+  const int KQ2 = p.N >> 1, K2 = KQ2 + p.KE, Kp2 = (K2 + 127) & ~127;
+  const int B = KQ2 >> 5, P = (KQ2 - p.KE) >> 5, Bp = Kp2 >> 5;
+  float v[32];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const uint4 u = *reinterpret_cast<const uint4*>(src + c * 16);
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      v[8 * c + 2 * d] = bf16_bits_to_f32(w[d] & 0xffffu);
+      v[8 * c + 2 * d + 1] = bf16_bits_to_f32(w[d] >> 16);
+    }
+  }
+  uint8_t* qrow = p.QACT + (size_t)m * (size_t)(Kp2 >> 1);
+  uint8_t* srow = p.SFACT + (size_t)m * (size_t)Bp;
+  mx_store_x_block(qrow, srow, b, B + (b - P), b >= P, v);
+  if (b == B - 1)
+    for (int pb = K2 >> 5; pb < Bp; ++pb) {         // [K2, Kp2): code 0, scale 2^0 (K2 % 64 == 0: none or two blocks)
+      *reinterpret_cast<uint4*>(qrow + (size_t)pb * 16) = make_uint4(0, 0, 0, 0);
+      srow[pb] = 127;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- tiled
 constexpr int kMxTile = 128;
 constexpr int kMxOpBytes = kMxTile * 64;                     // one operand tile of one K step: 128 rows x 64 bytes
 constexpr int kMxBufBytes = 2 * kMxOpBytes + 2 * kMxTile * 4;   // A, B, then one scale dword per row of A and of B
+// kEpiSiluMulQuant: the tile's 128 x 64 bf16 activations in the staging buffers, rows of 128 bytes padded to 144 (unpadded, the 16
+// lanes of a ds_read_b128 group -- 8 rows x 2 blocks -- would all start on banks 0 and 16; 36 r + 16 b mod 64 spreads them to 2-way at
+// worst, on four reads per thread)
+constexpr int kMxActRowBytes = 64 * 2 + 16;
+static_assert(kMxTile * kMxActRowBytes <= 2 * kMxBufBytes, "the activation image reuses the staging buffers");
 
 // LDS byte offset of 16-byte chunk c (0..3) of staged row r.  The chunk index is XORed with (r >> 2) & 3: the 16 lanes of each
 // ds_read_b128 lane group read 16 different rows at one logical chunk; rows equal mod 4 would share banks in a plain 64-byte
@@ -195,6 +239,27 @@ __global__ __launch_bounds__(256) void mx_tile_kernel(MxArgs p) {
   }
 
   const float alpha = p.alpha_host * (p.alpha_dev ? *p.alpha_dev : 1.0f);
+  if constexpr (kEpi == kEpiSiluMulQuant) {
+    // every wave is past its last read of the staging buffers (the barrier that ends the K loop); N % 128 == 0: no column is outside
+    const bool odd = lane & 1;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int nl = wn * 64 + j * 32 + r32;                 // y-column within the tile
+        const float bias = p.bias ? bf16_bits_to_f32(p.bias[n0 + nl]) : 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+          const uint32_t pk = mx_silu_pair(mx_y_bits(alpha, acc[i][j][r], p.bias, bias), mx_y_bits(alpha, acc[i][j][r + 1], p.bias, bias), odd);
+          const int ml = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h + (odd ? 1 : 0);
+          if (!(lane & 2)) *reinterpret_cast<uint32_t*>(lds + ml * kMxActRowBytes + (nl >> 1) * 2) = pk;   // rows >= M hold clamped rows' values
+        }
+      }
+    __syncthreads();
+    const int ml = tid >> 1, bl = tid & 1;                     // thread -> (row, block): a lane pair stores 32 adjacent code bytes
+    if (m0 + ml < p.M) mx_quantize_act_block(p, lds + ml * kMxActRowBytes + bl * 64, m0 + ml, (n0 >> 6) + bl);
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -289,11 +354,89 @@ __global__ __launch_bounds__(64 * kMxSmallWaves) void mx_small_kernel(MxArgs p) 
   }
 }
 
+// kEpiSiluMulQuant for M <= kMxSmallM.  mx_small_kernel's 16 y-columns are 8 activations, a quarter of a block; this kernel gives a
+// workgroup 64 y-columns = one block per row: one A fragment against four B fragments per K step.  Every (m, n) sum is mx_small_kernel's:
+// wave w takes the steps s = w (mod 8) in ascending order, the eight partial sums are added w = 0 .. 7.  Waves 0 .. 3 each finish one
+// 16-column fragment and put its activations into LDS (rows of 64 bytes padded to 80: 20 r mod 64 is a different multiple of 4 for each
+// of the 16 rows); 16 threads then quantise one row's block each.
+constexpr int kMxSliceCols = 64;
+constexpr int kMxSliceFrags = kMxSliceCols / 16;
+constexpr int kMxSliceUnroll = 2;
+constexpr int kMxSliceActRowBytes = 32 * 2 + 16;
+
+__global__ __launch_bounds__(64 * kMxSmallWaves) void mx_slice_quant_kernel(MxArgs p) {
+  __shared__ __attribute__((aligned(16))) float part[kMxSmallWaves][kMxSliceFrags][64][4];
+  __shared__ __attribute__((aligned(16))) uint8_t act[16 * kMxSliceActRowBytes];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n0 = blockIdx.x * kMxSliceCols, m0 = blockIdx.y * 16;
+  const size_t rowb = (size_t)(p.Kp >> 1), rows = (size_t)(p.Kp >> 5);
+  const int steps = p.Kp >> 7;
+  const int r16 = lane & 15, q = lane >> 4;
+  const uint8_t* gA = p.A + (size_t)min(m0 + r16, p.M - 1) * rowb + q * 16;
+  const uint8_t* gB = p.B + (size_t)(n0 + r16) * rowb + q * 16;                     // N % 128 == 0: always in range
+  const uint8_t* gSA = p.SFA + (size_t)min(m0 + r16, p.M - 1) * rows;
+  const uint8_t* gSB = p.SFB + (size_t)(n0 + r16) * rows;
+  const int sh = 8 * q;
+  f32x4 acc[kMxSliceFrags];
+#pragma unroll
+  for (int j = 0; j < kMxSliceFrags; ++j) acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  for (int s0 = wave; s0 < steps; s0 += kMxSmallWaves * kMxSliceUnroll) {
+    i32x4 a[kMxSliceUnroll], b[kMxSliceUnroll][kMxSliceFrags];
+    uint32_t sa[kMxSliceUnroll], sb[kMxSliceUnroll][kMxSliceFrags];
+#pragma unroll
+    for (int u = 0; u < kMxSliceUnroll; ++u) {
+      const int s = min(s0 + u * kMxSmallWaves, steps - 1);      // clamped loads; the MFMAs of a step past the end are skipped
+#pragma unroll
+      for (int j = 0; j < kMxSliceFrags; ++j) {
+        b[u][j] = ARCQ_WLOAD(reinterpret_cast<const i32x4*>(gB + (size_t)j * 16 * rowb + (size_t)s * 64));
+        sb[u][j] = ARCQ_WLOAD(reinterpret_cast<const uint32_t*>(gSB + (size_t)j * 16 * rows + (size_t)s * 4));
+      }
+      a[u] = *reinterpret_cast<const i32x4*>(gA + (size_t)s * 64);
+      sa[u] = *reinterpret_cast<const uint32_t*>(gSA + (size_t)s * 4);
+    }
+#pragma unroll
+    for (int u = 0; u < kMxSliceUnroll; ++u)
+      if (s0 + u * kMxSmallWaves < steps) {
+#pragma unroll
+        for (int j = 0; j < kMxSliceFrags; ++j)
+          acc[j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(frag(a[u]), frag(b[u][j]), acc[j], 4, 4, 0, (int)(sa[u] >> sh), 0,
+                                                                    (int)(sb[u][j] >> sh));
+      }
+  }
+#pragma unroll
+  for (int j = 0; j < kMxSliceFrags; ++j) *reinterpret_cast<f32x4*>(part[wave][j][lane]) = acc[j];
+  __syncthreads();
+  if (wave < kMxSliceFrags) {                                  // wave j: fragment j, y-columns [16 j, 16 j + 16) of the slice
+    const float alpha = p.alpha_host * (p.alpha_dev ? *p.alpha_dev : 1.0f);
+    f32x4 t = *reinterpret_cast<const f32x4*>(part[0][wave][lane]);
+#pragma unroll
+    for (int w = 1; w < kMxSmallWaves; ++w) {
+      const f32x4 o = *reinterpret_cast<const f32x4*>(part[w][wave][lane]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) t[r] += o[r];
+    }
+    const bool odd = lane & 1;
+    const int nl = wave * 16 + r16;
+    const float bias = p.bias ? bf16_bits_to_f32(p.bias[n0 + nl]) : 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; r += 2) {
+      const uint32_t pk = mx_silu_pair(mx_y_bits(alpha, t[r], p.bias, bias), mx_y_bits(alpha, t[r + 1], p.bias, bias), odd);
+      const int ml = 4 * q + r + (odd ? 1 : 0);
+      if (!(lane & 2)) *reinterpret_cast<uint32_t*>(act + ml * kMxSliceActRowBytes + (nl >> 1) * 2) = pk;
+    }
+  }
+  __syncthreads();
+  if (tid < 16 && m0 + tid < p.M) mx_quantize_act_block(p, act + tid * kMxSliceActRowBytes, m0 + tid, (int)blockIdx.x);
+}
+
 template <int kEpi>
 static int mx_launch_gemm(const MxArgs& p, const char* who, hipStream_t stream) {
-  if (p.M <= kMxSmallM)
-    hipLaunchKernelGGL(mx_small_kernel<kEpi>, dim3((unsigned)(p.N / 16), (unsigned)((p.M + 15) / 16)), dim3(64 * kMxSmallWaves), 0, stream, p);
-  else
+  if (p.M <= kMxSmallM) {
+    if constexpr (kEpi == kEpiSiluMulQuant)
+      hipLaunchKernelGGL(mx_slice_quant_kernel, dim3((unsigned)(p.N / kMxSliceCols), (unsigned)((p.M + 15) / 16)), dim3(64 * kMxSmallWaves), 0, stream, p);
+    else
+      hipLaunchKernelGGL(mx_small_kernel<kEpi>, dim3((unsigned)(p.N / 16), (unsigned)((p.M + 15) / 16)), dim3(64 * kMxSmallWaves), 0, stream, p);
+  } else
     hipLaunchKernelGGL(mx_tile_kernel<kEpi>, dim3((unsigned)((p.N + kMxTile - 1) / kMxTile), (unsigned)((p.M + kMxTile - 1) / kMxTile)), dim3(256), 0,
                        stream, p);
   hipError_t e = hipGetLastError();
@@ -308,6 +451,7 @@ int gemm_mx(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_
   p.M = (int)M; p.N = (int)N; p.Kp = (int)Kp;
   p.alpha_host = alpha_host; p.alpha_dev = alpha_dev;
   p.bias = (const uint16_t*)bias; p.residual = (const uint16_t*)residual; p.out_dtype = out_dtype;
+  p.QACT = nullptr; p.SFACT = nullptr; p.KE = 0;
   return mx_launch_gemm<kEpiPlain>(p, "arcq_gemm_mxfp4", stream);
 }
 
@@ -319,7 +463,20 @@ int gemm_mx_silu_mul(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, con
   p.M = (int)M; p.N = (int)N; p.Kp = (int)Kp;
   p.alpha_host = alpha_host; p.alpha_dev = alpha_dev;
   p.bias = (const uint16_t*)bias; p.residual = nullptr; p.out_dtype = ARCQ_OUT_BF16;
+  p.QACT = nullptr; p.SFACT = nullptr; p.KE = 0;
   return mx_launch_gemm<kEpiSiluMul>(p, "arcq_gemm_mxfp4_silu_mul", stream);
+}
+
+// (QACT, SFACT) = mx_quantize_x(ACT of gemm_mx_silu_mul, identity, KQ2 = N/2, KE); ACT is never written.  N % 128 == 0.
+int gemm_mx_silu_mul_quantize(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, uint8_t* QACT, uint8_t* SFACT, int64_t M,
+                              int64_t N, int64_t Kp, float alpha_host, const float* alpha_dev, const void* bias, int64_t KE, hipStream_t stream) {
+  MxArgs p;
+  p.A = A; p.B = B; p.SFA = SFA; p.SFB = SFB; p.D = nullptr;
+  p.M = (int)M; p.N = (int)N; p.Kp = (int)Kp;
+  p.alpha_host = alpha_host; p.alpha_dev = alpha_dev;
+  p.bias = (const uint16_t*)bias; p.residual = nullptr; p.out_dtype = ARCQ_OUT_BF16;
+  p.QACT = QACT; p.SFACT = SFACT; p.KE = (int)KE;
+  return mx_launch_gemm<kEpiSiluMulQuant>(p, "arcq_gemm_mxfp4_silu_mul_quantize", stream);
 }
 
 }  // namespace arcq

@@ -115,18 +115,24 @@ class DecoderModel:
     mx_decode_route = "epilogue"
 
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
-                 repacked_only: bool = False, quant_type: str = "NVFP4"):
+                 repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
-        the repack and every GEMM the repacked kernels do not serve runs through agemm.matmul_rw / matmul_rw_silu_mul."""
+        the repack and every GEMM the repacked kernels do not serve runs through agemm.matmul_rw / matmul_rw_silu_mul.
+        mx_quantised_epilogue (quant_type="MXFP4", fused=True only): the gate|up GEMM writes the down projection's quantised input itself
+        (mx.matmul_silu_mul_quantize) instead of mx.matmul_silu_mul + mx_reorder_quantize_x, prefill and decode alike; same logits."""
         if repacked_only and not fused:
             raise ValueError("DecoderModel: repacked_only=True needs fused=True (the unfused model is the reference's call structure)")
         if quant_type not in ("NVFP4", "MXFP4"):
             raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4 and MXFP4 are)")
         if quant_type == "MXFP4" and repacked_only:
             raise ValueError("DecoderModel: repacked_only applies to the NVFP4 weight layout only, not to quant_type='MXFP4'")
+        if mx_quantised_epilogue and (quant_type != "MXFP4" or not fused):
+            raise ValueError("DecoderModel: mx_quantised_epilogue needs quant_type='MXFP4' and fused=True (NVFP4's per-tensor scale needs the "
+                             "whole activation first; the unfused model is the reference's call structure)")
         self.quant_type = quant_type
+        self.mx_quantised_epilogue = mx_quantised_epilogue
         self.cfg, self.device, self.batch, self.max_len, self.fused = cfg, device, batch, max_len, fused
         self.repacked_only = repacked_only
         self.attention = attention
@@ -294,7 +300,8 @@ class DecoderModel:
         """forward() for quant_type="MXFP4".  Per layer, fused=True:
             mx.rmsnorm_quantize_x -> q|k|v mx_matmul (+bias) -> attention -> mx_reorder_quantize_x -> o mx_matmul (+bias, +residual)
             mx.rmsnorm_quantize_x -> mx.matmul_silu_mul (+bias) -> mx_reorder_quantize_x -> down mx_matmul (+bias, +residual)
-        (a decode step may take mx_matmul + mx.silu_mul_quantize_x instead of the middle two: mx_decode_route); fused=False, the
+        (a decode step may take mx_matmul + mx.silu_mul_quantize_x instead of the middle two: mx_decode_route; with
+        mx_quantised_epilogue the middle two are mx.matmul_silu_mul_quantize at every T -- idx_i is the identity); fused=False, the
         reference's call structure (model/qQwenLayer.py): separate q, k, v and gate, up GEMMs, bias / SiLU*up / residual as torch ops.
         Every activation quantiser is one launch either way -- MXFP4 has no per-tensor scale to find first."""
         cfg = self.cfg
@@ -314,7 +321,9 @@ class DecoderModel:
                 hcur = L["o"].matmul(qa, sfa, 1.0, residual=hcur)
                 A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln2"], cfg.eps, self.idx_h, ke)
                 Gt = L["gateup"]                            # one weight with gate and up rows interleaved (g0, u0, g1, u1, ...)
-                if T <= 64 and self.mx_decode_route == "quantiser":
+                if self.mx_quantised_epilogue:
+                    qa, sfa = mx.matmul_silu_mul_quantize(A, Gt.W, SFA, Gt.SFW, 1.0, ke, bias=Gt.bias)
+                elif T <= 64 and self.mx_decode_route == "quantiser":
                     qa, sfa = mx.silu_mul_quantize_x(Gt.matmul(A, SFA, 1.0), self.idx_i, ke, layout=agemm.GU_PAIRS)
                 else:
                     act = mx.matmul_silu_mul(A, Gt.W, SFA, Gt.SFW, 1.0, bias=Gt.bias)
@@ -385,7 +394,7 @@ class DecoderModel:
 
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
-                 attention="current", repacked_only=False, quant_type="NVFP4"):
+                 attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
     weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
@@ -395,7 +404,7 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
     with torch.no_grad():
         mem0 = torch.cuda.memory_allocated(device)
         model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
-                             quant_type=quant_type)
+                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -450,11 +459,13 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         res.update(repacked_only=True, model_resident_bytes=int(model_bytes))
     if quant_type != "NVFP4":
         res["quant_type"] = quant_type
+    if mx_quantised_epilogue:
+        res["mx_quantised_epilogue"] = True
     return res
 
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
-                   fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4"):
+                   fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -484,7 +495,7 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
 
     with torch.no_grad():
         model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
-                             quant_type=quant_type)
+                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue)
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -525,6 +536,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         res["repacked_only"] = True
     if quant_type != "NVFP4":
         res["quant_type"] = quant_type
+    if mx_quantised_epilogue:
+        res["mx_quantised_epilogue"] = True
     return res
 
 
@@ -664,13 +677,16 @@ if __name__ == "__main__":
     args = [a for a in argv if not a.startswith("--")]
     name = args[0] if args else "qwen2.5-7b"
     ro = "--repacked-only" in sys.argv       # one weight copy per linear (the fused model only)
+    qe = "--mx-quantised-epilogue" in sys.argv   # MXFP4, the fused model only: the gate|up GEMM quantises the down projection's input
+    if qe and qt != "MXFP4":
+        sys.exit("--mx-quantised-epilogue needs --quant-type MXFP4")
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
-            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt)), flush=True)
+            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
-            if ro and not fused:
+            if (ro or qe) and not fused:
                 continue
-            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt)), flush=True)
+            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe)), flush=True)
             torch.cuda.empty_cache()

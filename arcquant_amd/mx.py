@@ -1,7 +1,8 @@
 """MXFP4 decoder-layer operators (include/arcq.h "MXFP4 decoder-layer operators"): the fused RMSNorm and SiLU*up
 quantisers and the gate|up GEMM with SiLU*up in its epilogue -- what ``agemm.rmsnorm_quantize_x``, ``silu_mul_quantize_x_dynamic`` and
 ``matmul_silu_mul`` are to NVFP4.  MXFP4 has no per-tensor scale, so each operator is ONE launch and returns no scale and no abs-max
-slots.
+slots.  ``matmul_silu_mul_quantize`` ends the family: the gate|up GEMM that writes the down projection's quantised input itself, which
+NVFP4's per-tensor scale rules out (``gate_up_rows`` lays the weight out for it).
 
 The plain MXFP4 quantisers and GEMM stay in ``agemm`` (``mx_reorder_quantize_{x,w}``, ``mx_matmul``).  This module is a ctypes mirror
 only: the extension module ``agemm.so`` does not bind these operators.  Validation follows the mirror's order (``agemm._need`` ...):
@@ -92,3 +93,65 @@ def matmul_silu_mul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: to
                                                  alpha_p, bias_p, _stream(A))
     _lib.check(st, "mx.matmul_silu_mul")
     return out
+
+
+def matmul_silu_mul_quantize(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: torch.Tensor, scale, KE: int, *, scale_host: float = 1.0,
+                             bias=None):
+    """The gate|up GEMM that writes the down projection's quantised input: operands as ``matmul_silu_mul`` -> (QX u8 [M, Kp2/2], SFX u8
+    E8M0 [M, Kp2/32]) with KQ2 = N/2 and Kp2 = mx_k_padded(KQ2 + KE), byte for byte
+    ``agemm.mx_reorder_quantize_x(matmul_silu_mul(A, B, SFA, SFB, scale, ...), arange(KQ2), KE)``; the activation is never written.
+    There is no reorder_index: activation j is channel j of the result, so the channel order is the order of ``B``'s row pairs
+    (``gate_up_rows``).  KQ2 % 64 == 0 (N % 128 == 0), KE % 64 == 0, 0 <= KE <= KQ2 <= 32767."""
+    for t, name in ((A, "A"), (B, "B"), (SFA, "SFA"), (SFB, "SFB")):
+        _need(t, torch.uint8, name, 2)
+    M, N, K = A.shape[0], B.shape[0], A.shape[1] * 2
+    KE = int(KE)
+    if B.shape[1] * 2 != K:
+        raise RuntimeError(f"mx.matmul_silu_mul_quantize: A has K={K}, B has K={B.shape[1] * 2}")
+    if K % 128:
+        raise RuntimeError(f"mx.matmul_silu_mul_quantize: K={K} is not a padded MXFP4 K (a multiple of 128)")
+    if N % 128:
+        raise RuntimeError(f"mx.matmul_silu_mul_quantize: N={N} must be a multiple of 128 (N/2 activations in whole pairs of 32-blocks)")
+    if KE % 64 or KE < 0 or KE > N // 2 or N // 2 > 32767:
+        raise RuntimeError(f"Value error in mx.matmul_silu_mul_quantize: KQ={N // 2}, KE={KE} is not valid")
+    if tuple(SFA.shape) != (M, K // 32) or tuple(SFB.shape) != (N, K // 32):
+        raise RuntimeError("mx.matmul_silu_mul_quantize: SFA / SFB must be [rows, K/32]")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    bias_p = _opt(bias, torch.bfloat16, "bias", (N,))
+    _same_device("mx.matmul_silu_mul_quantize", A, B, SFA, SFB, alpha_dev, bias)
+    QX, SFX = _outputs(M, N // 2, KE, A)
+    with _on(A.device):
+        st = _lib.lib().arcq_gemm_mxfp4_silu_mul_quantize(A.data_ptr(), B.data_ptr(), SFA.data_ptr(), SFB.data_ptr(), QX.data_ptr(), SFX.data_ptr(),
+                                                          M, N, K, alpha_host, alpha_p, bias_p, KE, _stream(A))
+    _lib.check(st, "mx.matmul_silu_mul_quantize")
+    return QX, SFX
+
+
+def gate_up_rows(gate_w: torch.Tensor, up_w: torch.Tensor, reorder_index=None, gate_b=None, up_b=None):
+    """The gate|up weight of ``matmul_silu_mul`` / ``matmul_silu_mul_quantize`` from the two projections' [KQ2, in_features] weights: rows
+    g0, u0, g1, u1, ... where pair j is channel ``reorder_index[j]`` (None: channel j).  With the consumer's reorder_index the GEMM's
+    activations come out in the order that quantiser would gather them into, which is what ``matmul_silu_mul_quantize`` (identity
+    gather) needs; the weight is quantised per row, so permuting rows before quantising is exact.  Returns the [2*KQ2, in_features]
+    weight, or (weight, bias [2*KQ2]) when ``gate_b`` and ``up_b`` are given."""
+    if gate_w.dim() != 2 or gate_w.shape != up_w.shape or gate_w.dtype != up_w.dtype:
+        raise RuntimeError(f"mx.gate_up_rows: gate_w and up_w must be 2-D of one shape and dtype, got {tuple(gate_w.shape)} / {tuple(up_w.shape)}")
+    if (gate_b is None) != (up_b is None):
+        raise RuntimeError("mx.gate_up_rows: gate_b and up_b come together or not at all")
+    KQ2 = gate_w.shape[0]
+    order = None
+    if reorder_index is not None:
+        order = reorder_index.reshape(-1).long()
+        if order.numel() != KQ2 or not torch.equal(torch.sort(order).values, torch.arange(KQ2, device=order.device)):
+            raise RuntimeError(f"mx.gate_up_rows: reorder_index must be a permutation of 0 .. {KQ2 - 1}")
+
+    def pairs(g, u):
+        if order is not None:
+            g, u = g[order.to(g.device)], u[order.to(u.device)]
+        return torch.stack((g, u), dim=1).reshape(2 * KQ2, *g.shape[1:]).contiguous()
+
+    w = pairs(gate_w, up_w)
+    if gate_b is None:
+        return w
+    if gate_b.shape != (KQ2,) or up_b.shape != (KQ2,):
+        raise RuntimeError(f"mx.gate_up_rows: gate_b and up_b must have shape ({KQ2},)")
+    return w, pairs(gate_b, up_b)

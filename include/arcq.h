@@ -320,6 +320,21 @@ int arcq_mx_silu_mul_quantize_x(const void *GU, const int16_t *reorder_index, ui
  *   rows) 2-byte aligned.  Status as arcq_gemm_mxfp4; M == 0 or N == 0 returns ARCQ_OK; all before any HIP call. */
 int arcq_gemm_mxfp4_silu_mul(const uint8_t *A, const uint8_t *B, const uint8_t *SFA, const uint8_t *SFB, void *ACT, int64_t M,
                              int64_t N, int64_t K, float alpha_host, const float *alpha_dev, const void *bias, void *stream);
+/* arcq_gemm_mxfp4_silu_mul_quantize: the gate|up GEMM that writes the down projection's quantised input.  A, B, SFA, SFB, K, alpha and
+ *   bias exactly as arcq_gemm_mxfp4_silu_mul; with KQ2 = N / 2 (the activation width), K2 = KQ2 + KE and Kp2 = arcq_mx_k_padded(K2),
+ *   QACT u8 [M, Kp2/2] and SFACT u8 [M, Kp2/32] receive, byte for byte, what arcq_mx_quantize_x(ACT, identity, QACT, SFACT, M, KQ2, KE)
+ *   writes for the ACT of arcq_gemm_mxfp4_silu_mul and identity = 0 .. KQ2-1: the residual blocks of the last KE channels, the padding
+ *   blocks and the sign of zero included (same kernels' accumulation order, same roundings).  ACT is never written: a block of 32
+ *   activations is 64 adjacent output columns, which one workgroup holds, and an MXFP4 block needs nothing beyond its own 32 values.
+ *   CHANNEL ORDER IS THE CALLER'S: there is no reorder_index here, activation j is channel j of the quantised operand.  A consumer
+ *   whose quantiser would gather with a non-identity reorder_index stores the gate|up weight rows (and the bias) in that order at
+ *   deployment time -- pair j = (gate row, up row) of channel reorder_index[j] -- which is exact, the weight being quantised per row.
+ *   K % 128 == 0; KQ2 % 64 == 0 (so N % 128 == 0), KE % 64 == 0, 0 <= KE <= KQ2 <= 32767; A, B, QACT 16-byte, SFA, SFB 4-byte, bias
+ *   2-byte aligned.  Status as arcq_gemm_mxfp4_silu_mul (ARCQ_ERR_SHAPE / ARCQ_ERR_NULL); M == 0 returns ARCQ_OK; all before any HIP
+ *   call. */
+int arcq_gemm_mxfp4_silu_mul_quantize(const uint8_t *A, const uint8_t *B, const uint8_t *SFA, const uint8_t *SFB, uint8_t *QACT,
+                                      uint8_t *SFACT, int64_t M, int64_t N, int64_t K, float alpha_host, const float *alpha_dev,
+                                      const void *bias, int64_t KE, void *stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 before it existed, and the NVFP4 counterparts, in one process; prints ONE JSON line (the evidence behind
 profiles/mxfp4_fused_ops.json).
 
-    python tools/mx_fused_bench.py [--rounds R] [--out FILE]
+    python tools/mx_fused_bench.py [--rounds R] [--table {all,fused,quant_epilogue}] [--out FILE]
 
 Method (tools/mx_bench.py's): every chain is replayed from a HIP graph over inputs / weight copies rotated through > 320 MB (HBM-cold
 weights at decode sizes), warmed for ~40 ms and timed for >= 10 ms.  The chains of one shape ALTERNATE for `--rounds` rounds in the same
@@ -13,6 +13,9 @@ between rounds -- ratios closer to 1 than that are not a difference.  Run the co
   rmsnorm   torch's RMSNorm ops (Qwen2RMSNorm) + mx_reorder_quantize_x      against  mx.rmsnorm_quantize_x
   gate|up   mx_matmul + F.silu * up + mx_reorder_quantize_x                  against  mx.matmul_silu_mul + mx_reorder_quantize_x  (epilogue)
                                                                              and      mx_matmul + mx.silu_mul_quantize_x(GU_PAIRS) (quantiser)
+
+Second table (--table quant_epilogue, the evidence behind profiles/mxfp4_quant_epilogue.json), the same protocol at M = 4, 16, 64, 4096:
+  gate|up   mx.matmul_silu_mul + mx_reorder_quantize_x (the chain above)     against  mx.matmul_silu_mul_quantize  (one launch)
 """
 from __future__ import annotations
 
@@ -116,20 +119,52 @@ def gate_up(M, dev, rounds, KQ=3584, inter=18944):
     return rec
 
 
+def quant_epilogue(M, dev, rounds, KQ=3584, inter=18944):
+    """The two launches from packed operands to the down projection's (QX, SFX) against the one that replaces them."""
+    N = 2 * inter
+    x = bench.outlier_activations(M, KQ, dev)
+    w = (torch.randn(N, KQ, device=dev, generator=torch.Generator(device=dev).manual_seed(1)) * 0.05).to(torch.bfloat16)   # rows: g0, u0, g1, u1, ...
+    idx = torch.arange(KQ, dtype=torch.int16, device=dev)
+    idx_i = torch.arange(inter, dtype=torch.int16, device=dev)
+    qx, sx = agemm.mx_reorder_quantize_x(x, idx, KE)
+    qw, sw = agemm.mx_reorder_quantize_w(w, idx, KE)
+    del w
+    Kp = qx.shape[1] * 2
+    rot = max(2, int(320e6 // (N * Kp * 17 / 32)) + 1)
+    ws = [(qw.clone(), sw.clone()) for _ in range(rot)]
+    a, b = agemm.mx_reorder_quantize_x(mx.matmul_silu_mul(qx, ws[0][0], sx, ws[0][1], 1.0), idx_i, KE), mx.matmul_silu_mul_quantize(qx, ws[0][0], sx, ws[0][1], 1.0, KE)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), "the two forms disagree: nothing to time"
+    chains = {
+        "epilogue_gemm_then_quantize": [(lambda i=i: agemm.mx_reorder_quantize_x(mx.matmul_silu_mul(qx, ws[i][0], sx, ws[i][1], 1.0), idx_i, KE))
+                                        for i in range(rot)],
+        "quantising_epilogue_gemm": [(lambda i=i: mx.matmul_silu_mul_quantize(qx, ws[i][0], sx, ws[i][1], 1.0, KE)) for i in range(rot)],
+    }
+    t, spread = alternate(chains, rounds)
+    rec = {"M": M, "N": N, "KQ": KQ, "KE": KE, **t, "round_spread": spread,
+           "one_launch_speedup": round(t["epilogue_gemm_then_quantize_us"] / t["quantising_epilogue_gemm_us"], 3)}
+    del ws, a, b
+    torch.cuda.empty_cache()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--table", choices=("all", "fused", "quant_epilogue"), default="all")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("mx_fused_bench: needs a GPU (there is no CPU measurement)")
     dev = "cuda:0"
-    res = {"device": torch.cuda.get_device_name(0),
-           "rmsnorm_quantize": [rmsnorm(M, KQ, dev, a.rounds) for M in (4, 4096) for KQ in (3584, 4096)],
-           "gate_up_qwen2.5-7b": [gate_up(M, dev, a.rounds) for M in (4, 64, 4096)],
-           "note": ("us per chain, HIP-graph replay over inputs / weights rotated through > 320 MB; best of the alternating rounds; "
+    res = {"device": torch.cuda.get_device_name(0)}
+    if a.table in ("all", "fused"):
+        res["rmsnorm_quantize"] = [rmsnorm(M, KQ, dev, a.rounds) for M in (4, 4096) for KQ in (3584, 4096)]
+        res["gate_up_qwen2.5-7b"] = [gate_up(M, dev, a.rounds) for M in (4, 64, 4096)]
+    if a.table in ("all", "quant_epilogue"):
+        res["gate_up_quant_epilogue_qwen2.5-7b"] = [quant_epilogue(M, dev, a.rounds) for M in (4, 16, 64, 4096)]
+    res["note"] = ("us per chain, HIP-graph replay over inputs / weights rotated through > 320 MB; best of the alternating rounds; "
                     "round_spread = largest (max - min) / min of a chain between rounds; *_speedup = the parent chain's time over the "
-                    "fused form's")}
+                    "fused form's")
     line = json.dumps(res)
     print(line)
     if a.out:
