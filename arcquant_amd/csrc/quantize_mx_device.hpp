@@ -48,7 +48,9 @@ __device__ __forceinline__ MxBlock mx_quantize_block(float (&v)[32]) {
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
       const float q = e2m1_to_f32((w[i >> 3] >> (4 * (i & 7))) & 0xfu);
-      v[i] = v[i] - __builtin_ldexpf(q, e);      // exact: a multiple of ulp_bf16(v) with |res| <= |v|
+      // exact: a multiple of ulp_bf16(v) with |res| <= |v|.  Formed at half scale: deq(code) * 2^e itself is 2^128 for code 4.0 at
+      // e = 126 (amax >= 1.75 * 2^127 rounds up to it), +inf in fp32.  Halving a widened bf16 and doubling the result are exact.
+      v[i] = 2.0f * (0.5f * v[i] - __builtin_ldexpf(q, e - 1));
     }
   }
   MxBlock b;

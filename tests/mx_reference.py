@@ -126,6 +126,66 @@ def gemm(QA, QB, SFA, SFB, alpha=1.0) -> np.ndarray:
     return alpha * (dequantize(QA, SFA) @ dequantize(QB, SFB).T)
 
 
+def abs_gemm(QA, QB, SFA, SFB) -> np.ndarray:
+    """fp64 sum_k |deq(A)[m,k]| |deq(B)[n,k]|: the magnitude every partial sum of gemm() stays under, in any order."""
+    return np.abs(dequantize(QA, SFA)) @ np.abs(dequantize(QB, SFB)).T
+
+
+def bf16_rne_bits(x) -> np.ndarray:
+    """fp64 -> bit pattern of the nearest bf16 (RNE) in ONE rounding (bf16_round takes fp32: from fp64 that would round twice).
+    For zero and the normal range of bf16, which is all a GEMM output needs."""
+    x = np.asarray(x, dtype=np.float64)
+    assert np.all((x == 0) | ((np.abs(x) >= 2.0 ** -126) & (np.abs(x) < 2.0 ** 128 * (1 - 2.0 ** -9)))), "outside the range this helper rounds exactly"
+    m, e = np.frexp(x)                          # x = m * 2^e, |m| in [0.5, 1): 8 significant bits = a multiple of 2^-8
+    v = np.ldexp(np.rint(m * 256.0), e - 8)     # m * 256 is exact in fp64, rint rounds half to even
+    return (v.astype(np.float32).view(np.uint32) >> 16).astype(np.uint16)
+
+
+def bf16_key(b) -> np.ndarray:
+    """Monotone integer key of a bf16 bit pattern (tests/test_gpu_parity.py _max_bf16_ulp_diff): a < b as values <=> key(a) < key(b),
+    with -0 and +0 on the same key."""
+    b = np.asarray(b).astype(np.int32)
+    return np.where(b & 0x8000, -(b & 0x7FFF), b & 0x7FFF)
+
+
+# ---------------------------------------------------------------------------------------------------------------- special values
+BOUNDARY_BITS = (0x4040, 0x40C0, 0x4041, 0x40C1)           # 3.0, 6.0, 3.015625, 6.03125: the two with a residual come last
+TIE_BITS = (0x3E80, 0x3F40, 0x3FA0, 0x3FE0, 0x4020, 0x4060, 0x40A0, 0x40C0)    # 0.25 0.75 1.25 1.75 2.5 3.5 5.0 6.0
+SPECIAL_ROWS = ("zero", "negative zero", "subnormals", "smallest normals", "largest finite", "exponent boundaries", "e2m1 ties",
+                "subnormal blocks beside ordinary ones")
+
+
+def special_value_rows(KQ: int, idx, seed: int) -> np.ndarray:
+    """bf16 bit patterns [8, KQ] (SPECIAL_ROWS) whose REORDERED rows X[:, idx] are the blocks described below, so that whatever
+    the permutation every kind of block also lies in the outlier tail (the last KE reordered channels) for any KE >= 64:
+      0  +0 everywhere                              1  -0.0 everywhere
+      2  subnormals 0x0001..0x007F, both signs      3  the smallest normals 0x0080..0x00FF, both signs
+      4  0x7F00..0x7F7F, both signs, one 0x7F7F (the largest finite bf16) per block
+      5  block b is all +-BOUNDARY_BITS[b % 4]: amax on and one bf16 ulp above the exponent rule's two boundaries
+      6  the eight e2m1 ties (6.0 among them, so e = 0), both signs, four times per block
+      7  even blocks subnormals, odd blocks 1 <= |v| < 8 with one 7.0."""
+    assert KQ % 128 == 0
+    rng = np.random.default_rng(seed)
+    B = KQ // 32
+    sign = lambda: (rng.integers(0, 2, (B, 32)).astype(np.uint16) << 15)       # noqa: E731
+    xr = np.zeros((8, B, 32), dtype=np.uint16)
+    xr[1] = 0x8000
+    xr[2] = rng.integers(0x0001, 0x0080, (B, 32)).astype(np.uint16) | sign()
+    xr[3] = rng.integers(0x0080, 0x0100, (B, 32)).astype(np.uint16) | sign()
+    big = rng.integers(0x7F00, 0x7F80, (B, 32)).astype(np.uint16)
+    big[np.arange(B), rng.integers(0, 32, B)] = 0x7F7F
+    xr[4] = big | sign()
+    xr[5] = np.asarray(BOUNDARY_BITS, dtype=np.uint16)[np.arange(B) % 4][:, None] | sign()
+    xr[6] = np.tile(np.asarray(TIE_BITS, dtype=np.uint16), 4)[rng.permuted(np.tile(np.arange(32), (B, 1)), axis=1)] | sign()
+    ordinary = (bf16_round(rng.uniform(1.0, 7.9, (B, 32)).astype(np.float32)).view(np.uint32) >> 16).astype(np.uint16)
+    ordinary[np.arange(B), rng.integers(0, 32, B)] = 0x40E0                    # 7.0
+    sub = rng.integers(0x0001, 0x0080, (B, 32)).astype(np.uint16)
+    xr[7] = np.where((np.arange(B) % 2 == 0)[:, None], sub, ordinary) | sign()
+    X = np.empty((8, KQ), dtype=np.uint16)
+    X[:, np.asarray(idx, dtype=np.int64)] = xr.reshape(8, KQ)
+    return X
+
+
 # ---------------------------------------------------------------------------------------------------------------- fake path
 def _round_to(a: np.ndarray, dtype: str) -> np.ndarray:
     a = np.asarray(a, dtype=np.float32)

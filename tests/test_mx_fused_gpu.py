@@ -11,7 +11,7 @@ from arcquant_amd import _lib, agemm, mx
 from tests import mx_fused_reference as FR
 from tests import mx_reference as R
 from tests.test_mx_gpu import _check, deq_torch
-from tests.util import bits, outlier_activations, random_perm
+from tests.util import bits, from_bits, outlier_activations, random_perm
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -63,6 +63,30 @@ def test_rmsnorm_quantiser_bytes_equal_reference(M, KQ, KE, perm):
     from arcquant_amd.qlinear import MXFP4_rmsnorm_quantize_x
     qx, sx, one = MXFP4_rmsnorm_quantize_x(Xd, Wd, EPS, idxd, KE)
     assert torch.equal(qx, Qm) and torch.equal(sx, Sm) and one.dim() == 0 and one.item() == 1.0
+
+
+def test_rmsnorm_quantiser_zero_and_subnormal_rows():
+    """An all-zero row (sum of squares 0, rstd = 1 / sqrt(eps): every block zero, scale byte 127) and a row of bf16 subnormals (their
+    squares underflow to 0 in fp32 as well; x * w is an fp32 subnormal that rstd lifts into the normal range) among ordinary rows,
+    byte for byte against tests/mx_fused_reference.py + R.quantize_x."""
+    M, KQ, KE = 6, 2048, 64
+    Xb = bits(outlier_activations(M, KQ, 31))
+    rng = np.random.default_rng(5)
+    Xb[1] = 0
+    Xb[4] = rng.integers(1, 0x80, KQ).astype(np.uint16) | (rng.integers(0, 2, KQ).astype(np.uint16) << 15)
+    W = _norm_weight(KQ, 9)
+    idx = random_perm(KQ, 13)
+    rows = FR.normalised_rows(Xb, bits(W), EPS, idx.numpy().astype(np.int64))
+    assert np.all(rows[1] == 0) and np.all(np.abs(rows[4]) >= 2.0 ** -126) and len(np.unique(rows[4])) > 100
+    wq, ws = FR.rmsnorm_quantize_x(Xb, bits(W), EPS, idx.numpy().astype(np.int64), KE)
+    assert np.all(ws[1] == 127) and np.all(wq[1] == 0) and wq[4, KQ // 2:(KQ + KE) // 2].any()
+    Xd, Wd, idxd = from_bits(Xb).to(DEV), W.to(DEV), idx.to(DEV)
+    fn = _lib.lib().arcq_mx_rmsnorm_quantize_x
+    for poison in (0x00, 0xFF):
+        Q, S = _poisoned(lambda q, sf: fn(Xd.data_ptr(), Wd.data_ptr(), EPS, idxd.data_ptr(), q, sf, M, KQ, KE, None), M, KQ, KE, poison)
+        for r in range(M):
+            assert np.array_equal(S[r], ws[r]), f"row {r}: scale bytes differ (poison {poison:#x})"
+            assert np.array_equal(Q[r], wq[r]), f"row {r}: codes differ (poison {poison:#x})"
 
 
 # -------------------------------------------------------------------------------------------------------------- SiLU*up quantiser

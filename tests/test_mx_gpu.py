@@ -1,6 +1,6 @@
-"""MXFP4 on the MI355X: the quantisers' bytes against tests/mx_reference.py, the operand / scale lane map of the block-scaled fp4
-MFMA pinned with exact integer data, the GEMM's accuracy against an fp64 dequantised product, the epilogue's roundings, the
-extension module against the ctypes mirror, and QLinearLayer(quant_type='MXFP4')."""
+"""MXFP4 on the MI355X: the quantisers' bytes against tests/mx_reference.py (special values included), the operand / scale lane
+map of the block-scaled fp4 MFMA pinned with exact integer data, the GEMM's accuracy against an fp64 dequantised product, the
+epilogue's roundings, the extension module against the ctypes mirror, and QLinearLayer(quant_type='MXFP4')."""
 import os
 
 import numpy as np
@@ -10,7 +10,7 @@ import torch
 from arcquant_amd import _build_ext, _lib, agemm
 from arcquant_amd.qlinear import QLinearLayer, reorder_quantize_x
 from tests import mx_reference as R
-from tests.util import bits, outlier_activations, random_perm
+from tests.util import bits, from_bits, outlier_activations, random_perm
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -60,6 +60,45 @@ def test_quantiser_bytes_equal_reference(M, KQ, KE, perm, is_x):
     # the mirror allocates and returns the same bytes
     Qm, Sm = (agemm.mx_reorder_quantize_x if is_x else agemm.mx_reorder_quantize_w)(Xd, idxd, KE)
     assert np.array_equal(Qm.cpu().numpy(), Q0) and np.array_equal(Sm.cpu().numpy(), S0)
+
+
+@pytest.mark.parametrize("perm", ["identity", "random"])
+@pytest.mark.parametrize("KE", [0, 64, "KQ"])
+@pytest.mark.parametrize("KQ", [128, 4096])
+def test_quantiser_special_values_byte_exact(KQ, KE, perm):
+    """R.special_value_rows through arcq_mx_quantize_x / _w: zero and -0.0 blocks, bf16 subnormals (the exponent clamp at -127), the
+    smallest normals, the largest finite values, amax on and one ulp above the exponent rule's boundaries, the e2m1 ties, and subnormal
+    blocks beside ordinary ones -- each kind also inside the outlier tail, where the residual block is quantised too.  The reference
+    runs first (its residual-exact and no-saturation assertions hold on this input); Inf and NaN are outside the contract."""
+    KE = KQ if KE == "KQ" else KE
+    idx = torch.arange(KQ, dtype=torch.int16) if perm == "identity" else random_perm(KQ, KQ + 7)
+    idxn = idx.numpy().astype(np.int64)
+    Xb = R.special_value_rows(KQ, idxn, KQ + KE)
+    xf = R.bf16_bits_to_f32(Xb)
+    want = {True: R.quantize_x(xf, idxn, KE), False: R.quantize_w(xf, idxn, KE)}
+    wq, ws = want[True]
+    B, P = KQ // 32, (KQ - KE) // 32
+    assert {0, 126, 127, 128, 253} <= set(np.unique(ws[:, :B]))
+    assert np.all(ws[:2] == 127) and np.all(R.unpack(wq[0]) == 0) and np.all(R.unpack(wq[1, :KQ // 2]) == 8)
+    if KE:
+        mag = Xb[:, idxn].reshape(8, B, 32)[:, P:] & 0x7FFF             # the tail of the reordered rows, whatever the permutation
+        assert np.all((mag[2] >= 1) & (mag[2] <= 0x7F)) and np.all(mag[4].max(axis=-1) == 0x7F7F)
+        assert {0x4041, 0x40C1} <= set(mag[5][:, 0]) and np.any(mag[7].max(axis=-1) <= 0x7F) and np.any(mag[7].min(axis=-1) >= 0x3F80)
+        rs, rq = ws[:, B:B + KE // 32], R.unpack(wq[:, KQ // 2:(KQ + KE) // 2])
+        # a subnormal's residual is at most a quarter of the clamped block's code step: it rounds to zero and leaves its sign in the code
+        assert len(np.unique(rs)) >= 5 and all((rq[r] & 7).any() for r in (3, 4, 5, 7)) and set(np.unique(rq[2])) == {0, 8}, \
+            "the tail's residual blocks are not exercised"
+    Xd, idxd = from_bits(Xb).to(DEV), idx.to(DEV)
+    for is_x in (True, False):
+        Q0, S0 = _quantize_poisoned(is_x, Xd, idxd, KE, 0x00)
+        Q1, S1 = _quantize_poisoned(is_x, Xd, idxd, KE, 0xFF)
+        assert np.array_equal(Q0, Q1) and np.array_equal(S0, S1), "some output byte is not written"
+        for r, name in enumerate(R.SPECIAL_ROWS):
+            who = f"{'x' if is_x else 'w'} row {r} ({name})"
+            bad = np.flatnonzero(S0[r] != want[is_x][1][r])
+            assert len(bad) == 0, f"{who}: scale bytes differ at blocks {bad[:8]}: got {S0[r][bad[:8]]} want {want[is_x][1][r][bad[:8]]}"
+            bad = np.flatnonzero(Q0[r] != want[is_x][0][r])
+            assert len(bad) == 0, f"{who}: codes differ at bytes {bad[:8]}: got {Q0[r][bad[:8]]} want {want[is_x][0][r][bad[:8]]}"
 
 
 # -------------------------------------------------------------------------------------------------------------- lane map

@@ -87,6 +87,35 @@ def test_bytes_equal_the_two_launch_chain(M, N, KQ, KE_in, KE):
         assert torch.equal(ms, want_s) and torch.equal(mq, want_q), f"the module returns other bytes ({sorted(kw)})"
 
 
+@pytest.mark.parametrize("M,N,KQ,KE_in,KE", [(5, 256, 1088, 64, 64), (65, 2176, 4096, 64, 256)])
+def test_bytes_equal_the_two_launch_chain_zero_and_negative_alpha(M, N, KQ, KE_in, KE):
+    """alpha = 0 (host and device): every y is +-0, so every activation is +-0 -- scale byte 127 in every block, residual and padding
+    included, and the codes carry nothing but the sign of zero; the precondition on distinct scale bytes is replaced by exactly that.
+    A negative alpha (host and device, with and without bias) under the usual preconditions.  Chain and fused kernel byte for byte."""
+    QX, QW, SX, SW, bias = _operands(M, N, KQ, KE_in, N + KQ + M)
+    KQ2 = N // 2
+    ident = torch.arange(KQ2, dtype=torch.int16, device=DEV)
+    dev = lambda v: torch.tensor(v, dtype=torch.float32, device=DEV)       # noqa: E731
+    cases = [(True, dict(scale=0.0)), (True, dict(scale=dev(0.0), scale_host=1.5)), (False, dict(scale=-0.75)),
+             (False, dict(scale=dev(-0.5), scale_host=1.5, bias=bias)), (False, dict(scale=-0.75, bias=bias))]
+    for zero, kw in cases:
+        want_q, want_s = agemm.mx_reorder_quantize_x(mx.matmul_silu_mul(QX, QW, SX, SW, **kw), ident, KE)
+        wq, ws = want_q.cpu().numpy(), want_s.cpu().numpy()
+        if zero:
+            assert np.all(ws == 127), "a zero activation has scale byte 127"
+            nib = R.unpack(wq[:, :KQ2 // 2])
+            assert set(np.unique(nib)) == {0, 8}, "both signs of zero among the reference's codes"
+            assert not wq[:, KQ2 // 2:].any(), "the residual of a zero and the padding are +0"
+        else:
+            assert len(np.unique(ws)) >= 4, f"reference scale bytes take {len(np.unique(ws))} values"
+            assert wq[:, KQ2 // 2:(KQ2 + KE) // 2].any(), "the reference's residual codes are all zero"
+        q0, s0 = _cabi(QX, QW, SX, SW, KE, 0x00, **kw)
+        q1, s1 = _cabi(QX, QW, SX, SW, KE, 0xFF, **kw)
+        assert np.array_equal(s0, s1) and np.array_equal(q0, q1), f"some output byte is not written ({sorted(kw)})"
+        assert np.array_equal(s0, ws), f"scale bytes differ ({sorted(kw)})"
+        assert np.array_equal(q0, wq), f"codes differ ({sorted(kw)})"
+
+
 @pytest.mark.parametrize("M", [4, 130])
 def test_deployment_row_order_equals_the_quantisers_gather(M):
     """The operator on the weight of mx.gate_up_rows(gate, up, reorder_index, ...) == mx_reorder_quantize_x(act, reorder_index, KE) of the
