@@ -367,9 +367,10 @@ extern "C" int arcq_harness_attn_decode(const void* qkv, void* kcache, void* vca
   return arcq_harness_attn_decode_window(qkv, kcache, vcache, out, workspace, B, H, Tmax, pos, 0, stream);
 }
 
-// the same over positions [first, pos] only (first == pos: what benchmarks/modeling_arc.py:169-198 attends over in a decode step)
-extern "C" int arcq_harness_attn_decode_window(const void* qkv, void* kcache, void* vcache, void* out, void* workspace, int64_t B, int64_t H,
-                                               int64_t Tmax, int64_t pos, int64_t first, void* stream) {
+// the same over positions [first, pos] only (first == pos: what benchmarks/modeling_arc.py:169-198 attends over in a decode step);
+// sliced != 0: the two-launch slice kernels instead of the one-launch kernel
+static int attn_decode_launch(const void* qkv, void* kcache, void* vcache, void* out, void* workspace, int64_t B, int64_t H, int64_t Tmax,
+                              int64_t pos, int64_t first, int sliced, void* stream) {
   const char* who = "arcq_harness_attn_decode";
   if (B <= 0 || H <= 0 || Tmax <= 0 || pos < 0 || pos >= Tmax || first < 0 || first > pos) return fail(ARCQ_ERR_SHAPE, "%s: bad B / H / Tmax / pos / first", who);
   if (!qkv || !kcache || !vcache || !out || !workspace) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
@@ -388,7 +389,6 @@ extern "C" int arcq_harness_attn_decode_window(const void* qkv, void* kcache, vo
   p.S = S; p.chunk = chunk;
   p.scale = 0.08838834764831845f;                           // 128^-0.5
   const int live = (T + chunk - 1) / chunk;
-  static const int sliced = getenv("ARCQ_HARNESS_ATTN_SLICED") ? atoi(getenv("ARCQ_HARNESS_ATTN_SLICED")) : 0;   // A-B: the two-launch slice kernels
   if (!sliced) {
     hipLaunchKernelGGL(attn_decode_fused, dim3((unsigned)(B * H)), dim3(kAttnFusedWaves * 64), 0, (hipStream_t)stream, p);
     hipError_t e1 = hipGetLastError();
@@ -400,6 +400,19 @@ extern "C" int arcq_harness_attn_decode_window(const void* qkv, void* kcache, vo
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
   return ARCQ_OK;
+}
+
+extern "C" int arcq_harness_attn_decode_window(const void* qkv, void* kcache, void* vcache, void* out, void* workspace, int64_t B, int64_t H,
+                                               int64_t Tmax, int64_t pos, int64_t first, void* stream) {
+  static const int sliced = getenv("ARCQ_HARNESS_ATTN_SLICED") ? atoi(getenv("ARCQ_HARNESS_ATTN_SLICED")) : 0;   // A-B: the two-launch slice kernels
+  return attn_decode_launch(qkv, kcache, vcache, out, workspace, B, H, Tmax, pos, first, sliced, stream);
+}
+
+// the two-launch slice kernels whatever the environment says: lets a test reach them (and their workspace) in the process that also runs
+// the default kernel
+extern "C" int arcq_harness_attn_decode_window_sliced(const void* qkv, void* kcache, void* vcache, void* out, void* workspace, int64_t B,
+                                                      int64_t H, int64_t Tmax, int64_t pos, int64_t first, void* stream) {
+  return attn_decode_launch(qkv, kcache, vcache, out, workspace, B, H, Tmax, pos, first, 1, stream);
 }
 
 // HARNESS ONLY: out[r, :] = rmsnorm(X[r, :]) * W for `rows` rows of H bf16 values (row stride ldx elements), one launch.

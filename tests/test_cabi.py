@@ -116,6 +116,7 @@ def test_round2_entry_points_reject_bad_arguments_without_a_gpu():
     # harness (include/arcq_harness.h)
     assert L.arcq_harness_attn_decode_window(P, P, P, P, P, 4, 28, 1152, 10, 11, None) == -1             # first > pos
     assert L.arcq_harness_attn_decode(P, P, P, P, P, 4, 28, 1152, 1152, None) == -1                       # pos >= Tmax
+    assert L.arcq_harness_attn_decode_window_sliced(P, P, P, P, P, 4, 28, 1152, 10, 11, None) == -1      # the same checks on the forced two-launch path
     assert L.arcq_harness_rmsnorm(P, 3584, P, P, 4, 3587, 1e-6, None) == -1
     assert L.arcq_harness_rmsnorm(P, 3584, P, P, 0, 3584, 1e-6, None) == 0
 
