@@ -75,6 +75,18 @@ HARNESS_SYMBOLS = {
     "arcq_harness_rmsnorm": (_i32, [_p, _i64, _p, _p, _i64, _i64, _f32, _p]),
 }
 
+# include/arcq_kv.h: the paged KV cache (arcquant_amd/kvcache.py)
+KV_INT4, KV_16BIT = 0, 1
+KV_F16, KV_BF16 = 0, 1
+KV_SYMBOLS = {
+    "arcq_kv_init": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p]),
+    "arcq_kv_append": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _p]),
+    "arcq_kv_append_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p]),
+    "arcq_kv_init_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p]),
+    "arcq_kv_decode_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
+    "arcq_kv_batch_decode": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p]),
+}
+
 _lib = None
 
 
@@ -92,7 +104,7 @@ def lib() -> ctypes.CDLL:
                 "There is no CPU fallback."
             )
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(HARNESS_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(HARNESS_SYMBOLS.items()) + list(KV_SYMBOLS.items()):
             fn = getattr(L, name)          # AttributeError if the .so does not export a declared symbol
             fn.restype = res
             fn.argtypes = args

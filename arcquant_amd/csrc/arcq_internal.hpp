@@ -137,4 +137,27 @@ int gemm_regtile_cfg(int64_t M, int64_t N, int64_t K, int epilogue);   // 0 = no
 int gemm_regtile(const GemmArgs& a, int cfg, hipStream_t stream);        // either B layout
 int gemm_regtile_fits(int64_t M, int64_t N, int64_t K, int b_layout);   // every operand addressable with the kernel's 32-bit offsets
 
+// kv_cache.hip: the paged KV cache of include/arcq_kv.h (arguments validated by c_api_kv.hip)
+struct KvWriteArgs {
+  void* kv_data;
+  void* kv_param;
+  const int32_t *kv_indptr, *kv_indices, *last_page_offset;
+  const void *k, *v, *k_param, *v_param;   // quantize: k, v are 16-bit [ntok, N, 128] and the parameters are computed
+  const int32_t* seqlen_indptr;            // NULL: append (ntok == B, token b is sequence b's last position)
+  int64_t ntok, B, L, layer, N, P;
+  int format, dtype;
+  bool quantize;
+};
+int kv_write(const KvWriteArgs& a, hipStream_t stream);
+struct KvDecodeArgs {
+  void* o;
+  const void *q, *kv_data, *kv_param;
+  const int32_t *kv_indptr, *kv_indices, *last_page_offset;
+  int64_t B, Nq, L, layer, N, P, nnz;
+  int format, dtype;
+  void* workspace;
+};
+int kv_decode_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P);   // slices per sequence; > 1 needs the workspace
+int kv_decode(const KvDecodeArgs& a, hipStream_t stream);
+
 }  // namespace arcq

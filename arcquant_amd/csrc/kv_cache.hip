@@ -1,0 +1,468 @@
+// The paged KV cache of include/arcq_kv.h: writers (copy and quantise-and-write) and the decode attention over int4 or 16-bit pages.
+//
+// Layout (the reference's, include/flashinfer/page.cuh:76-103): rows of the grid [pages, L, 2, N, P]; a row is 64 bytes of codes
+// (element 2j in the low nibble of byte j) or 128 16-bit values, and has one (scale, zero) fp16 pair in kv_param at the same row
+// index.  Position t of sequence b lives in page kv_indices[kv_indptr[b] + t / P], entry t % P.
+//
+//   kv_write_kernel      one workgroup per token: 16-byte copies of the K and V rows of every head + their parameter pairs
+//   kv_quantize_kernel   four rows per wave (16 lanes x 8 values): amax / amin over the row, the torch-eager formula with every
+//                        operation rounded to the input dtype, codes and parameters stored straight into the page
+//   kv_decode_kernel     grid (B * N * chunks, S): a 256-thread workgroup per (sequence, kv head, chunk of <= 4 query heads of that kv
+//                        head, slice of the sequence).  A wave streams a contiguous range of positions: each lane holds 16 codes (8
+//                        bytes, 8 rows per 512-byte wave load) or 8 16-bit values (16 bytes, 4 rows per 1-KiB load) of a row, four
+//                        K loads, four V loads and their parameters requested together, the next block's in flight while this one
+//                        is reduced.  Scores use  sum_d q_d (c_d s - z) = s sum_d q_d c_d - z sum_d q_d  and the value sum
+//                        sum_t p_t (c_td s_t - z_t) = sum_t (p_t s_t) c_td - sum_t p_t z_t:  one conversion and one FMA per code
+//                        and query head.  Online softmax per wave, the waves merge through LDS; S > 1 leaves (max, sum, 128
+//                        accumulators) records in the workspace for kv_decode_combine.  fp32 throughout.
+//   Rows past a wave's range are clamped to the sequence's last valid position and masked: no byte outside the valid positions of
+//   the pages the tables name is read.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/arcq_kv.h"
+#include "arcq_device.hpp"
+#include "arcq_internal.hpp"
+
+namespace arcq {
+
+constexpr int kKvD = 128;
+constexpr int kKvRec = kKvD + 2;         // a merge record: max, sum, 128 accumulators
+constexpr int kKvWaves = 4;
+constexpr float kKvIdle = -3.0e38f;
+
+struct KvTables {
+  const int32_t* indptr;
+  const int32_t* indices;
+  const int32_t* last;
+};
+
+__device__ __forceinline__ int kv_seq_len(const KvTables& t, int b, int P) { return (t.indptr[b + 1] - t.indptr[b] - 1) * P + t.last[b]; }
+
+// row index in [pages, L, 2, N, P] of position `pos` of sequence b: K of head n (V: + N * P)
+__device__ __forceinline__ size_t kv_row(const KvTables& t, int b, int n, int pos, int L, int layer, int N, int P) {
+  const int pg = pos / P, e = pos - pg * P;
+  const size_t page = (size_t)t.indices[t.indptr[b] + pg];
+  return (((page * L + layer) * 2) * N + n) * P + e;
+}
+
+// ---- the 16-bit element types
+template <bool BF16>
+__device__ __forceinline__ float kv_to_f32(uint32_t bits) {
+  if constexpr (BF16) return bf16_bits_to_f32(bits & 0xffffu);
+  else return (float)__builtin_bit_cast(_Float16, (uint16_t)bits);
+}
+template <bool BF16>
+__device__ __forceinline__ uint32_t kv_from_f32(float f) {
+  if constexpr (BF16) return f32_to_bf16_bits(f);
+  else return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)f);
+}
+template <bool BF16>
+__device__ __forceinline__ float kv_round(float f) { return kv_to_f32<BF16>(kv_from_f32<BF16>(f)); }
+
+// ---- writers
+struct KvWriteParams {
+  uint8_t* data;
+  uint32_t* param;
+  KvTables t;
+  const uint8_t* k;
+  const uint8_t* v;
+  const uint32_t* kp;             // fp16 (scale, zero) pairs [ntok, N] (copy kernel only)
+  const uint32_t* vp;
+  const int32_t* seqlen_indptr;   // NULL: append -- token b is the last position of sequence b
+  int ntok, B, L, layer, N, P, row_bytes;
+};
+
+// token -> (sequence, position); false: the token belongs to no sequence
+__device__ __forceinline__ bool kv_locate(const KvWriteParams& p, int tok, int& b, int& pos) {
+  if (p.seqlen_indptr == nullptr) {
+    b = tok;
+    pos = kv_seq_len(p.t, b, p.P) - 1;
+    return pos >= 0;
+  }
+  if (tok >= p.seqlen_indptr[p.B]) return false;
+  int lo = 0, hi = p.B;           // the last b with seqlen_indptr[b] <= tok
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (p.seqlen_indptr[mid] <= tok) lo = mid; else hi = mid;
+  }
+  b = lo;
+  pos = kv_seq_len(p.t, b, p.P) - (p.seqlen_indptr[b + 1] - p.seqlen_indptr[b]) + (tok - p.seqlen_indptr[b]);
+  return pos >= 0;
+}
+
+__global__ __launch_bounds__(256) void kv_write_kernel(KvWriteParams p) {
+  const int tok = blockIdx.x, tid = threadIdx.x;
+  int b, pos;
+  if (!kv_locate(p, tok, b, pos)) return;
+  const int cpr = p.row_bytes >> 4;                     // 16-byte chunks per row
+  const int chunks = p.N * cpr;
+  const size_t vrows = (size_t)p.N * p.P;
+  const size_t row0 = kv_row(p.t, b, 0, pos, p.L, p.layer, p.N, p.P);
+  for (int i = tid; i < 2 * chunks; i += 256) {
+    const int which = i >= chunks, j = i - which * chunks;
+    const int n = j / cpr, c = j - n * cpr;
+    const uint4 d = *reinterpret_cast<const uint4*>((which ? p.v : p.k) + ((size_t)tok * p.N + n) * p.row_bytes + c * 16);
+    *reinterpret_cast<uint4*>(p.data + (row0 + which * vrows + (size_t)n * p.P) * p.row_bytes + c * 16) = d;
+  }
+  for (int i = tid; i < 2 * p.N; i += 256) {
+    const int which = i >= p.N, n = i - which * p.N;
+    p.param[row0 + which * vrows + (size_t)n * p.P] = (which ? p.vp : p.kp)[(size_t)tok * p.N + n];
+  }
+}
+
+// rows = (token, K | V, head); four rows per wave, 16 lanes x 8 values each
+template <bool BF16>
+__global__ __launch_bounds__(256) void kv_quantize_kernel(KvWriteParams p) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane >> 4, c = lane & 15;
+  const int64_t rows = (int64_t)p.ntok * 2 * p.N;
+  const int64_t R = ((int64_t)blockIdx.x * 4 + wave) * 4 + r;
+  if (R >= rows) return;                                // (the 16 lanes of a row leave together; the shuffles below stay inside a row)
+  const int tok = (int)(R / (2 * p.N)), rem = (int)(R - (int64_t)tok * 2 * p.N);
+  const int which = rem >= p.N, n = rem - which * p.N;
+  int b, pos;
+  if (!kv_locate(p, tok, b, pos)) return;
+  const uint4 d = *reinterpret_cast<const uint4*>((which ? p.v : p.k) + ((size_t)tok * p.N + n) * (kKvD * 2) + c * 16);
+  const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    x[2 * j] = kv_to_f32<BF16>(w[j] & 0xffffu);
+    x[2 * j + 1] = kv_to_f32<BF16>(w[j] >> 16);
+  }
+  float xmax = x[0], xmin = x[0];
+#pragma unroll
+  for (int j = 1; j < 8; ++j) {
+    xmax = fmaxf(xmax, x[j]);
+    xmin = fminf(xmin, x[j]);
+  }
+#pragma unroll
+  for (int sh = 8; sh > 0; sh >>= 1) {
+    xmax = fmaxf(xmax, __shfl_xor(xmax, sh, 64));
+    xmin = fminf(xmin, __shfl_xor(xmin, sh, 64));
+  }
+  // torch eager on a tensor of the input dtype: every operation's result is rounded to that dtype (the Scalar 1e-5 too)
+  const float range = fmaxf(kv_round<BF16>(xmax - xmin), kv_round<BF16>(1e-5f));
+  const float scale = kv_round<BF16>(range / 15.0f);
+  const float zero = -xmin;
+  uint32_t codes = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float a = kv_round<BF16>(x[j] + zero);
+    const float qv = kv_round<BF16>(a / scale);
+    const float rc = fminf(fmaxf(__builtin_rintf(qv), 0.0f), 15.0f);      // (NaN -- inf / inf of an overflowing fp16 range -- becomes code 0)
+    codes |= (uint32_t)rc << (4 * j);
+  }
+  const size_t row = kv_row(p.t, b, n, pos, p.L, p.layer, p.N, p.P) + (size_t)which * p.N * p.P;
+  *reinterpret_cast<uint32_t*>(p.data + row * 64 + c * 4) = codes;
+  if (c == 0) p.param[row] = kv_from_f32<false>(scale) | (kv_from_f32<false>(zero) << 16);
+}
+
+// ---- decode attention
+struct KvDecodeParams {
+  void* o;
+  const void* q;
+  const uint8_t* data;
+  const uint32_t* param;
+  KvTables t;
+  float* ws;                // [B * Nq, S, kKvRec]
+  int B, Nq, L, layer, N, P, S, g, chunks;
+  float sm_scale;
+};
+
+template <int EPL>
+struct KvRaw {
+  uint32_t w[EPL == 16 ? 2 : 4];                       // 16 codes = 2 words, 8 16-bit values = 4 words
+};
+
+template <int FMT, bool BF16, int GC>
+__global__ __launch_bounds__(kKvWaves * 64) void kv_decode_kernel(KvDecodeParams p) {
+  constexpr bool I4 = FMT == ARCQ_KV_INT4;
+  constexpr int EPL = I4 ? 16 : 8;                     // elements per lane
+  constexpr int LPR = kKvD / EPL;                      // lanes per row: 8 | 16
+  constexpr int RPL = 64 / LPR;                        // rows per wave load: 8 | 4
+  constexpr int NL = 4;                                // loads of K (and of V) in flight per block
+  constexpr int BP = NL * RPL;                         // positions per block: 32 | 16
+  constexpr int ROWB = I4 ? 64 : 256, LANEB = ROWB / LPR, NW = LANEB / 4;
+  __shared__ float rec[kKvWaves][GC][kKvRec];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane / LPR, c = lane % LPR;
+  const int ch = blockIdx.x % p.chunks, bn = blockIdx.x / p.chunks;
+  const int b = bn / p.N, n = bn - b * p.N;
+  const int s = blockIdx.y;
+  const int T = kv_seq_len(p.t, b, p.P);
+  const int nblk = (T + BP - 1) / BP, units = p.S * kKvWaves;
+  const int per = (nblk + units - 1) / units;
+  const int t0 = min(T, (s * kKvWaves + wave) * per * BP), t1 = min(T, t0 + per * BP);
+  const size_t vrows = (size_t)p.N * p.P;
+
+  // this chunk's query heads (a head past the group repeats the last one and is not stored)
+  float qf[GC][EPL], qsum[GC];
+#pragma unroll
+  for (int gi = 0; gi < GC; ++gi) {
+    const int h = n * p.g + min(ch * GC + gi, p.g - 1);
+    const uint16_t* qrow = reinterpret_cast<const uint16_t*>(p.q) + ((size_t)b * p.Nq + h) * kKvD + c * EPL;
+    float acc = 0.f;
+#pragma unroll
+    for (int e8 = 0; e8 < EPL / 8; ++e8) {
+      const uint4 d = *reinterpret_cast<const uint4*>(qrow + e8 * 8);
+      const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        qf[gi][e8 * 8 + 2 * j] = kv_to_f32<BF16>(w[j] & 0xffffu) * p.sm_scale;
+        qf[gi][e8 * 8 + 2 * j + 1] = kv_to_f32<BF16>(w[j] >> 16) * p.sm_scale;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) acc += qf[gi][e];
+#pragma unroll
+    for (int sh = LPR / 2; sh > 0; sh >>= 1) acc += __shfl_xor(acc, sh, 64);
+    qsum[gi] = acc;
+  }
+
+  using Raw = KvRaw<EPL>;
+  auto load_block = [&](int tb, Raw (&kk)[NL], Raw (&vv)[NL], uint32_t (&pk)[NL], uint32_t (&pv)[NL]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < NL; ++u) {
+      const int t = min(tb + u * RPL + r, T - 1);       // past the range: the sequence's last valid row, masked below
+      const size_t row = kv_row(p.t, b, n, t, p.L, p.layer, p.N, p.P);
+      const uint8_t* ka = p.data + row * ROWB + c * LANEB;
+      const uint8_t* va = ka + vrows * ROWB;
+      if constexpr (I4) {
+        const uint2 a = *reinterpret_cast<const uint2*>(ka), bb = *reinterpret_cast<const uint2*>(va);
+        kk[u].w[0] = a.x; kk[u].w[1] = a.y;
+        vv[u].w[0] = bb.x; vv[u].w[1] = bb.y;
+        pk[u] = p.param[row];
+        pv[u] = p.param[row + vrows];
+      } else {
+        const uint4 a = *reinterpret_cast<const uint4*>(ka), bb = *reinterpret_cast<const uint4*>(va);
+        kk[u].w[0] = a.x; kk[u].w[1] = a.y; kk[u].w[2] = a.z; kk[u].w[3] = a.w;
+        vv[u].w[0] = bb.x; vv[u].w[1] = bb.y; vv[u].w[2] = bb.z; vv[u].w[3] = bb.w;
+        pk[u] = 0; pv[u] = 0;
+      }
+    }
+  };
+  auto decode = [&](const Raw& raw, float (&x)[EPL]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int wi = 0; wi < NW; ++wi) {
+      if constexpr (I4) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[wi * 8 + i] = (float)((raw.w[wi] >> (4 * i)) & 15u);
+      } else {
+        x[wi * 2] = kv_to_f32<BF16>(raw.w[wi] & 0xffffu);
+        x[wi * 2 + 1] = kv_to_f32<BF16>(raw.w[wi] >> 16);
+      }
+    }
+  };
+
+  float m[GC], l[GC], zacc[GC], acc[GC][EPL];
+#pragma unroll
+  for (int gi = 0; gi < GC; ++gi) {
+    m[gi] = kKvIdle; l[gi] = 0.f; zacc[gi] = 0.f;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) acc[gi][e] = 0.f;
+  }
+  auto consume = [&](int tb, const Raw (&kk)[NL], const Raw (&vv)[NL], const uint32_t (&pk)[NL], const uint32_t (&pv)[NL]) __attribute__((always_inline)) {
+    float d[NL][GC], mb[GC];
+#pragma unroll
+    for (int gi = 0; gi < GC; ++gi) mb[gi] = kKvIdle;
+#pragma unroll
+    for (int u = 0; u < NL; ++u) {
+      float x[EPL];
+      decode(kk[u], x);
+      const bool valid = tb + u * RPL + r < t1;
+      const float ks = I4 ? kv_to_f32<false>(pk[u] & 0xffffu) : 1.f, kz = I4 ? kv_to_f32<false>(pk[u] >> 16) : 0.f;
+#pragma unroll
+      for (int gi = 0; gi < GC; ++gi) {
+        float dot = 0.f;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) dot = fmaf(qf[gi][e], x[e], dot);
+#pragma unroll
+        for (int sh = LPR / 2; sh > 0; sh >>= 1) dot += __shfl_xor(dot, sh, 64);
+        const float sc = I4 ? ks * dot - kz * qsum[gi] : dot;
+        d[u][gi] = valid ? sc : kKvIdle;
+        mb[gi] = fmaxf(mb[gi], d[u][gi]);
+      }
+    }
+#pragma unroll
+    for (int gi = 0; gi < GC; ++gi) {
+#pragma unroll
+      for (int sh = LPR; sh < 64; sh <<= 1) mb[gi] = fmaxf(mb[gi], __shfl_xor(mb[gi], sh, 64));   // over the row groups: wave-uniform
+      const float mn = fmaxf(m[gi], mb[gi]), a = __expf(m[gi] - mn);
+      l[gi] *= a;
+      zacc[gi] *= a;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) acc[gi][e] *= a;
+      m[gi] = mn;
+    }
+#pragma unroll
+    for (int u = 0; u < NL; ++u) {
+      float x[EPL];
+      decode(vv[u], x);
+      const bool valid = tb + u * RPL + r < t1;
+      const float vs = I4 ? kv_to_f32<false>(pv[u] & 0xffffu) : 1.f, vz = I4 ? kv_to_f32<false>(pv[u] >> 16) : 0.f;
+#pragma unroll
+      for (int gi = 0; gi < GC; ++gi) {
+        const float pt = valid ? __expf(d[u][gi] - m[gi]) : 0.f;
+        l[gi] += pt;                                    // (this lane's row group; the groups are added at the end)
+        const float ps = pt * vs;
+        if constexpr (I4) zacc[gi] += pt * vz;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) acc[gi][e] = fmaf(ps, x[e], acc[gi][e]);
+      }
+    }
+  };
+
+  if (t0 < t1) {
+    Raw k0[NL], v0[NL], k1[NL], v1[NL];
+    uint32_t pk0[NL], pv0[NL], pk1[NL], pv1[NL];
+    load_block(t0, k0, v0, pk0, pv0);
+    for (int tb = t0; tb < t1; tb += 2 * BP) {         // two blocks per trip: the other buffer's loads stay in flight
+      if (tb + BP < t1) load_block(tb + BP, k1, v1, pk1, pv1);
+      consume(tb, k0, v0, pk0, pv0);
+      if (tb + BP < t1) {
+        if (tb + 2 * BP < t1) load_block(tb + 2 * BP, k0, v0, pk0, pv0);
+        consume(tb + BP, k1, v1, pk1, pv1);
+      }
+    }
+  }
+  // the row groups of a wave hold the same columns: add them; then the wave's record
+#pragma unroll
+  for (int gi = 0; gi < GC; ++gi) {
+#pragma unroll
+    for (int sh = LPR; sh < 64; sh <<= 1) {
+      l[gi] += __shfl_xor(l[gi], sh, 64);
+      zacc[gi] += __shfl_xor(zacc[gi], sh, 64);
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) acc[gi][e] += __shfl_xor(acc[gi][e], sh, 64);
+    }
+    if (r == 0) {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) rec[wave][gi][2 + c * EPL + e] = acc[gi][e] - zacc[gi];
+      if (c == 0) {
+        rec[wave][gi][0] = m[gi];
+        rec[wave][gi][1] = l[gi];
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < kKvD) {                                     // merge of the waves (idle ones carry m = kKvIdle, l = 0)
+#pragma unroll
+    for (int gi = 0; gi < GC; ++gi) {
+      if (ch * GC + gi >= p.g) break;
+      const int h = n * p.g + ch * GC + gi;
+      float M = kKvIdle;
+#pragma unroll
+      for (int w = 0; w < kKvWaves; ++w) M = fmaxf(M, rec[w][gi][0]);
+      float Ls = 0.f, a = 0.f;
+#pragma unroll
+      for (int w = 0; w < kKvWaves; ++w) {
+        const float f = __expf(rec[w][gi][0] - M);
+        Ls += rec[w][gi][1] * f;
+        a += rec[w][gi][2 + tid] * f;
+      }
+      const size_t bh = (size_t)b * p.Nq + h;
+      if (p.S == 1) {
+        reinterpret_cast<uint16_t*>(p.o)[bh * kKvD + tid] = (uint16_t)kv_from_f32<BF16>(Ls > 0.f ? a / Ls : 0.f);
+      } else {
+        float* o = p.ws + (bh * p.S + s) * kKvRec;
+        o[2 + tid] = a;
+        if (tid == 0) {
+          o[0] = M;
+          o[1] = Ls;
+        }
+      }
+    }
+  }
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(kKvD) void kv_decode_combine(KvDecodeParams p) {
+  const size_t bh = blockIdx.x;
+  const int d = threadIdx.x;
+  const float* w = p.ws + bh * p.S * kKvRec;
+  float M = kKvIdle;
+  for (int s = 0; s < p.S; ++s) M = fmaxf(M, w[s * kKvRec]);
+  float Ls = 0.f, a = 0.f;
+  for (int s = 0; s < p.S; ++s) {
+    const float f = __expf(w[s * kKvRec] - M);
+    Ls += w[s * kKvRec + 1] * f;
+    a += w[s * kKvRec + 2 + d] * f;
+  }
+  reinterpret_cast<uint16_t*>(p.o)[bh * kKvD + d] = (uint16_t)kv_from_f32<BF16>(Ls > 0.f ? a / Ls : 0.f);
+}
+
+// ---- launchers (arguments validated by c_api_kv.hip)
+static int launched(const char* who) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return ARCQ_OK;
+}
+
+int kv_write(const KvWriteArgs& a, hipStream_t stream) {
+  KvWriteParams p;
+  p.data = (uint8_t*)a.kv_data; p.param = (uint32_t*)a.kv_param;
+  p.t = {a.kv_indptr, a.kv_indices, a.last_page_offset};
+  p.k = (const uint8_t*)a.k; p.v = (const uint8_t*)a.v; p.kp = (const uint32_t*)a.k_param; p.vp = (const uint32_t*)a.v_param;
+  p.seqlen_indptr = a.seqlen_indptr;
+  p.ntok = (int)a.ntok; p.B = (int)a.B; p.L = (int)a.L; p.layer = (int)a.layer; p.N = (int)a.N; p.P = (int)a.P;
+  p.row_bytes = a.format == ARCQ_KV_INT4 ? 64 : 256;
+  if (!a.quantize) {
+    hipLaunchKernelGGL(kv_write_kernel, dim3((unsigned)a.ntok), dim3(256), 0, stream, p);
+    return launched("arcq_kv_write");
+  }
+  const int64_t rows = a.ntok * 2 * a.N;
+  const dim3 grid((unsigned)((rows + 15) / 16));
+  if (a.dtype == ARCQ_KV_BF16) hipLaunchKernelGGL(kv_quantize_kernel<true>, grid, dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL(kv_quantize_kernel<false>, grid, dim3(256), 0, stream, p);
+  return launched("arcq_kv_quantize");
+}
+
+// query heads of a kv head that share a workgroup's pass over its rows
+static int kv_group_chunk(int64_t g) { return g == 1 ? 1 : g == 2 ? 2 : 4; }
+
+// slices per sequence: enough workgroups for ~4 per CU while a wave keeps at least one 32-position block of an average sequence
+int kv_decode_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P) {
+  if (B <= 0 || Nq <= 0 || N <= 0 || nnz <= 0 || P <= 0) return 1;
+  const int64_t g = Nq / N, gc = kv_group_chunk(g), chunks = (g + gc - 1) / gc;
+  const int64_t avg = nnz * P / B;
+  int64_t S = (1024 + B * N * chunks - 1) / (B * N * chunks);
+  const int64_t cap = avg / (32 * kKvWaves);
+  if (S > cap) S = cap;
+  if (S > 32) S = 32;
+  return S < 1 ? 1 : (int)S;
+}
+
+int kv_decode(const KvDecodeArgs& a, hipStream_t stream) {
+  KvDecodeParams p;
+  p.o = a.o; p.q = a.q; p.data = (const uint8_t*)a.kv_data; p.param = (const uint32_t*)a.kv_param;
+  p.t = {a.kv_indptr, a.kv_indices, a.last_page_offset};
+  p.ws = (float*)a.workspace;
+  p.B = (int)a.B; p.Nq = (int)a.Nq; p.L = (int)a.L; p.layer = (int)a.layer; p.N = (int)a.N; p.P = (int)a.P;
+  p.g = (int)(a.Nq / a.N);
+  const int gc = kv_group_chunk(p.g);
+  p.chunks = (p.g + gc - 1) / gc;
+  p.S = kv_decode_splits(a.B, a.Nq, a.N, a.nnz, a.P);
+  p.sm_scale = 0.08838834764831845f;                    // 128^-0.5
+  const dim3 grid((unsigned)(a.B * a.N * p.chunks), (unsigned)p.S), block(kKvWaves * 64);
+  const bool bf = a.dtype == ARCQ_KV_BF16;
+#define ARCQ_KV_LAUNCH(FMT, GC)                                                                         \
+  do {                                                                                                  \
+    if (bf) hipLaunchKernelGGL((kv_decode_kernel<FMT, true, GC>), grid, block, 0, stream, p);           \
+    else hipLaunchKernelGGL((kv_decode_kernel<FMT, false, GC>), grid, block, 0, stream, p);             \
+  } while (0)
+  if (a.format == ARCQ_KV_INT4) {
+    if (gc == 1) ARCQ_KV_LAUNCH(ARCQ_KV_INT4, 1); else if (gc == 2) ARCQ_KV_LAUNCH(ARCQ_KV_INT4, 2); else ARCQ_KV_LAUNCH(ARCQ_KV_INT4, 4);
+  } else {
+    if (gc == 1) ARCQ_KV_LAUNCH(ARCQ_KV_16BIT, 1); else if (gc == 2) ARCQ_KV_LAUNCH(ARCQ_KV_16BIT, 2); else ARCQ_KV_LAUNCH(ARCQ_KV_16BIT, 4);
+  }
+#undef ARCQ_KV_LAUNCH
+  if (p.S > 1) {
+    if (bf) hipLaunchKernelGGL(kv_decode_combine<true>, dim3((unsigned)(a.B * a.Nq)), dim3(kKvD), 0, stream, p);
+    else hipLaunchKernelGGL(kv_decode_combine<false>, dim3((unsigned)(a.B * a.Nq)), dim3(kKvD), 0, stream, p);
+  }
+  return launched("arcq_kv_batch_decode");
+}
+
+}  // namespace arcq

@@ -16,6 +16,9 @@ allocation-free apart from torch's caching allocator).
 
 ``quant_type="MXFP4"`` runs the same layer structure on the block-scaled fp4 MFMA (``DecoderModel._forward_mx``): weights quantised with
 ``agemm.mx_reorder_quantize_w`` (no per-tensor scale, alpha = 1), activations with the one-launch operators of ``arcquant_amd.mx``.
+
+``kv_cache="int4"`` (``--kv-cache int4``) swaps the dense bf16 cache for the reference's int4 paged cache served by ``arcquant_amd.kvcache``
+(``DecoderModel._attention_int4``); the default is the dense cache.
 """
 from __future__ import annotations
 
@@ -25,7 +28,7 @@ import time
 import torch
 import torch.nn.functional as F
 
-from . import agemm, mx
+from . import agemm, kvcache, mx
 
 
 @dataclasses.dataclass
@@ -113,15 +116,23 @@ class DecoderModel:
     # Chosen by measurement (tools/mx_fused_bench.py): at the Qwen2.5-7B gate|up shape the epilogue route takes 34.3 us
     # against 35.5 at M = 4 and 134 against 140 at M = 64.
     mx_decode_route = "epilogue"
+    kv_page_size = 16         # kv_cache="int4": positions per page (the reference's benchmark default)
 
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
-                 repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False):
+                 repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False, kv_cache: str = "bf16"):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
         the repack and every GEMM the repacked kernels do not serve runs through agemm.matmul_rw / matmul_rw_silu_mul.
         mx_quantised_epilogue (quant_type="MXFP4", fused=True only): the gate|up GEMM writes the down projection's quantised input itself
-        (mx.matmul_silu_mul_quantize) instead of mx.matmul_silu_mul + mx_reorder_quantize_x, prefill and decode alike; same logits."""
+        (mx.matmul_silu_mul_quantize) instead of mx.matmul_silu_mul + mx_reorder_quantize_x, prefill and decode alike; same logits.
+        kv_cache="int4" (attention="cache", head dimension 128): the reference's int4 paged cache (arcquant_amd.kvcache)
+        instead of the dense bf16 one -- a prefill writes its k / v through init_kv_quantize_i4, a decode step appends with
+        append_kv_quantize_i4 and attends with batch_decode_i4.  "bf16" (default) is the dense cache."""
+        if kv_cache not in ("bf16", "int4"):
+            raise ValueError(f"DecoderModel: kv_cache must be 'bf16' or 'int4', got {kv_cache!r}")
+        if kv_cache == "int4" and (attention != "cache" or cfg.hidden_size // cfg.num_heads != kvcache.HEAD_DIM):
+            raise ValueError("DecoderModel: kv_cache='int4' needs attention='cache' and a head dimension of 128")
         if repacked_only and not fused:
             raise ValueError("DecoderModel: repacked_only=True needs fused=True (the unfused model is the reference's call structure)")
         if quant_type not in ("NVFP4", "MXFP4"):
@@ -136,6 +147,8 @@ class DecoderModel:
         self.cfg, self.device, self.batch, self.max_len, self.fused = cfg, device, batch, max_len, fused
         self.repacked_only = repacked_only
         self.attention = attention
+        self.kv_cache = kv_cache
+        self.kv_trace = None      # a list: _attention_int4 appends (layer, pos, q, k, v, out) of every decode step to it (tests)
         # the down projection's quantiser as its GEMM's prologue: every CU then quantises the whole M x intermediate activation
         # itself, which only pays while that is small (measured: Qwen2.5-7B, 4 x 18944: slower than the separate launch)
         self.fused_down = batch * cfg.intermediate_size <= 4 * 8192
@@ -167,7 +180,7 @@ class DecoderModel:
                    dict(q=QLinear(h, h, ke, device, g, ab, qt), k=QLinear(h, h, ke, device, g, ab, qt), v=QLinear(h, h, ke, device, g, ab, qt),
                         gate=QLinear(h, it, ke, device, g, mb, qt), up=QLinear(h, it, ke, device, g, mb, qt))),
                 o=QLinear(h, h, ke, device, g, ab, qt), down=QLinear(it, h, ke, device, g, mb, qt),
-                kv=torch.zeros(2, batch, cfg.num_heads, max_len, h // cfg.num_heads, dtype=torch.bfloat16, device=device)))
+                kv=torch.zeros(2, batch, cfg.num_heads, max_len if kv_cache == "bf16" else 0, h // cfg.num_heads, dtype=torch.bfloat16, device=device)))
             self.layers[-1]["kc"], self.layers[-1]["vc"] = self.layers[-1]["kv"][0], self.layers[-1]["kv"][1]
         if fused and quant_type == "NVFP4":
             for L in self.layers:
@@ -182,6 +195,8 @@ class DecoderModel:
         self.lm_head = (torch.randn(cfg.vocab_size, h, generator=g, device=device) * 0.02).to(torch.bfloat16)
         self.embed = (torch.randn(cfg.vocab_size, h, generator=g, device=device) * 0.02).to(torch.bfloat16)
         self.one = torch.ones(1, dtype=torch.float32, device=device)
+        # every layer's pages in one paged cache, with the page tables of every length built here -- before any graph capture
+        self.kvc = kvcache.PagedKVCacheI4(batch, self.kv_page_size, max_len, device, cfg.num_layers, cfg.num_heads) if kv_cache == "int4" else None
 
     def weight_bytes(self):
         per_layer = sum(v.bytes() for v in self.layers[0].values() if isinstance(v, QLinear))
@@ -204,7 +219,7 @@ class DecoderModel:
         hcur = F.embedding(tokens, self.embed).reshape(bsz * q_len, cfg.hidden_size)      # one gather launch (advanced indexing: ~10)
         h, it, ke = cfg.hidden_size, cfg.intermediate_size, cfg.select_num
         T = bsz * q_len
-        for L in self.layers:
+        for li, L in enumerate(self.layers):
             # ---- attention block: RMSNorm + quantise, q|k|v projection
             if self.fused:
                 Q = L["qkv"]
@@ -218,7 +233,9 @@ class DecoderModel:
             else:
                 A, SFA = agemm.rmsnorm_quantize_x(hcur, L["ln1"], cfg.eps, self.idx_h, ke)
                 q, k, v = (self._ref_linear(L[n], A, SFA, L[n].scale) for n in ("q", "k", "v"))
-            if self.fused and q_len == 1 and hd == 128 and self.decode_attention == "stream":
+            if self.kv_cache == "int4":
+                att = self._attention_int4(li, q, k, v, qkv if self.fused else None, pos, bsz, q_len)
+            elif self.fused and q_len == 1 and hd == 128 and self.decode_attention == "stream":
                 att = self._attn_decode_stream(qkv, L, pos)          # K|V append + attention over [0, pos]: the harness's own kernel
             else:
                 att = self._attention_torch(L, q, k, v, qkv if self.fused else None, pos, bsz, q_len)
@@ -309,11 +326,13 @@ class DecoderModel:
         h, ke, hd = cfg.hidden_size, cfg.select_num, cfg.hidden_size // cfg.num_heads
         T = bsz * q_len
         hcur = F.embedding(tokens, self.embed).reshape(T, h)
-        for L in self.layers:
+        for li, L in enumerate(self.layers):
             A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln1"], cfg.eps, self.idx_h, ke)
             if self.fused:
                 qkv = L["qkv"].matmul(A, SFA, 1.0)
-                if q_len == 1 and hd == 128 and self.decode_attention == "stream":
+                if self.kv_cache == "int4":
+                    att = self._attention_int4(li, qkv[:, :h], qkv[:, h:2 * h], qkv[:, 2 * h:], qkv, pos, bsz, q_len)
+                elif q_len == 1 and hd == 128 and self.decode_attention == "stream":
                     att = self._attn_decode_stream(qkv, L, pos)
                 else:
                     att = self._attention_torch(L, qkv[:, :h], qkv[:, h:2 * h], qkv[:, 2 * h:], qkv, pos, bsz, q_len)
@@ -331,7 +350,8 @@ class DecoderModel:
                 hcur = L["down"].matmul(qa, sfa, 1.0, residual=hcur)
             else:
                 q, k, v = (self._ref_linear_mx(L[n], A, SFA) for n in ("q", "k", "v"))
-                att = self._attention_torch(L, q, k, v, None, pos, bsz, q_len)
+                att = (self._attention_int4(li, q, k, v, None, pos, bsz, q_len) if self.kv_cache == "int4" else
+                       self._attention_torch(L, q, k, v, None, pos, bsz, q_len))
                 qa, sfa = agemm.mx_reorder_quantize_x(att, self.idx_h, ke)
                 hcur = hcur + self._ref_linear_mx(L["o"], qa, sfa)
                 A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln2"], cfg.eps, self.idx_h, ke)
@@ -368,6 +388,35 @@ class DecoderModel:
                                                  v.reshape(bsz, q_len, nh, hd).transpose(1, 2), is_causal=q_len > 1)
         return att.transpose(1, 2).reshape(bsz * q_len, h)
 
+    def _attention_int4(self, li, q, k, v, qkv, pos, bsz, q_len):
+        """kv_cache="int4": layer ``li``'s K / V go into the int4 paged cache and a decode step attends over it (arcquant_amd.kvcache).
+        Prefill (q_len > 1, from position 0 only): init_kv_quantize_i4 writes the pages; the prompt's own causal attention is torch
+        SDPA over this call's k / v, as with the dense cache -- there is no prefill attention over int4 pages.  Decode:
+        append_kv_quantize_i4, then batch_decode_i4 over positions [0, pos], on the q, k and v slices of the projection output (one
+        transposing copy makes the three contiguous).  Harness glue around the operators, like the dense cache's kernel."""
+        cfg = self.cfg
+        nh, hd, h = cfg.num_heads, cfg.hidden_size // cfg.num_heads, cfg.hidden_size
+        if q_len > 1:
+            if pos != 0:
+                raise ValueError("DecoderModel(kv_cache='int4'): a multi-token call must start at position 0 (no prefill attention over the int4 pages)")
+            kk, vv = k.reshape(bsz * q_len, nh, hd).contiguous(), v.reshape(bsz * q_len, nh, hd).contiguous()
+            seqlens = torch.arange(bsz + 1, dtype=torch.int32, device=kk.device) * q_len
+            kvcache.init_kv_quantize_i4(**self.kvc.tables(q_len), k=kk, v=vv, seqlen_indptr=seqlens, layer_idx=li)
+            att = F.scaled_dot_product_attention(q.reshape(bsz, q_len, nh, hd).transpose(1, 2), kk.view(bsz, q_len, nh, hd).transpose(1, 2),
+                                                 vv.view(bsz, q_len, nh, hd).transpose(1, 2), is_causal=True)
+            return att.transpose(1, 2).reshape(bsz * q_len, h)
+        if qkv is not None:
+            qq, kk, vv = qkv.view(bsz, 3, nh, hd).transpose(0, 1).contiguous().unbind(0)
+        else:
+            qq, kk, vv = (t.reshape(bsz, nh, hd).contiguous() for t in (q, k, v))
+        tables = self.kvc.tables(pos + 1)
+        kvcache.append_kv_quantize_i4(**tables, k=kk, v=vv, layer_idx=li)
+        out = torch.empty_like(qq)
+        kvcache.batch_decode_i4(out, qq, **tables, layer_idx=li)
+        if self.kv_trace is not None:
+            self.kv_trace.append(dict(layer=li, pos=pos, q=qq.clone(), k=kk.clone(), v=vv.clone(), out=out.clone()))
+        return out.view(bsz, h)
+
     def _attn_decode_stream(self, qkv, L, pos):
         """One decode step of attention over the dense bf16 cache with the harness kernel (include/arcq_harness.h): appends this
         token's k / v at `pos` and attends over [0, pos] (attention="cache") or over the current token only ("current", what
@@ -394,7 +443,7 @@ class DecoderModel:
 
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
-                 attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False):
+                 attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False, kv_cache="bf16"):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
     weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
@@ -404,7 +453,7 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
     with torch.no_grad():
         mem0 = torch.cuda.memory_allocated(device)
         model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
-                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue)
+                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -448,6 +497,8 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         eager_ms = (time.perf_counter() - t0) / 4 * 1e3
         wb = model.weight_bytes()
         kv = 2 * cfg.num_layers * batch * cfg.hidden_size * pos * 2 if attention == "cache" else 0
+        if kv_cache == "int4":      # 64 bytes of codes + a 4-byte (scale, zero) pair per head and position
+            kv = 2 * cfg.num_layers * batch * cfg.num_heads * pos * 68
         assert out.shape == (batch, cfg.vocab_size)
     res = {"model": name, "fused": fused, "attention": attention, "layers": cfg.num_layers, "batch": batch, "prefill": prefill, "attn_window": pos,
            "decode_ms_per_step_graph": round(best, 4), "decode_tok_per_s": round(batch / best * 1e3, 1),
@@ -461,11 +512,14 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         res["quant_type"] = quant_type
     if mx_quantised_epilogue:
         res["mx_quantised_epilogue"] = True
+    if kv_cache != "bf16":
+        res["kv_cache"] = kv_cache
     return res
 
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
-                   fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False):
+                   fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False,
+                   kv_cache="bf16"):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -495,7 +549,7 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
 
     with torch.no_grad():
         model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
-                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue)
+                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache)
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -538,6 +592,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         res["quant_type"] = quant_type
     if mx_quantised_epilogue:
         res["mx_quantised_epilogue"] = True
+    if kv_cache != "bf16":
+        res["kv_cache"] = kv_cache
     return res
 
 
@@ -674,6 +730,13 @@ if __name__ == "__main__":
         if qt not in ("NVFP4", "MXFP4"):
             sys.exit("--quant-type takes NVFP4 or MXFP4")
         del argv[i:i + 2]
+    kvc = "bf16"
+    if "--kv-cache" in argv:          # --kv-cache {bf16,int4}: int4 = the reference's paged cache (attention over the whole cache only)
+        i = argv.index("--kv-cache")
+        kvc = argv[i + 1] if i + 1 < len(argv) else ""
+        if kvc not in ("bf16", "int4"):
+            sys.exit("--kv-cache takes bf16 or int4")
+        del argv[i:i + 2]
     args = [a for a in argv if not a.startswith("--")]
     name = args[0] if args else "qwen2.5-7b"
     ro = "--repacked-only" in sys.argv       # one weight copy per linear (the fused model only)
@@ -682,11 +745,12 @@ if __name__ == "__main__":
         sys.exit("--mx-quantised-epilogue needs --quant-type MXFP4")
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
-            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe)), flush=True)
+            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
-            if (ro or qe) and not fused:
+            if ((ro or qe) and not fused) or (kvc == "int4" and att != "cache"):
                 continue
-            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe)), flush=True)
+            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc)),
+                  flush=True)
             torch.cuda.empty_cache()

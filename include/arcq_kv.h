@@ -1,0 +1,80 @@
+/*
+ * arcq_kv.h -- the KV-cache half of the reference's operator module on gfx950: the paged cache writers and the decode attention
+ * behind `init_kv_*`, `append_kv_*` and `batch_decode_*` (kernels/src/bindings.cpp:287-581, kernels/src/flashinfer.cu,
+ * model/kv_cache.py).  Python mirror: arcquant_amd/kvcache.py.  Status codes and arcq_last_error() are those of arcq.h.
+ *
+ * FORMAT (the reference's, include/flashinfer/page.cuh:76-103), head dimension 128 only:
+ *   kv_data   ARCQ_KV_INT4: uint8 [pages, L, 2, N, P, 64]; byte j of a row holds element 2j in its low nibble and 2j+1 in its high one
+ *             ARCQ_KV_16BIT: 16-bit values [pages, L, 2, N, P, 128] (fp16 or bf16, see `dtype`)
+ *   kv_param  fp16 [pages, L, 2, N, P, 2] = (scale, zero); an int4 value is float(code) * float(scale) - float(zero) in fp32.
+ *             ARCQ_KV_16BIT stores the parameters and decode does not apply them (vec_dtypes.cuh:67-68).
+ *   index 2 is K then V, N kv heads, P entries per page (any P >= 1).
+ *   kv_indptr int32 [B + 1], kv_indices int32 [nnz], last_page_offset int32 [B]: sequence b owns the pages
+ *             kv_indices[kv_indptr[b] .. kv_indptr[b+1]) in order and holds
+ *             (kv_indptr[b+1] - kv_indptr[b] - 1) * P + last_page_offset[b] positions, the ones init / append write INCLUDED.
+ *
+ * THE CONTENTS OF THE INDEX TENSORS ARE THE CALLER'S CONTRACT, as in the reference: kv_indptr non-decreasing from 0 with
+ * kv_indptr[B] <= nnz, every kv_indices entry a page of kv_data, 1 <= last_page_offset[b] <= P for a non-empty sequence,
+ * seqlen_indptr non-decreasing from 0 with seqlen_indptr[B] <= ntok and no sequence appended to beyond its length.  They live on the
+ * device and are not read on the host; a call that breaks the contract reads or writes wherever the tables point.
+ *
+ * Every shape, NULL and alignment check runs before any HIP call.  B == 0 (and ntok == 0 for the init pair) returns ARCQ_OK.
+ * Alignment: kv_data, k, v, q, o 16 bytes; kv_param, k_param, v_param, the index tensors and the workspace 4 bytes.
+ * No entry point reads a byte of kv_data / kv_param outside the valid positions of the pages the tables name in layer `layer_idx`,
+ * and the writers change the rows they are asked to write and nothing else.
+ */
+#ifndef ARCQ_KV_H_
+#define ARCQ_KV_H_
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define ARCQ_KV_INT4 0  /* cache format: 4-bit codes + (scale, zero) */
+#define ARCQ_KV_16BIT 1 /* cache format: 16-bit values (the reference's `_f16` trio) */
+#define ARCQ_KV_F16 0   /* element dtype of q / o / k / v (and of an ARCQ_KV_16BIT cache): float16, the reference's */
+#define ARCQ_KV_BF16 1  /* bfloat16, the harness's */
+
+/* Prefill write (AppendPagedKVCachePrefillKernel): k, v = rows [ntok, N, 64 bytes | 128 x 16 bit], k_param, v_param = fp16 [ntok, N, 2].
+ * Tokens seqlen_indptr[b] .. seqlen_indptr[b+1] become the LAST positions of sequence b, in order. */
+int arcq_kv_init(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
+                 const void *k, const void *v, const void *k_param, const void *v_param, const int32_t *seqlen_indptr, int64_t ntok,
+                 int64_t B, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int format, void *stream);
+
+/* Decode write (AppendPagedKVCacheDecodeKernel): one token per sequence, k, v = rows [B, N, .], written at position seq_len - 1. */
+int arcq_kv_append(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
+                   const void *k, const void *v, const void *k_param, const void *v_param, int64_t B, int64_t L, int64_t layer_idx,
+                   int64_t N, int64_t P, int format, void *stream);
+
+/* arcq_kv_append with the quantiser in front, ONE launch (the reference: five torch launches per tensor, kv_cache.py:22-33, then
+ * append_kv_i4): k, v = `dtype` [B, N, 128].  Each (token, head) row is quantised as torch eager computes
+ *     scale = (amax - amin).clamp(min=1e-5) / 15;  zero = -amin;  code = clamp(round((x + zero) / scale), 0, 15)
+ * on a CPU tensor of `dtype` (every operation rounded to `dtype`, round half to even), parameters then converted to fp16; codes and
+ * parameters go straight into the page.  ARCQ_KV_INT4 only (ARCQ_KV_16BIT: ARCQ_ERR_UNSUPPORTED).  Inputs are finite. */
+int arcq_kv_append_quantize(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                            const int32_t *last_page_offset, const void *k, const void *v, int64_t B, int64_t L, int64_t layer_idx, int64_t N,
+                            int64_t P, int format, int dtype, void *stream);
+
+/* arcq_kv_init with the same quantiser in front: k, v = `dtype` [ntok, N, 128]. */
+int arcq_kv_init_quantize(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset,
+                          const void *k, const void *v, const int32_t *seqlen_indptr, int64_t ntok, int64_t B, int64_t L, int64_t layer_idx,
+                          int64_t N, int64_t P, int format, int dtype, void *stream);
+
+/* Bytes of fp32 scratch arcq_kv_batch_decode needs for this call (0: none, the workspace may be NULL).  nnz = entries of kv_indices. */
+int64_t arcq_kv_decode_workspace_bytes(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P);
+
+/* Decode attention: o, q = `dtype` [B, Nq, 128], Nq = g * N; query head h reads kv head h / g (g == 1 is the reference's contract),
+ * and the g query heads of a kv head share one pass over its rows.
+ *     o[b, h] = softmax_t(q[b, h] . K[t] / sqrt(128)) V[t]   over the positions of sequence b, no RoPE (flashinfer.cu:26-31),
+ * fp32 accumulation, rounded once to `dtype`.  A sequence without positions gives zeros.  nnz = entries of kv_indices: it sizes the
+ * slices, so pass what arcq_kv_decode_workspace_bytes was asked with; workspace_bytes >= that query's answer (0: workspace may be NULL). */
+int arcq_kv_batch_decode(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                         const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
+                         int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *workspace, int64_t workspace_bytes, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* ARCQ_KV_H_ */
