@@ -55,6 +55,17 @@ extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpre
 #define ARCQ_TILE_WIDE_STORES 1
 #endif
 
+// Where the 8-fragment hand-pipelined K step (k_step_pipe below) keeps its one barrier: kTileRot blocks of 8 MFMAs BEFORE the end of the
+// step, so that what follows the release is MFMAs on fragments already in registers.  -DARCQ_TILE_BARRIER_AT_STEP_END=1 builds the step as
+// it was (barrier last, the next step opening with its fragment reads) and -DARCQ_TILE_ROT=1|2|3 the other rotations: the arms of the A-B
+// and of the sweep recorded in DESIGN.md 3.2 (tools/scripts/build_variant_lib.sh).
+#ifndef ARCQ_TILE_BARRIER_AT_STEP_END
+#define ARCQ_TILE_BARRIER_AT_STEP_END 0
+#endif
+#ifndef ARCQ_TILE_ROT
+#define ARCQ_TILE_ROT 1
+#endif
+
 // kStagger (8-wave tiles): the two waves of a SIMD (w and w + 4) run half a step apart -- waves 0-3 multiply step k and
 // then stage step k+1, waves 4-7 stage step k+2 FIRST (into the buffer step k was just read from, after the barrier)
 // and then multiply step k+1 -- so that one wave's dequantise/ds_write phase overlaps the other's MFMA phase instead
@@ -233,6 +244,11 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
   // after issuing it (LDS latency exposed every 8 MFMAs) and clusters the dequantisation.  Here a step is cut into
   // TM blocks of [2 fragment reads for the NEXT block | 2 x TN MFMAs of this block | 1/TM of the staging work], fenced
   // with sched_barrier so that hipcc keeps the order; waits become counted lgkmcnt(N) on reads issued a block earlier.
+  constexpr int kRot = ARCQ_TILE_ROT;
+  // (the 256 x 256 8-wave tile alone: no partial staging pass, one A and one B unit per thread; the other tiles keep the barrier last)
+  constexpr bool kRotate = !ARCQ_TILE_BARRIER_AT_STEP_END && kPipe && !kMfma32 && TM == 8 && TN == 4 && WAVES_M * WAVES_N == 8 && !A_PARTIAL && !B_PARTIAL;
+  auto rd_frag = [&](const unsigned char* tile, int base, int ks, int i) { Frag8 f; f.u = *reinterpret_cast<const uint4*>(tile + (base ^ (ks * 64)) + i * 16 * kRowBytes); return f; };
+  [[maybe_unused]] Frag8 head_b[TN], head_a[2];   // kRotate: the fragments a step is entered with, carried across the loop's back-edge
   auto k_step_pipe = [&](int kt, unsigned char* ca, unsigned char* cb, unsigned char* na, unsigned char* nb) {
     static_assert(kMfma32 || TM % 2 == 0, "pairs of A fragments");
     Staged ta[A_UNITS], tb[B_UNITS];
@@ -290,8 +306,91 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
       __syncthreads();
       return;
     }
-    auto rd_a = [&](int ks, int i) { Frag8 f; f.u = *reinterpret_cast<const uint4*>(ca + (fa_base ^ (ks * 64)) + i * 16 * kRowBytes); return f; };
-    auto rd_b = [&](int ks, int j) { Frag8 f; f.u = *reinterpret_cast<const uint4*>(cb + (fb_base ^ (ks * 64)) + j * 16 * kRowBytes); return f; };
+    auto rd_a = [&](int ks, int i) { return rd_frag(ca, fa_base, ks, i); };
+    auto rd_b = [&](int ks, int j) { return rd_frag(cb, fb_base, ks, j); };
+    if constexpr (kRotate) {
+      // ROTATED step: the barrier sits kRot blocks before the end.  The step is entered with B's fragments of K half 0 and the first A pair
+      // in registers (head_b / head_a, read from this buffer behind the previous step's barrier).  Blocks 0 .. kLast multiply, stage ALL of
+      // step kt + 1 into (na, nb) and issue every remaining fragment read of (ca, cb); then lgkmcnt(0) + barrier: this wave has finished its
+      // reads of (ca, cb) and its writes of (na, nb).  Blocks kLast + 1 .. multiply fragments already held -- MFMAs are what follows the
+      // release -- and between them read step kt + 1's first fragments from (na, nb).  Same MFMAs, same order, same accumulators.
+      // Hazards by the barrier alone: (na, nb) is read only behind a barrier every writer reached with lgkmcnt(0); (ca, cb) is overwritten
+      // (next step, blocks 0 ..) only behind a barrier every reader reached with its reads retired.
+      constexpr int kQ = 2 * (TM / 2), kHalf = TM / 2, kLast = kQ - 1 - kRot, kNPre = kLast + 1;
+      static_assert(kRot >= 1 && kLast >= kHalf, "the second K half's B fragments are read ahead of the barrier, a block before their use");
+      // A pairs requested by the end of block b's read phase: one ahead, two per block over the last blocks so that pairs kLast + 2 .. are in
+      auto read_by = [](int b) { const int extra = b - (kLast - kRot), h = b + 1 + (extra > 0 ? extra : 0); return h < kQ - 1 ? h : kQ - 1; };
+      Frag8 fb1[TN], fq[kQ][2];
+      fq[0][0] = head_a[0];
+      fq[0][1] = head_a[1];
+#pragma unroll
+      for (int q = 0; q < kQ; ++q) {
+        const int ks = q / kHalf, pr = q % kHalf;
+        constexpr int kHeadReads = TN + 2;
+        int n_pieces = 0, n_reads = 0;
+        if (q <= kLast) {
+          // (1) reads for later blocks
+#pragma unroll
+          for (int r = (q ? read_by(q - 1) : 0) + 1; r <= read_by(q); ++r) {
+            fq[r][0] = rd_a(r / kHalf, 2 * (r % kHalf));
+            fq[r][1] = rd_a(r / kHalf, 2 * (r % kHalf) + 1);
+          }
+          if (q == kHalf - 1) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) fb1[j] = rd_b(1, j);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // (2) this block's MFMAs; weights are the MFMA A operand
+#pragma unroll
+        for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[2 * pr + ii][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16((ks ? fb1[j] : head_b[j]).v, fq[q][ii].v, acc[2 * pr + ii][j], 0, 0, 0);
+        if (q <= kLast) {
+          // (3) its share of the staging of step kt + 1: all kPieces over the blocks ahead of the barrier
+#pragma unroll
+          for (int c = 0; c < kPieces; ++c)
+            if (c * kNPre / kPieces == q) {
+              const int u = c >> 2, j = c & 3;
+              if (u < A_UNITS) {
+                stage_piece(na, a_slot[u][j], ta[u], a_live[u], j);
+              } else {
+                stage_piece(nb, b_slot[u - A_UNITS][j], tb[u - A_UNITS], b_live[u - A_UNITS], j);
+              }
+              ++n_pieces;
+            }
+        } else {
+          // (3') step kt + 1's first fragments, from the buffer the barrier has just published (the last step of a range reads bytes that
+          // were staged from the clamped atom and are never multiplied): B's K half 0, then the first A pair
+          const int i0 = q - kLast - 1;
+#pragma unroll
+          for (int n = i0 * kHeadReads / kRot; n < (i0 + 1) * kHeadReads / kRot; ++n) {
+            if (n < TN) head_b[n] = rd_frag(nb, fb_base, 0, n);
+            else head_a[n - TN] = rd_frag(na, fa_base, 0, n - TN);
+            ++n_reads;
+          }
+        }
+        // spacing: ahead of the barrier two vector instructions per staged piece in the shadow of every MFMA, behind it one fragment read
+#pragma unroll
+        for (int m8 = 0; m8 < 2 * TN; ++m8) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          if (q <= kLast) {
+            if (n_pieces == 1) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);          // (the builtin takes literal counts)
+            else if (n_pieces == 2) __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+            else if (n_pieces >= 3) __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+          } else if (m8 < n_reads) {
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (q == kLast) {
+          __syncthreads();
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      return;
+    }
     // fragment queue: A fragments are requested kAhead pairs before their MFMAs, the B set of the second K half during the
     // last pairs of the first
     constexpr int kPairs = TM / 2, kSeq = 2 * kPairs, kAhead = 1;   // 2 measured the same (1188-1202 vs 1193-1200) with 8 more registers
@@ -357,6 +456,12 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
     load_step(min(a_begin + 2, a_end - 1));
   }
   __syncthreads();
+  if constexpr (kRotate) {                      // the first step's head fragments
+#pragma unroll
+    for (int j = 0; j < TN; ++j) head_b[j] = rd_frag(lds_b0, fb_base, 0, j);
+    head_a[0] = rd_frag(lds_a0, fa_base, 0, 0);
+    head_a[1] = rd_frag(lds_a0, fa_base, 0, 1);
+  }
   int kt = a_begin;
   // alpha_dev is workgroup-uniform: a scalar load ahead of the loop, held in one SGPR across it (no tile's epilogue starts with a
   // vector-memory round trip); the product with alpha_host is formed after the loop, so that no VGPR is live through it
