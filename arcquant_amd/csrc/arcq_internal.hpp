@@ -159,5 +159,12 @@ struct KvDecodeArgs {
 };
 int kv_decode_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P);   // slices per sequence; > 1 needs the workspace
 int kv_decode(const KvDecodeArgs& a, hipStream_t stream);
+struct KvStepArgs {                        // what the decode step takes beside KvDecodeArgs (whose q is then strided too)
+  const void *k, *v;                       // 16-bit [B, N, 128], tokens kv_stride elements apart
+  int64_t q_stride, kv_stride;
+  void* state;                             // int32 [B * N * kv_decode_chunks], zero between launches
+};
+int64_t kv_decode_chunks(int64_t Nq, int64_t N);   // workgroups per (sequence, kv head): ceil(g / min(g, 4))
+int kv_decode_step(const KvDecodeArgs& a, const KvStepArgs& st, hipStream_t stream);
 
 }  // namespace arcq

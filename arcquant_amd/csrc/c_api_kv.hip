@@ -111,4 +111,43 @@ int arcq_kv_batch_decode(void* o, const void* q, const void* kv_data, const void
   return kv_decode(a, (hipStream_t)stream);
 }
 
+int64_t arcq_kv_decode_step_state_bytes(int64_t B, int64_t Nq, int64_t N) {
+  if (B <= 0 || Nq <= 0 || N <= 0 || Nq % N) return 0;
+  return B * N * kv_decode_chunks(Nq, N) * (int64_t)sizeof(int32_t);
+}
+
+int arcq_kv_decode_step(void* o, const void* q, const void* k, const void* v, int64_t q_stride, int64_t kv_stride, void* kv_data, void* kv_param,
+                        const int32_t* kv_indptr, const int32_t* kv_indices, const int32_t* last_page_offset, int64_t B, int64_t Nq, int64_t L,
+                        int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int format, int dtype, void* workspace, int64_t workspace_bytes,
+                        void* state, int64_t state_bytes, void* stream) {
+  const char* who = "arcq_kv_decode_step";
+  int rc = geometry(who, B, L, layer_idx, N, P, format);
+  if (rc != ARCQ_OK) return rc;
+  if ((rc = dtype_ok(who, dtype)) != ARCQ_OK) return rc;
+  if (Nq <= 0 || Nq % N || Nq > 65535)
+    return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (at most 65535)", who, (long long)Nq, (long long)N);
+  if (nnz < 0 || nnz > kMaxDim || nnz * P > INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: nnz=%lld pages of P=%lld entries are out of range", who, (long long)nnz, (long long)P);
+  if (B * Nq > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: B * Nq = %lld is out of range", who, (long long)(B * Nq));
+  if (format != ARCQ_KV_INT4) return fail(ARCQ_ERR_UNSUPPORTED, "%s: the decode step quantises into ARCQ_KV_INT4 caches only", who);
+  if (q_stride < Nq * 128 || kv_stride < N * 128 || q_stride % 8 || kv_stride % 8 || q_stride > kMaxDim || kv_stride > kMaxDim)
+    return fail(ARCQ_ERR_SHAPE, "%s: q_stride=%lld >= Nq * 128 = %lld and kv_stride=%lld >= N * 128 = %lld must be multiples of 8 elements", who,
+                (long long)q_stride, (long long)(Nq * 128), (long long)kv_stride, (long long)(N * 128));
+  if (B == 0) return ARCQ_OK;
+  if (!o || !q || !k || !v || !kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
+  if (misaligned(o, 16) || misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(kv_data, 16))
+    return fail(ARCQ_ERR_SHAPE, "%s: o, q, k, v and kv_data must be 16-byte aligned", who);
+  if (misaligned(kv_param, 4) || misaligned(kv_indptr, 4) || misaligned(kv_indices, 4) || misaligned(last_page_offset, 4) || misaligned(workspace, 4) ||
+      misaligned(state, 4))
+    return fail(ARCQ_ERR_SHAPE, "%s: kv_param, the index tensors, the workspace and the state must be 4-byte aligned", who);
+  const int64_t need = arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P);
+  if (need > 0 && (!workspace || workspace_bytes < need))
+    return fail(ARCQ_ERR_WORKSPACE, "%s: workspace of %lld bytes, need %lld (arcq_kv_decode_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
+  const int64_t need_state = arcq_kv_decode_step_state_bytes(B, Nq, N);
+  if (need > 0 && (!state || state_bytes < need_state))
+    return fail(ARCQ_ERR_WORKSPACE, "%s: state of %lld bytes, need %lld (arcq_kv_decode_step_state_bytes)", who, (long long)state_bytes, (long long)need_state);
+  KvDecodeArgs a{o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, B, Nq, L, layer_idx, N, P, nnz, format, dtype, workspace};
+  KvStepArgs st{k, v, q_stride, kv_stride, state};
+  return kv_decode_step(a, st, (hipStream_t)stream);
+}
+
 }  // extern "C"

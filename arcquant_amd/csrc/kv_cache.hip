@@ -15,8 +15,14 @@
 //                        sum_t p_t (c_td s_t - z_t) = sum_t (p_t s_t) c_td - sum_t p_t z_t:  one conversion and one FMA per code
 //                        and query head.  Online softmax per wave, the waves merge through LDS; S > 1 leaves (max, sum, 128
 //                        accumulators) records in the workspace for kv_decode_combine.  fp32 throughout.
-//   Rows past a wave's range are clamped to the sequence's last valid position and masked: no byte outside the valid positions of
-//   the pages the tables name is read.
+//   kv_decode_kernel<.., STEP>  the decode step in one launch (arcq_kv_decode_step): the same grid, ranges and arithmetic over strided
+//                        q / k / v rows of the projection output.  The wave whose range holds position T - 1 quantises k[b, n] and
+//                        v[b, n] (kv_quantize_row, the quantiser's own formula) in front of its last block and uses the codes in place
+//                        of the page's row; chunk 0's owner stores them.  With S > 1 every workgroup publishes its records (agent-scope
+//                        release) and draws a ticket from cnt[b, n, chunk]; the one that draws S - 1 acquires, merges the S records as
+//                        kv_decode_combine does, stores o and puts the counter back to 0.  Nobody waits for anybody.
+//   Rows past a wave's range are clamped to the sequence's last valid position (STEP: the one before it, which is in the page) and
+//   masked: no byte outside the valid positions of the pages the tables name is read.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -111,6 +117,40 @@ __global__ __launch_bounds__(256) void kv_write_kernel(KvWriteParams p) {
   }
 }
 
+// The quantiser of a row of 128 values held NE per lane by 128 / NE adjacent lanes (lane c: elements c * NE ..): this lane's codes, element
+// j in nibble j % 8 of word j / 8, and the row's fp16 (scale, zero) pair.  torch eager on a tensor of the input dtype: every operation's
+// result is rounded to that dtype (the Scalar 1e-5 too).
+template <bool BF16, int NE>
+__device__ __forceinline__ uint32_t kv_quantize_row(const float (&x)[NE], uint32_t (&codes)[NE / 8]) {
+  float xmax = x[0], xmin = x[0];
+#pragma unroll
+  for (int j = 1; j < NE; ++j) {
+    xmax = fmaxf(xmax, x[j]);
+    xmin = fminf(xmin, x[j]);
+  }
+#pragma unroll
+  for (int sh = kKvD / NE / 2; sh > 0; sh >>= 1) {
+    xmax = fmaxf(xmax, __shfl_xor(xmax, sh, 64));
+    xmin = fminf(xmin, __shfl_xor(xmin, sh, 64));
+  }
+  const float range = fmaxf(kv_round<BF16>(xmax - xmin), kv_round<BF16>(1e-5f));
+  const float scale = kv_round<BF16>(range / 15.0f);
+  const float zero = -xmin;
+#pragma unroll
+  for (int w = 0; w < NE / 8; ++w) {
+    uint32_t cw = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float a = kv_round<BF16>(x[w * 8 + j] + zero);
+      const float qv = kv_round<BF16>(a / scale);
+      const float rc = fminf(fmaxf(__builtin_rintf(qv), 0.0f), 15.0f);      // (NaN -- inf / inf of an overflowing fp16 range -- becomes code 0)
+      cw |= (uint32_t)rc << (4 * j);
+    }
+    codes[w] = cw;
+  }
+  return kv_from_f32<false>(scale) | (kv_from_f32<false>(zero) << 16);
+}
+
 // rows = (token, K | V, head); four rows per wave, 16 lanes x 8 values each
 template <bool BF16>
 __global__ __launch_bounds__(256) void kv_quantize_kernel(KvWriteParams p) {
@@ -131,32 +171,11 @@ __global__ __launch_bounds__(256) void kv_quantize_kernel(KvWriteParams p) {
     x[2 * j] = kv_to_f32<BF16>(w[j] & 0xffffu);
     x[2 * j + 1] = kv_to_f32<BF16>(w[j] >> 16);
   }
-  float xmax = x[0], xmin = x[0];
-#pragma unroll
-  for (int j = 1; j < 8; ++j) {
-    xmax = fmaxf(xmax, x[j]);
-    xmin = fminf(xmin, x[j]);
-  }
-#pragma unroll
-  for (int sh = 8; sh > 0; sh >>= 1) {
-    xmax = fmaxf(xmax, __shfl_xor(xmax, sh, 64));
-    xmin = fminf(xmin, __shfl_xor(xmin, sh, 64));
-  }
-  // torch eager on a tensor of the input dtype: every operation's result is rounded to that dtype (the Scalar 1e-5 too)
-  const float range = fmaxf(kv_round<BF16>(xmax - xmin), kv_round<BF16>(1e-5f));
-  const float scale = kv_round<BF16>(range / 15.0f);
-  const float zero = -xmin;
-  uint32_t codes = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float a = kv_round<BF16>(x[j] + zero);
-    const float qv = kv_round<BF16>(a / scale);
-    const float rc = fminf(fmaxf(__builtin_rintf(qv), 0.0f), 15.0f);      // (NaN -- inf / inf of an overflowing fp16 range -- becomes code 0)
-    codes |= (uint32_t)rc << (4 * j);
-  }
+  uint32_t codes[1];
+  const uint32_t param = kv_quantize_row<BF16, 8>(x, codes);
   const size_t row = kv_row(p.t, b, n, pos, p.L, p.layer, p.N, p.P) + (size_t)which * p.N * p.P;
-  *reinterpret_cast<uint32_t*>(p.data + row * 64 + c * 4) = codes;
-  if (c == 0) p.param[row] = kv_from_f32<false>(scale) | (kv_from_f32<false>(zero) << 16);
+  *reinterpret_cast<uint32_t*>(p.data + row * 64 + c * 4) = codes[0];
+  if (c == 0) p.param[row] = param;
 }
 
 // ---- decode attention
@@ -170,14 +189,45 @@ struct KvDecodeParams {
   int B, Nq, L, layer, N, P, S, g, chunks;
   float sm_scale;
 };
+// what the decode step takes on top (its own type, so the other instances keep their kernel arguments as they were): this token's k, v
+// rows [B, N, 128] (tokens kv_stride elements apart; q: q_stride) and the arrival counters
+struct KvStepParams : KvDecodeParams {
+  const uint16_t* k;
+  const uint16_t* v;
+  int32_t* cnt;             // [B * N * chunks], zero between launches
+  int64_t q_stride, kv_stride;
+};
+template <bool STEP>
+struct KvParamsOf { using type = KvDecodeParams; };
+template <>
+struct KvParamsOf<true> { using type = KvStepParams; };
 
 template <int EPL>
 struct KvRaw {
   uint32_t w[EPL == 16 ? 2 : 4];                       // 16 codes = 2 words, 8 16-bit values = 4 words
 };
 
-template <int FMT, bool BF16, int GC>
-__global__ __launch_bounds__(kKvWaves * 64) void kv_decode_kernel(KvDecodeParams p) {
+// The S slice records of one (sequence, query head) -> output element d: max over s, the sums in s order, one rounding.
+template <bool BF16>
+__device__ __forceinline__ uint16_t kv_merge_slices(const float* w, int S, int d) {
+  float M = kKvIdle;
+  for (int s = 0; s < S; ++s) M = fmaxf(M, w[s * kKvRec]);
+  float Ls = 0.f, a = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const float f = __expf(w[s * kKvRec] - M);
+    Ls += w[s * kKvRec + 1] * f;
+    a += w[s * kKvRec + 2 + d] * f;
+  }
+  return (uint16_t)kv_from_f32<BF16>(Ls > 0.f ? a / Ls : 0.f);
+}
+
+// STEP (int4 only) is the whole decode step in one launch: q, k, v are strided rows of the projection output, position T - 1 is taken from
+// k / v -- quantised by the wave whose range holds it, which uses the codes in place of the page's row and, in chunk 0, stores them -- and
+// the last workgroup of a (sequence, kv head, chunk) to arrive merges the S records.  No position T - 1 of the page is read: rows past a
+// wave's range clamp to T - 2, and a sequence of one position loads nothing.  No workgroup waits for another.
+template <int FMT, bool BF16, int GC, bool STEP = false>
+__global__ __launch_bounds__(kKvWaves * 64) void kv_decode_kernel(typename KvParamsOf<STEP>::type p) {
+  static_assert(!STEP || FMT == ARCQ_KV_INT4, "the decode step quantises into an int4 cache");
   constexpr bool I4 = FMT == ARCQ_KV_INT4;
   constexpr int EPL = I4 ? 16 : 8;                     // elements per lane
   constexpr int LPR = kKvD / EPL;                      // lanes per row: 8 | 16
@@ -202,7 +252,9 @@ __global__ __launch_bounds__(kKvWaves * 64) void kv_decode_kernel(KvDecodeParams
 #pragma unroll
   for (int gi = 0; gi < GC; ++gi) {
     const int h = n * p.g + min(ch * GC + gi, p.g - 1);
-    const uint16_t* qrow = reinterpret_cast<const uint16_t*>(p.q) + ((size_t)b * p.Nq + h) * kKvD + c * EPL;
+    size_t qoff = ((size_t)b * p.Nq + h) * kKvD;
+    if constexpr (STEP) qoff = (size_t)b * p.q_stride + (size_t)h * kKvD;
+    const uint16_t* qrow = reinterpret_cast<const uint16_t*>(p.q) + qoff + c * EPL;
     float acc = 0.f;
 #pragma unroll
     for (int e8 = 0; e8 < EPL / 8; ++e8) {
@@ -223,9 +275,19 @@ __global__ __launch_bounds__(kKvWaves * 64) void kv_decode_kernel(KvDecodeParams
 
   using Raw = KvRaw<EPL>;
   auto load_block = [&](int tb, Raw (&kk)[NL], Raw (&vv)[NL], uint32_t (&pk)[NL], uint32_t (&pv)[NL]) __attribute__((always_inline)) {
+    if constexpr (STEP) {
+      if (T == 1) {                                     // the new position alone: nothing of the page is read
+#pragma unroll
+        for (int u = 0; u < NL; ++u) {
+          kk[u].w[0] = 0; kk[u].w[1] = 0; vv[u].w[0] = 0; vv[u].w[1] = 0;
+          pk[u] = 0; pv[u] = 0;
+        }
+        return;
+      }
+    }
 #pragma unroll
     for (int u = 0; u < NL; ++u) {
-      const int t = min(tb + u * RPL + r, T - 1);       // past the range: the sequence's last valid row, masked below
+      const int t = min(tb + u * RPL + r, STEP ? T - 2 : T - 1);   // past the range: the sequence's last stored row, masked below
       const size_t row = kv_row(p.t, b, n, t, p.L, p.layer, p.N, p.P);
       const uint8_t* ka = p.data + row * ROWB + c * LANEB;
       const uint8_t* va = ka + vrows * ROWB;
@@ -314,15 +376,61 @@ __global__ __launch_bounds__(kKvWaves * 64) void kv_decode_kernel(KvDecodeParams
     }
   };
 
+  // STEP: the wave whose range ends at T owns position T - 1.  In front of its last block it quantises k[b, n] and v[b, n] and puts the
+  // codes and parameters where load_block's row T - 1 would be (that row holds T - 2's, or zeros); chunk 0's owner stores them.
+  const bool own = STEP && t0 < t1 && t1 == T;
+  auto new_row = [&](int tb, Raw (&kk)[NL], Raw (&vv)[NL], uint32_t (&pk)[NL], uint32_t (&pv)[NL]) __attribute__((always_inline)) {
+    if constexpr (STEP) {
+      if (own && tb + BP >= T) {
+        const int rel = T - 1 - tb, us = rel / RPL;
+        const bool mine = r == rel - us * RPL;
+        const size_t row = kv_row(p.t, b, n, T - 1, p.L, p.layer, p.N, p.P);
+        uint8_t* data = const_cast<uint8_t*>(p.data);
+        uint32_t* param = const_cast<uint32_t*>(p.param);
+        auto one = [&](const uint16_t* src, size_t dst, Raw (&cc)[NL], uint32_t (&pp)[NL]) __attribute__((always_inline)) {
+          const uint16_t* xr = src + (size_t)b * p.kv_stride + (size_t)n * kKvD + c * EPL;
+          float x[EPL];
+#pragma unroll
+          for (int e8 = 0; e8 < EPL / 8; ++e8) {
+            const uint4 d = *reinterpret_cast<const uint4*>(xr + e8 * 8);
+            const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              x[e8 * 8 + 2 * j] = kv_to_f32<BF16>(w[j] & 0xffffu);
+              x[e8 * 8 + 2 * j + 1] = kv_to_f32<BF16>(w[j] >> 16);
+            }
+          }
+          uint32_t cw[EPL / 8];
+          const uint32_t pw = kv_quantize_row<BF16, EPL>(x, cw);
+#pragma unroll
+          for (int u = 0; u < NL; ++u) {
+            const bool here = mine && u == us;
+            cc[u].w[0] = here ? cw[0] : cc[u].w[0];
+            cc[u].w[1] = here ? cw[1] : cc[u].w[1];
+            pp[u] = here ? pw : pp[u];
+          }
+          if (ch == 0 && mine) {
+            *reinterpret_cast<uint2*>(data + dst * ROWB + c * LANEB) = make_uint2(cw[0], cw[1]);
+            if (c == 0) param[dst] = pw;
+          }
+        };
+        one(p.k, row, kk, pk);
+        one(p.v, row + vrows, vv, pv);
+      }
+    }
+  };
+
   if (t0 < t1) {
     Raw k0[NL], v0[NL], k1[NL], v1[NL];
     uint32_t pk0[NL], pv0[NL], pk1[NL], pv1[NL];
     load_block(t0, k0, v0, pk0, pv0);
     for (int tb = t0; tb < t1; tb += 2 * BP) {         // two blocks per trip: the other buffer's loads stay in flight
       if (tb + BP < t1) load_block(tb + BP, k1, v1, pk1, pv1);
+      new_row(tb, k0, v0, pk0, pv0);
       consume(tb, k0, v0, pk0, pv0);
       if (tb + BP < t1) {
         if (tb + 2 * BP < t1) load_block(tb + 2 * BP, k0, v0, pk0, pv0);
+        new_row(tb + BP, k1, v1, pk1, pv1);
         consume(tb + BP, k1, v1, pk1, pv1);
       }
     }
@@ -375,22 +483,40 @@ __global__ __launch_bounds__(kKvWaves * 64) void kv_decode_kernel(KvDecodeParams
       }
     }
   }
+  if constexpr (STEP) {
+    if (p.S == 1) return;
+    // records out, then one ticket per workgroup; the workgroup that draws the last one merges.  rec is free again behind the barrier.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const int ticket = __hip_atomic_fetch_add(p.cnt + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const bool last = ticket == p.S - 1;
+      if (last) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      rec[0][0][0] = last ? 1.f : 0.f;
+    }
+    __syncthreads();                                    // two duties: "last" reaches every wave, and no wave loads a record before the acquire is complete
+    if (rec[0][0][0] == 0.f) return;
+    const int d = tid & (kKvD - 1);
+#pragma unroll
+    for (int gi = tid >> 7; gi < GC; gi += 2) {         // two query heads at a time
+      if (ch * GC + gi >= p.g) break;
+      const size_t bh = (size_t)b * p.Nq + n * p.g + ch * GC + gi;
+      reinterpret_cast<uint16_t*>(p.o)[bh * kKvD + d] = kv_merge_slices<BF16>(p.ws + bh * p.S * kKvRec, p.S, d);
+    }
+    if (tid == 0) __hip_atomic_store(p.cnt + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 template <bool BF16>
 __global__ __launch_bounds__(kKvD) void kv_decode_combine(KvDecodeParams p) {
   const size_t bh = blockIdx.x;
   const int d = threadIdx.x;
-  const float* w = p.ws + bh * p.S * kKvRec;
-  float M = kKvIdle;
-  for (int s = 0; s < p.S; ++s) M = fmaxf(M, w[s * kKvRec]);
-  float Ls = 0.f, a = 0.f;
-  for (int s = 0; s < p.S; ++s) {
-    const float f = __expf(w[s * kKvRec] - M);
-    Ls += w[s * kKvRec + 1] * f;
-    a += w[s * kKvRec + 2 + d] * f;
-  }
-  reinterpret_cast<uint16_t*>(p.o)[bh * kKvD + d] = (uint16_t)kv_from_f32<BF16>(Ls > 0.f ? a / Ls : 0.f);
+  reinterpret_cast<uint16_t*>(p.o)[bh * kKvD + d] = kv_merge_slices<BF16>(p.ws + bh * p.S * kKvRec, p.S, d);
 }
 
 // ---- launchers (arguments validated by c_api_kv.hip)
@@ -430,21 +556,49 @@ int kv_decode_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P) {
   int64_t S = (1024 + B * N * chunks - 1) / (B * N * chunks);
   const int64_t cap = avg / (32 * kKvWaves);
   if (S > cap) S = cap;
-  if (S > 32) S = 32;
+  if (S > 32) S = 32;                                   // (kvstep.DecodeStepState sizes its record scratch for this cap: _MAX_SLICES)
   return S < 1 ? 1 : (int)S;
 }
 
-int kv_decode(const KvDecodeArgs& a, hipStream_t stream) {
-  KvDecodeParams p;
+int64_t kv_decode_chunks(int64_t Nq, int64_t N) {
+  const int64_t g = Nq / N, gc = kv_group_chunk(g);
+  return (g + gc - 1) / gc;
+}
+
+template <typename Params>
+static Params kv_decode_params(const KvDecodeArgs& a) {
+  Params p{};
   p.o = a.o; p.q = a.q; p.data = (const uint8_t*)a.kv_data; p.param = (const uint32_t*)a.kv_param;
   p.t = {a.kv_indptr, a.kv_indices, a.last_page_offset};
   p.ws = (float*)a.workspace;
   p.B = (int)a.B; p.Nq = (int)a.Nq; p.L = (int)a.L; p.layer = (int)a.layer; p.N = (int)a.N; p.P = (int)a.P;
   p.g = (int)(a.Nq / a.N);
-  const int gc = kv_group_chunk(p.g);
-  p.chunks = (p.g + gc - 1) / gc;
+  p.chunks = (int)kv_decode_chunks(a.Nq, a.N);
   p.S = kv_decode_splits(a.B, a.Nq, a.N, a.nnz, a.P);
   p.sm_scale = 0.08838834764831845f;                    // 128^-0.5
+  return p;
+}
+
+int kv_decode_step(const KvDecodeArgs& a, const KvStepArgs& st, hipStream_t stream) {
+  KvStepParams p = kv_decode_params<KvStepParams>(a);
+  p.k = (const uint16_t*)st.k; p.v = (const uint16_t*)st.v; p.cnt = (int32_t*)st.state;
+  p.q_stride = st.q_stride; p.kv_stride = st.kv_stride;
+  const int gc = kv_group_chunk(p.g);
+  const dim3 grid((unsigned)(a.B * a.N * p.chunks), (unsigned)p.S), block(kKvWaves * 64);
+  const bool bf = a.dtype == ARCQ_KV_BF16;
+#define ARCQ_KV_LAUNCH(GC)                                                                                        \
+  do {                                                                                                            \
+    if (bf) hipLaunchKernelGGL((kv_decode_kernel<ARCQ_KV_INT4, true, GC, true>), grid, block, 0, stream, p);      \
+    else hipLaunchKernelGGL((kv_decode_kernel<ARCQ_KV_INT4, false, GC, true>), grid, block, 0, stream, p);        \
+  } while (0)
+  if (gc == 1) ARCQ_KV_LAUNCH(1); else if (gc == 2) ARCQ_KV_LAUNCH(2); else ARCQ_KV_LAUNCH(4);
+#undef ARCQ_KV_LAUNCH
+  return launched("arcq_kv_decode_step");
+}
+
+int kv_decode(const KvDecodeArgs& a, hipStream_t stream) {
+  KvDecodeParams p = kv_decode_params<KvDecodeParams>(a);
+  const int gc = kv_group_chunk(p.g);
   const dim3 grid((unsigned)(a.B * a.N * p.chunks), (unsigned)p.S), block(kKvWaves * 64);
   const bool bf = a.dtype == ARCQ_KV_BF16;
 #define ARCQ_KV_LAUNCH(FMT, GC)                                                                         \

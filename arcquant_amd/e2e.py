@@ -28,7 +28,7 @@ import time
 import torch
 import torch.nn.functional as F
 
-from . import agemm, kvcache, mx
+from . import agemm, kvcache, kvstep, mx
 
 
 @dataclasses.dataclass
@@ -119,7 +119,8 @@ class DecoderModel:
     kv_page_size = 16         # kv_cache="int4": positions per page (the reference's benchmark default)
 
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
-                 repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False, kv_cache: str = "bf16"):
+                 repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False, kv_cache: str = "bf16",
+                 kv_fused_step: bool = False):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
@@ -133,6 +134,8 @@ class DecoderModel:
             raise ValueError(f"DecoderModel: kv_cache must be 'bf16' or 'int4', got {kv_cache!r}")
         if kv_cache == "int4" and (attention != "cache" or cfg.hidden_size // cfg.num_heads != kvcache.HEAD_DIM):
             raise ValueError("DecoderModel: kv_cache='int4' needs attention='cache' and a head dimension of 128")
+        if kv_fused_step and kv_cache != "int4":
+            raise ValueError("DecoderModel: kv_fused_step=True needs kv_cache='int4' (the one-launch decode step is the int4 paged cache's)")
         if repacked_only and not fused:
             raise ValueError("DecoderModel: repacked_only=True needs fused=True (the unfused model is the reference's call structure)")
         if quant_type not in ("NVFP4", "MXFP4"):
@@ -147,7 +150,7 @@ class DecoderModel:
         self.cfg, self.device, self.batch, self.max_len, self.fused = cfg, device, batch, max_len, fused
         self.repacked_only = repacked_only
         self.attention = attention
-        self.kv_cache = kv_cache
+        self.kv_cache, self.kv_fused_step = kv_cache, kv_fused_step
         self.kv_trace = None      # a list: _attention_int4 appends (layer, pos, q, k, v, out) of every decode step to it (tests)
         # the down projection's quantiser as its GEMM's prologue: every CU then quantises the whole M x intermediate activation
         # itself, which only pays while that is small (measured: Qwen2.5-7B, 4 x 18944: slower than the separate launch)
@@ -197,6 +200,7 @@ class DecoderModel:
         self.one = torch.ones(1, dtype=torch.float32, device=device)
         # every layer's pages in one paged cache, with the page tables of every length built here -- before any graph capture
         self.kvc = kvcache.PagedKVCacheI4(batch, self.kv_page_size, max_len, device, cfg.num_layers, cfg.num_heads) if kv_cache == "int4" else None
+        self.kv_step_state = kvstep.DecodeStepState(batch, cfg.num_heads, cfg.num_heads, device) if kv_fused_step else None
 
     def weight_bytes(self):
         per_layer = sum(v.bytes() for v in self.layers[0].values() if isinstance(v, QLinear))
@@ -393,7 +397,8 @@ class DecoderModel:
         Prefill (q_len > 1, from position 0 only): init_kv_quantize_i4 writes the pages; the prompt's own causal attention is torch
         SDPA over this call's k / v, as with the dense cache -- there is no prefill attention over int4 pages.  Decode:
         append_kv_quantize_i4, then batch_decode_i4 over positions [0, pos], on the q, k and v slices of the projection output (one
-        transposing copy makes the three contiguous).  Harness glue around the operators, like the dense cache's kernel."""
+        transposing copy makes the three contiguous); with kv_fused_step the three become ONE kvstep.decode_step_i4 launch on views of
+        the projection output, bit for bit the same.  Harness glue around the operators, like the dense cache's kernel."""
         cfg = self.cfg
         nh, hd, h = cfg.num_heads, cfg.hidden_size // cfg.num_heads, cfg.hidden_size
         if q_len > 1:
@@ -405,14 +410,19 @@ class DecoderModel:
             att = F.scaled_dot_product_attention(q.reshape(bsz, q_len, nh, hd).transpose(1, 2), kk.view(bsz, q_len, nh, hd).transpose(1, 2),
                                                  vv.view(bsz, q_len, nh, hd).transpose(1, 2), is_causal=True)
             return att.transpose(1, 2).reshape(bsz * q_len, h)
-        if qkv is not None:
-            qq, kk, vv = qkv.view(bsz, 3, nh, hd).transpose(0, 1).contiguous().unbind(0)
-        else:
-            qq, kk, vv = (t.reshape(bsz, nh, hd).contiguous() for t in (q, k, v))
         tables = self.kvc.tables(pos + 1)
-        kvcache.append_kv_quantize_i4(**tables, k=kk, v=vv, layer_idx=li)
-        out = torch.empty_like(qq)
-        kvcache.batch_decode_i4(out, qq, **tables, layer_idx=li)
+        if self.kv_fused_step:      # one launch on views of the projection output (kvstep, DESIGN.md 11 "Decode step")
+            qq, kk, vv = (qkv.view(bsz, 3 * nh, hd).split(nh, dim=1) if qkv is not None else (t.reshape(bsz, nh, hd) for t in (q, k, v)))
+            out = torch.empty((bsz, nh, hd), dtype=qq.dtype, device=qq.device)
+            kvstep.decode_step_i4(out, qq, kk, vv, **tables, layer_idx=li, state=self.kv_step_state)
+        else:
+            if qkv is not None:
+                qq, kk, vv = qkv.view(bsz, 3, nh, hd).transpose(0, 1).contiguous().unbind(0)
+            else:
+                qq, kk, vv = (t.reshape(bsz, nh, hd).contiguous() for t in (q, k, v))
+            kvcache.append_kv_quantize_i4(**tables, k=kk, v=vv, layer_idx=li)
+            out = torch.empty_like(qq)
+            kvcache.batch_decode_i4(out, qq, **tables, layer_idx=li)
         if self.kv_trace is not None:
             self.kv_trace.append(dict(layer=li, pos=pos, q=qq.clone(), k=kk.clone(), v=vv.clone(), out=out.clone()))
         return out.view(bsz, h)
@@ -443,7 +453,8 @@ class DecoderModel:
 
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
-                 attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False, kv_cache="bf16"):
+                 attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False, kv_cache="bf16",
+                 kv_fused_step=False):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
     weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
@@ -453,7 +464,7 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
     with torch.no_grad():
         mem0 = torch.cuda.memory_allocated(device)
         model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
-                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache)
+                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -514,12 +525,14 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         res["mx_quantised_epilogue"] = True
     if kv_cache != "bf16":
         res["kv_cache"] = kv_cache
+    if kv_fused_step:
+        res["kv_fused_step"] = True
     return res
 
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
                    fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False,
-                   kv_cache="bf16"):
+                   kv_cache="bf16", kv_fused_step=False):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -549,7 +562,7 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
 
     with torch.no_grad():
         model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
-                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache)
+                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step)
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -594,6 +607,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         res["mx_quantised_epilogue"] = True
     if kv_cache != "bf16":
         res["kv_cache"] = kv_cache
+    if kv_fused_step:
+        res["kv_fused_step"] = True
     return res
 
 
@@ -739,18 +754,22 @@ if __name__ == "__main__":
         del argv[i:i + 2]
     args = [a for a in argv if not a.startswith("--")]
     name = args[0] if args else "qwen2.5-7b"
+    kfs = "--kv-fused-step" in sys.argv      # --kv-cache int4 only: the decode step's append + attention as one launch (kvstep)
+    if kfs and kvc != "int4":
+        sys.exit("--kv-fused-step needs --kv-cache int4")
     ro = "--repacked-only" in sys.argv       # one weight copy per linear (the fused model only)
     qe = "--mx-quantised-epilogue" in sys.argv   # MXFP4, the fused model only: the gate|up GEMM quantises the down projection's input
     if qe and qt != "MXFP4":
         sys.exit("--mx-quantised-epilogue needs --quant-type MXFP4")
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
-            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc)), flush=True)
+            print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
+                                            kv_fused_step=kfs)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
             if ((ro or qe) and not fused) or (kvc == "int4" and att != "cache"):
                 continue
-            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc)),
-                  flush=True)
+            print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
+                                          kv_fused_step=kfs)), flush=True)
             torch.cuda.empty_cache()

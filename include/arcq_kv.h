@@ -19,7 +19,7 @@
  * device and are not read on the host; a call that breaks the contract reads or writes wherever the tables point.
  *
  * Every shape, NULL and alignment check runs before any HIP call.  B == 0 (and ntok == 0 for the init pair) returns ARCQ_OK.
- * Alignment: kv_data, k, v, q, o 16 bytes; kv_param, k_param, v_param, the index tensors and the workspace 4 bytes.
+ * Alignment: kv_data, k, v, q, o 16 bytes; kv_param, k_param, v_param, the index tensors, the workspace and the state 4 bytes.
  * No entry point reads a byte of kv_data / kv_param outside the valid positions of the pages the tables name in layer `layer_idx`,
  * and the writers change the rows they are asked to write and nothing else.
  */
@@ -73,6 +73,24 @@ int64_t arcq_kv_decode_workspace_bytes(int64_t B, int64_t Nq, int64_t N, int64_t
 int arcq_kv_batch_decode(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
                          const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
                          int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Bytes of the decode step's state: one int32 arrival counter per (sequence, kv head, chunk of <= 4 of its g = Nq / N query heads). */
+int64_t arcq_kv_decode_step_state_bytes(int64_t B, int64_t Nq, int64_t N);
+
+/* The whole decode step of an ARCQ_KV_INT4 cache in ONE launch: arcq_kv_append_quantize of k, v followed by arcq_kv_batch_decode of q,
+ * bit for bit (pages, parameters and o), without the launches in between.  q = `dtype` rows [B, Nq, 128] and k, v = rows [B, N, 128] whose
+ * heads are contiguous and whose tokens lie q_stride / kv_stride ELEMENTS apart (>= Nq * 128 / N * 128, multiples of 8): the three may be
+ * slices of one [B, (Nq + 2 N) * 128] projection output.  o = `dtype` [B, Nq, 128], contiguous.  The tables describe the sequences
+ * INCLUDING the position being written, as for arcq_kv_append; that position is taken from k, v and the result does not depend on what
+ * the page held there.  An empty sequence writes nothing and gives zeros.  ARCQ_KV_16BIT: ARCQ_ERR_UNSUPPORTED.
+ * workspace: arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P) bytes of scratch, contents don't-care.
+ * state: arcq_kv_decode_step_state_bytes(B, Nq, N) bytes, 4-byte aligned.  The caller zero-fills it ONCE after allocation; every call
+ * whose kernel completes leaves it all zero, so it is reused without clearing.  Calls that share a state (or a workspace) are
+ * stream-ordered.  When the workspace query answers 0 neither is touched and both may be NULL.  No workgroup waits for another. */
+int arcq_kv_decode_step(void *o, const void *q, const void *k, const void *v, int64_t q_stride, int64_t kv_stride, void *kv_data,
+                        void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B,
+                        int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *workspace,
+                        int64_t workspace_bytes, void *state, int64_t state_bytes, void *stream);
 
 #ifdef __cplusplus
 }
