@@ -123,38 +123,57 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
   const int half_k = p.K >> 1, atoms_k = p.K >> 6;
   const int a_begin = split * p.atoms_per_split, a_end = min(atoms_k, a_begin + p.atoms_per_split);   // never empty
 
-  // ---- per-thread staging geometry (loop invariant)
-  const uint8_t* a_q[A_UNITS];
-  const uint8_t* a_sf[A_UNITS];
+  // ---- staging geometry (loop invariant): per operand two descriptors at the tile origin (workgroup-uniform: kernel arguments and
+  //      m0 / n0) and per unit two 32-bit lane offsets against it (gemm_tile_common.hpp).  Rows are clamped into the matrix, so a lane
+  //      offset is non-negative and spans at most BM - 1 / BN - 1 rows; the launcher refuses a K whose tile would not fit 32 bits.
+  static_assert((128 % BM == 0 || BM % 128 == 0) && (128 % BN == 0 || BN % 128 == 0) && BM % 32 == 0 && BN % 32 == 0,
+                "a tile lies inside one 128-row block of the scale layout or starts on one, and on a 32-row boundary: no row's scales precede the origin's");
+  // reference layout: the tile's rows [t0, t0 + rows) of codes, and of scale bytes from the tile origin to the end of its last 128-row block
+  auto ref_src = [&](const uint8_t* Q, const uint8_t* SF, int t0, int rows) {
+    const uint32_t blocks = (uint32_t)(((t0 + rows - 1) >> 7) - (t0 >> 7) + 1), lead = (uint32_t)sf_atom_offset(t0 & 127, 0, atoms_k);
+    return StageSrc{stage_rsrc(Q + (size_t)t0 * half_k, (uint32_t)rows * (uint32_t)half_k),
+                    stage_rsrc(SF + sf_atom_offset(t0, 0, atoms_k), blocks * (uint32_t)atoms_k * 512u - lead)};
+  };
+  const StageSrc a_src = ref_src(p.A, p.SFA, m0, min(p.M - m0, BM));
+  [[maybe_unused]] const int rw_tiles = ((p.K + 255) >> 8) * 2;      // kBRepacked: tiles of 128 K per block of 16 rows
+  const StageSrc b_src = [&] {
+    if constexpr (kBLayout == kBRepacked) {         // whole blocks of 16 rows (N is padded to 16 in RW / RSF)
+      const uint32_t blocks = (uint32_t)((min(p.N - n0, BN) + 15) >> 4);
+      return StageSrc{stage_rsrc(p.B + (size_t)(n0 >> 4) * rw_tiles * 1024, blocks * (uint32_t)rw_tiles * 1024u),
+                      stage_rsrc(p.SFB + (size_t)(n0 >> 4) * rw_tiles * 128, blocks * (uint32_t)rw_tiles * 128u)};
+    } else {
+      return ref_src(p.B, p.SFB, n0, min(p.N - n0, BN));
+    }
+  }();
+  uint32_t a_q[A_UNITS], a_sf[A_UNITS];
   uint32_t a_live[A_UNITS];
   int a_slot[A_UNITS][4];
 #pragma unroll
   for (int u = 0; u < A_UNITS; ++u) {
     const int unit = tid + u * kThreads, r = A_PARTIAL ? min(unit >> 1, BM - 1) : unit >> 1, h = unit & 1;
     const int row = m0 + r, rc = row < p.M ? row : p.M - 1;
-    a_q[u] = p.A + (size_t)rc * half_k + h * 16;
-    a_sf[u] = p.SFA + sf_atom_offset(rc, 0, atoms_k) + h * 2;
-    a_live[u] = row < p.M ? 0xffffu : 0u;
+    a_q[u] = (uint32_t)(rc - m0) * (uint32_t)half_k + h * 16;
+    a_sf[u] = (uint32_t)(sf_atom_offset(rc, 0, atoms_k) - sf_atom_offset(m0, 0, atoms_k)) + h * 2;
+    a_live[u] = row < p.M ? kSfLive : 0u;
 #pragma unroll
     for (int j = 0; j < 4; ++j) a_slot[u][j] = kMfma32 ? lds_slot32(r, h * 4 + j) : lds_slot(r, h * 4 + j);
   }
-  const uint8_t* b_q[B_UNITS];
-  const uint8_t* b_sf[B_UNITS];
+  uint32_t b_q[B_UNITS], b_sf[B_UNITS];
   uint32_t b_live[B_UNITS];
   int b_slot[B_UNITS][4];
 #pragma unroll
   for (int u = 0; u < B_UNITS; ++u) {
     const int unit = tid + u * kThreads, r = B_PARTIAL ? min(unit >> 1, BN - 1) : unit >> 1, h = unit & 1;
     const int row = n0 + r, rc = row < p.N ? row : p.N - 1;
-    if constexpr (kBLayout == kBRepacked) {         // the atom-independent terms of stage_load_rw
-      const int tiles = ((p.K + 255) >> 8) * 2;
-      b_q[u] = p.B + (size_t)(rc >> 4) * tiles * 1024 + h * 256 + (rc & 15) * 16;
-      b_sf[u] = p.SFB + (size_t)(rc >> 4) * tiles * 128 + h * 64 + (rc & 15) * 4;
+    if constexpr (kBLayout == kBRepacked) {         // the atom-independent terms of stage_step_rw's layout
+      const uint32_t rb = (uint32_t)((rc >> 4) - (n0 >> 4));
+      b_q[u] = rb * (uint32_t)rw_tiles * 1024u + h * 256 + (rc & 15) * 16;
+      b_sf[u] = rb * (uint32_t)rw_tiles * 128u + h * 64 + (rc & 15) * 4;
     } else {
-      b_q[u] = p.B + (size_t)rc * half_k + h * 16;
-      b_sf[u] = p.SFB + sf_atom_offset(rc, 0, atoms_k) + h * 2;
+      b_q[u] = (uint32_t)(rc - n0) * (uint32_t)half_k + h * 16;
+      b_sf[u] = (uint32_t)(sf_atom_offset(rc, 0, atoms_k) - sf_atom_offset(n0, 0, atoms_k)) + h * 2;
     }
-    b_live[u] = row < p.N ? 0xffffu : 0u;
+    b_live[u] = row < p.N ? kSfLive : 0u;
 #pragma unroll
     for (int j = 0; j < 4; ++j) b_slot[u][j] = kMfma32 ? lds_slot32(r, h * 4 + j) : lds_slot(r, h * 4 + j);
   }
@@ -172,10 +191,12 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
 
   Staged sa[A_UNITS], sb[B_UNITS];     // registers holding step kt+1 while step kt is multiplied
   auto load_step = [&](int atom) {
+    atom = __builtin_amdgcn_readfirstlane(atom);    // (uniform already unless kStagger shifts it by the wave's group: the step offsets are scalar operands)
+    const StageStep sa_step = stage_step(atom), sb_step = kBLayout == kBRepacked ? stage_step_rw(atom) : sa_step;
 #pragma unroll
-    for (int u = 0; u < A_UNITS; ++u) sa[u] = stage_load(a_q[u], a_sf[u], atom);
+    for (int u = 0; u < A_UNITS; ++u) sa[u] = stage_load(a_src, a_q[u], a_sf[u], sa_step);
 #pragma unroll
-    for (int u = 0; u < B_UNITS; ++u) sb[u] = kBLayout == kBRepacked ? stage_load_rw(b_q[u], b_sf[u], atom) : stage_load(b_q[u], b_sf[u], atom);
+    for (int u = 0; u < B_UNITS; ++u) sb[u] = stage_load(b_src, b_q[u], b_sf[u], sb_step);
   };
   auto store_step = [&](unsigned char* la, unsigned char* lb) {
 #pragma unroll
@@ -353,9 +374,13 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
           for (int c = 0; c < kPieces; ++c)
             if (c * kNPre / kPieces == q) {
               const int u = c >> 2, j = c & 3;
+              // (a unit's first piece pins its scale bytes to this block: left free, hipcc lifts the shifts that form the scale pair of
+              // BOTH units to the top of the step, four vector instructions and the wait for the scale loads ahead of the first MFMA)
               if (u < A_UNITS) {
+                if (j == 0) asm volatile("" : "+v"(ta[u].sf));
                 stage_piece(na, a_slot[u][j], ta[u], a_live[u], j);
               } else {
+                if (j == 0) asm volatile("" : "+v"(tb[u - A_UNITS].sf));
                 stage_piece(nb, b_slot[u - A_UNITS][j], tb[u - A_UNITS], b_live[u - A_UNITS], j);
               }
               ++n_pieces;
@@ -814,6 +839,10 @@ static int launch_tile(const GemmArgs& a, hipStream_t stream, bool allow_split =
       p.partial = reinterpret_cast<float*>(a.workspace);
     }
   }
+  // the staging loads address an operand's tile with 32-bit offsets: up to 256 rows of K / 2 code bytes, or 16 row blocks of the repacked
+  // weight (K rounded up to 256)
+  if (((int64_t)a.K + 255) / 256 * 256 * 128 > 0xffffffffll)
+    return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4 (tile): K = %lld: a tile's rows of an operand exceed 32-bit offsets", (long long)a.K);
   const size_t lds = 2 * (size_t)(BM + BN) * kRowBytes;
   constexpr bool kCanStagger = WAVES_M * WAVES_N == 8 && BM == 256 && BN == 256, kCanPipe = true;
   auto kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false, kBLayout>;

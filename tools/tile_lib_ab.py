@@ -10,9 +10,10 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# M, N, KQ, epilogue: "" plain, "silu" SiLU * up, "bias", "residual"      (the model shapes: down, gate|up, q|k|v with its bias, o with its residual)
+# M, N, KQ, epilogue: "" plain, "silu" SiLU * up, "bias", "residual"      (the model shapes: down, gate|up, q|k|v with its bias, o with its residual;
+# M = 1024: the 128 x 256 tile)
 SHAPES = [(4096, 4096, 4096, ""), (8192, 8192, 8192, ""), (4096, 3584, 18944, ""), (4096, 37888, 3584, "silu"), (4096, 10752, 3584, "bias"),
-          (4096, 3584, 3584, "residual")]
+          (4096, 3584, 3584, "residual"), (1024, 4096, 4096, "")]
 
 CODE = """
 import json, sys, torch
