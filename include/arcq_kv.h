@@ -12,6 +12,9 @@
  *   kv_indptr int32 [B + 1], kv_indices int32 [nnz], last_page_offset int32 [B]: sequence b owns the pages
  *             kv_indices[kv_indptr[b] .. kv_indptr[b+1]) in order and holds
  *             (kv_indptr[b+1] - kv_indptr[b] - 1) * P + last_page_offset[b] positions, the ones init / append write INCLUDED.
+ *             A sequence WITHOUT POSITIONS is one for which that count is <= 0.  Two spellings are supported and mean the same: no pages
+ *             (kv_indptr[b+1] == kv_indptr[b]) with last_page_offset[b] = 0, where the formula gives -P, and one page with
+ *             last_page_offset[b] = 0, where it gives 0.  Neither has a page entry read or written.
  *
  * THE CONTENTS OF THE INDEX TENSORS ARE THE CALLER'S CONTRACT, as in the reference: kv_indptr non-decreasing from 0 with
  * kv_indptr[B] <= nnz, every kv_indices entry a page of kv_data, 1 <= last_page_offset[b] <= P for a non-empty sequence,

@@ -128,6 +128,16 @@ def test_kv_quantising_writers(P, lens, dtype):
 
 # lengths that end mid-page, at a page's last slot and at a page's first; the last case splits the sequences (workspace + combine)
 DECODE = [(16, (1, 15, 16), N), (16, (17, 50, 32), N), (5, (6, 17, 10), N), (16, (600, 515), 1)]
+# the ragged batches of tests/kv_reference.CASES (ragged, odd, empty): a wave streams three or four blocks, and the clamped loads of the
+# last one are where a stray read would show; slices without work; a sequence of 1, of 2 and of no positions
+RAGGED = [(16, (1000, 1, 33, 2), 1), (16, (700, 1, 67), 1), (16, (1000, 0, 33, 0), 1)]
+# slices per sequence (kv_decode_splits), the same at every group width used here
+SLICES = {(1, 15, 16): 1, (17, 50, 32): 1, (6, 17, 10): 1, (600, 515): 4, (300, 260): 2, (1000, 1, 33, 2): 2, (700, 1, 67): 2, (1000, 0, 33, 0): 2}
+
+
+def expected_workspace_bytes(lens, Nq):
+    S = SLICES[tuple(lens)]
+    return 0 if S == 1 else len(lens) * Nq * S * 130 * 4
 
 
 @pytest.mark.parametrize("P,lens,n_heads", DECODE)
@@ -135,6 +145,19 @@ DECODE = [(16, (1, 15, 16), N), (16, (17, 50, 32), N), (5, (6, 17, 10), N), (16,
 @pytest.mark.parametrize("fmt,dtype", [(KV_INT4, F16), (KV_INT4, BF16), (KV_16BIT, F16), (KV_16BIT, BF16)], ids=["i4-f16", "i4-bf16", "16-f16", "16-bf16"])
 def test_kv_batch_decode_reads_valid_positions_only(P, lens, n_heads, g, fmt, dtype):
     """The output is bit-identical under all three poisons in every byte decode must not read."""
+    _decode_in_arenas(P, lens, n_heads, g, fmt, dtype)
+
+
+@pytest.mark.parametrize("P,lens,n_heads", RAGGED)
+@pytest.mark.parametrize("g", [2, 7])
+@pytest.mark.parametrize("fmt,dtype", [(KV_INT4, F16), (KV_INT4, BF16), (KV_16BIT, F16), (KV_16BIT, BF16)], ids=["i4-f16", "i4-bf16", "16-f16", "16-bf16"])
+def test_kv_batch_decode_of_ragged_batches_reads_valid_positions_only(P, lens, n_heads, g, fmt, dtype):
+    want = _decode_in_arenas(P, lens, n_heads, g, fmt, dtype)
+    for b, T in enumerate(lens):
+        assert T or not want["o"].view(len(lens), -1)[b].any(), "a sequence without positions gives zeros"
+
+
+def _decode_in_arenas(P, lens, n_heads, g, fmt, dtype):
     lib = _L()
     B, Nq, layer, code = len(lens), g * n_heads, 1, 0 if dtype is F16 else 1
     pages, tabs, tin = _tables(lens, P, 9)
@@ -156,7 +179,7 @@ def test_kv_batch_decode_reads_valid_positions_only(P, lens, n_heads, g, fmt, dt
     ins["param"] = In(param, 4, dont_care=_byte_mask(unread if fmt == KV_INT4 else np.ones_like(unread), 4))
     nnz = int(tabs[1].shape[0])
     ws_bytes = int(lib.arcq_kv_decode_workspace_bytes(B, Nq, n_heads, nnz, P))
-    assert (ws_bytes > 0) == (sum(lens) > 1000)
+    assert ws_bytes == expected_workspace_bytes(lens, Nq), "the slice count of this case changed"
     scratch = {"ws": Out((ws_bytes // 4,), torch.float32, 4)} if ws_bytes else {}
 
     def call(o):
@@ -164,3 +187,4 @@ def test_kv_batch_decode_reads_valid_positions_only(P, lens, n_heads, g, fmt, dt
                                         layer, n_heads, P, nnz, fmt, code, _p(o.get("ws")), ws_bytes, _stream())
     want = run_in_arenas(call, ins, {"o": Out((B, Nq, 128), dtype, 16)}, scratch, device=DEV)
     assert torch.isfinite(want["o"].view(dtype).float()).all()
+    return want

@@ -6,7 +6,11 @@ with a bound computed from the inputs:
 
 u = half an ulp of the output dtype (one rounding of the result); the second term is the worst-case fp32 dot-product error of a score
 (either algebraic form), carried through the softmax, plus the exp term.  For randn inputs it is ~1e-3 relative; a nibble, page or head
-mix-up is O(1).  A length-1 sequence must return the dequantised V row rounded once: exact equality."""
+mix-up is O(1).  A length-1 sequence must return the dequantised V row rounded once: exact equality.
+
+The decode cases include the ragged batches of tests/kv_reference.CASES (deep loops, idle slices, T = 1 | 2 under S > 1, sequences without
+positions, an over-provisioned table) at every group width, and inputs with controlled scores -- uniform, ramps and the range-edge probes
+-- for which one position too few, too many or misplaced is an O(1) error."""
 import functools
 
 import numpy as np
@@ -152,72 +156,163 @@ def test_quantising_writers_are_byte_exact(P, dtype):
 
 
 # ---- decode
+#   name: P, lens, kv heads, slices per sequence S (kv_decode_splits; asserted through arcq_kv_decode_workspace_bytes), and for the ragged
+#   cases of tests/kv_reference.py (what each reaches: there and DESIGN.md 11) empty_pages / pad of the tables
 DECODE_CASES = {
-    "p16a": (16, lens_for(16)[0], N), "p16b": (16, lens_for(16)[1], N), "p5a": (5, lens_for(5)[0], N), "p5b": (5, lens_for(5)[1], N),
-    "long": (16, (1100, 700), 1),           # B = 2, N = 1: every split-and-merge path (slices per sequence, waves per slice, the combine)
+    "p16a": dict(P=16, lens=lens_for(16)[0], N=N, S=1), "p16b": dict(P=16, lens=lens_for(16)[1], N=N, S=1),
+    "p5a": dict(P=5, lens=lens_for(5)[0], N=N, S=1), "p5b": dict(P=5, lens=lens_for(5)[1], N=N, S=1),
+    "long": dict(P=16, lens=(1100, 700), N=1, S=7),   # B = 2, N = 1: every split-and-merge path (slices per sequence, waves per slice, the combine)
+    **R.CASES,
 }
+GS = list(R.G_ALL)
+U = {F16: 2.0 ** -11, BF16: 2.0 ** -8}
+
+
+def _check_splits(B, Nq, n_heads, nnz, P, S):
+    from arcquant_amd import _lib
+    want = 0 if S == 1 else B * Nq * S * 130 * 4
+    assert _lib.lib().arcq_kv_decode_workspace_bytes(B, Nq, n_heads, nnz, P) == want, "the slice count of this case changed"
 
 
 @functools.lru_cache(maxsize=None)
-def _decode_case(case, fmt, dtype, g):
-    """Cache contents, q and the fp64 reference of one case, built once and shared (nothing below modifies them)."""
-    P, lens, n_heads = DECODE_CASES[case]
+def _decode_pages(case, fmt, dtype):
+    """Cache contents of one case (quantised randn * 3 rows), built once and shared by every g (nothing below modifies them)."""
+    spec = DECODE_CASES[case]
+    P, lens, n_heads = spec["P"], spec["lens"], spec["N"]
     layer = 1
-    pages, indptr, indices, last = R.make_tables(lens, P, seed=len(case) + P)
+    # the path a ragged case claims: blocks the busiest wave streams (the rest of the claims: tests/test_kv_reference.py, without a GPU)
+    assert "per" not in spec or R.blocks_per_wave(max(lens), spec["S"], 32) == spec["per"]
+    pages, indptr, indices, last = R.case_tables(spec, seed=len(case) + P)
     gen = torch.Generator().manual_seed(P + sum(lens))
     ntok = sum(lens)
     sl = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
     k, v = (torch.randn(ntok, n_heads, 128, generator=gen) * 3).to(dtype), (torch.randn(ntok, n_heads, 128, generator=gen) * 3).to(dtype)
-    q = torch.randn(len(lens), g * n_heads, 128, generator=gen).to(dtype)
     param = np.zeros((pages, L, 2, n_heads, P, 2), dtype=np.float16)
     param.view(np.uint8)[...] = SENTINEL
     if fmt == "i4":
         (kq, kp), (vq, vp) = R.quantize_i4(k), R.quantize_i4(v)
         data = np.full((pages, L, 2, n_heads, P, 64), SENTINEL, dtype=np.uint8)
         R.write_rows(data, param, indptr, indices, last, kq.numpy(), vq.numpy(), kp.numpy(), vp.numpy(), sl, layer)
-        ref, (spa, qa) = R.paged_attention_f64(q.double().numpy(), data, param, indptr, indices, last, layer, i4=True)
         data_t = _dev(data)
     else:
-        data64 = np.full((pages, L, 2, n_heads, P, 128), np.nan)
+        data = np.full((pages, L, 2, n_heads, P, 128), np.nan)
         ones = np.ones((ntok, n_heads, 2), dtype=np.float16)
-        R.write_rows(data64, param, indptr, indices, last, k.double().numpy(), v.double().numpy(), ones, ones, sl, layer)
-        ref, (spa, qa) = R.paged_attention_f64(q.double().numpy(), data64, param, indptr, indices, last, layer, i4=False)
-        data_t = torch.from_numpy(data64).to(dtype).to(DEV)              # (the unwritten rows stay NaN: reading one is loud)
-    return dict(P=P, lens=lens, layer=layer, data=data_t, param=_dev(param), indptr=_dev(indptr), indices=_dev(indices), last=_dev(last),
-                q=q.to(DEV), ref=ref, spa=spa, qa=qa, first_v=(v[0] if fmt != "i4" else None), np_tables=(indptr, indices, last),
-                np_data=(data if fmt == "i4" else None), np_param=param)
+        R.write_rows(data, param, indptr, indices, last, k.double().numpy(), v.double().numpy(), ones, ones, sl, layer)
+        data_t = torch.from_numpy(data).to(dtype).to(DEV)                # (the unwritten rows stay NaN: reading one is loud)
+    return dict(P=P, lens=lens, N=n_heads, S=spec["S"], layer=layer, data=data_t, param=_dev(param), indptr=_dev(indptr), indices=_dev(indices),
+                last=_dev(last), first_v=(v[0] if fmt != "i4" else None), np_tables=(indptr, indices, last), np_data=data, np_param=param,
+                gen_state=gen.get_state())
 
 
-@pytest.mark.parametrize("case", list(DECODE_CASES))
-@pytest.mark.parametrize("g", [1, 4])
-@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
-@pytest.mark.parametrize("fmt", ["i4", "16bit"])
-def test_batch_decode_within_the_fp32_bound(case, g, dtype, fmt):
+@functools.lru_cache(maxsize=None)
+def _decode_case(case, fmt, dtype, g):
+    """The pages of a case + q and the fp64 reference for g query heads per kv head."""
+    c = _decode_pages(case, fmt, dtype)
+    gen = torch.Generator()
+    gen.set_state(c["gen_state"])
+    q = torch.randn(len(c["lens"]), g * c["N"], 128, generator=gen).to(dtype)
+    ref, (spa, qa) = R.paged_attention_f64(q.double().numpy(), c["np_data"], c["np_param"], *c["np_tables"], c["layer"], i4=fmt == "i4")
+    return dict(c, q=q.to(DEV), ref=ref, spa=spa, qa=qa)
+
+
+def _decode(c, fmt, dtype):
     kv = _kv()
-    c = _decode_case(case, fmt, dtype, g)
+    B, Nq = c["q"].shape[:2]
+    _check_splits(B, Nq, c["N"], c["indices"].numel(), c["P"], c["S"])
     o = torch.full_like(c["q"], float("nan"))
     fn = kv.batch_decode_i4 if fmt == "i4" else kv.batch_decode_f16
     fn(o, c["q"], c["data"], c["param"], c["indptr"], c["indices"], c["last"], c["layer"])
+    return o
+
+
+def _ratio(got, c, u, n=0):
+    """max |got - ref| / bound; an element whose bound is 0 (a sequence without positions) must be exactly the reference's."""
+    err, bound = np.abs(got - c["ref"]), R.decode_bound(c["ref"], c["spa"], c["qa"], u, n)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(np.where(bound > 0, err / bound, np.where(err > 0, np.inf, 0.0)).max()), float(err.max())
+
+
+@pytest.mark.parametrize("case", list(DECODE_CASES))
+@pytest.mark.parametrize("g", GS)
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("fmt", ["i4", "16bit"])
+def test_batch_decode_within_the_fp32_bound(case, g, dtype, fmt):
+    c = _decode_case(case, fmt, dtype, g)
+    o = _decode(c, fmt, dtype)
     got = o.double().cpu().numpy()
-    u = 2.0 ** -11 if dtype is F16 else 2.0 ** -8
-    bound = R.decode_bound(c["ref"], c["spa"], c["qa"], u)
+    bound = R.decode_bound(c["ref"], c["spa"], c["qa"], U[dtype])
     err = np.abs(got - c["ref"])
-    worst = float((err / bound).max())
+    worst = _ratio(got, c, U[dtype])[0]
     print(f"{case} {fmt} {dtype} g={g}: max err/bound = {worst:.3f}, max |err| = {err.max():.3e}")
     assert np.isfinite(got).all()
     assert (err <= bound).all(), f"max err / bound = {worst}"
-    # a length-1 sequence: the dequantised V row (the 16-bit cache: the V row itself), rounded once
+    n_heads = c["N"]
     for b, T in enumerate(c["lens"]):
+        if T == 0:                                             # a sequence without positions: zeros (the bound is 0 there as well)
+            assert not o[b].cpu().view(torch.int16).any(), b
+        # a length-1 sequence: the dequantised V row (the 16-bit cache: the V row itself), rounded once
         if T != 1:
             continue
-        n_heads = DECODE_CASES[case][2]
         for h in range(g * n_heads):
             if fmt == "i4":
                 vr, vp = R.gather_rows(c["np_data"], c["np_param"], *c["np_tables"], c["layer"], b, h // g, 1)
                 want = torch.from_numpy(R.dequantize_f32(vr, vp)[0]).to(dtype)
             else:
-                want = c["first_v"][h // g] if b == 0 else None
+                vr, _ = R.gather_rows(c["np_data"], c["np_param"], *c["np_tables"], c["layer"], b, h // g, 1)
+                want = torch.from_numpy(vr[0]).to(dtype)
+                assert b != 0 or torch.equal(want, c["first_v"][h // g])
             assert torch.equal(o[b, h].cpu(), want), (b, h)
+
+
+def _upload(c, fmt, dtype):
+    data = _dev(c["data"]) if fmt == "i4" else torch.from_numpy(c["data"]).to(dtype).to(DEV)
+    indptr, indices, last = c["tables"]
+    return dict(P=c["P"], N=c["N"], S=c["S"], layer=c["layer"], data=data, param=_dev(c["param"]), indptr=_dev(indptr), indices=_dev(indices),
+                last=_dev(last), q=torch.from_numpy(c["q"]).to(dtype).to(DEV))
+
+
+@pytest.mark.parametrize("case", ["ragged", "odd", "single"])
+@pytest.mark.parametrize("profile", ["uniform", "ramp_up", "ramp_down"])
+@pytest.mark.parametrize("g", [2, 7])
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("fmt", ["i4", "16bit"])
+def test_batch_decode_controlled_scores(case, profile, g, dtype, fmt):
+    """The cache written from codes and (scale, zero) pairs (tests/kv_reference.profile_rows).  uniform: q = 0, every position weighs
+    1 / T and the bound is the rounding of o plus the accumulation term alone (kv_reference.accumulation_chain, derived from the kernel's
+    structure), so one position too few or too many is hundreds of bounds away (tests/test_kv_reference.py).  ramps: the scores rise
+    (every block raises the running maximum and rescales l, the zero sum and the accumulators) or fall (the far blocks underflow)."""
+    c = R.profile_case(case, profile, fmt == "i4", dtype, g)
+    assert torch.equal(torch.from_numpy(c["q"]).to(dtype).double(), torch.from_numpy(c["q"]))
+    got = _decode(_upload(c, fmt, dtype), fmt, dtype).double().cpu().numpy()
+    n = c["n"] if profile == "uniform" else 0
+    worst, err = _ratio(got, c, U[dtype], n)
+    print(f"{case} {profile} {fmt} {dtype} g={g}: max err/bound = {worst:.3f} (without the accumulation term: {_ratio(got, c, U[dtype])[0]:.3f}), "
+          f"max |err| = {err:.3e}")
+    assert np.isfinite(got).all()
+    assert worst <= 1.0, f"max err / bound = {worst}"
+
+
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+@pytest.mark.parametrize("fmt", ["i4", "16bit"])
+def test_batch_decode_range_edge_probes(dtype, fmt):
+    """One launch: ten sequences that name the same pages, seven query heads each, every (sequence, head) a spike at another position --
+    every multiple of the block, the position before each, 0, T - 2, T - 1 -- whose fp64 score leads by more than 30, so o is the
+    target's dequantised V row and a dropped, masked or misaddressed row at any wave-range or block edge is an O(1) error."""
+    c = R.probe_case(fmt == "i4", dtype)
+    assert R.spike_gap(c) >= 30.0
+    edges = set(R.wave_ranges(c["T"], c["S"], c["block"]).reshape(-1).tolist()) - {c["T"]}
+    targets = set(c["targets"].reshape(-1).tolist())
+    assert edges <= targets and {e - 1 for e in edges if e} <= targets and {0, c["T"] - 2, c["T"] - 1} <= targets
+    o = _decode(_upload(c, fmt, dtype), fmt, dtype)
+    got = o.double().cpu().numpy()
+    worst, err = _ratio(got, c, U[dtype])
+    want = torch.from_numpy(c["want"]).to(dtype)
+    exact = int((o.cpu().view(torch.int16) == want.view(torch.int16)).all(-1).sum())
+    print(f"probes {fmt} {dtype}: S = {c['S']}, max err/bound = {worst:.3f}, max |err| = {err:.3e}, {exact} of {want.shape[0] * want.shape[1]} rows "
+          f"equal the target's V row bit for bit")
+    assert np.abs(c["ref"] - c["want"]).max() < 1e-9
+    assert np.isfinite(got).all()
+    assert worst <= 1.0, f"max err / bound = {worst}"
 
 
 @pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])

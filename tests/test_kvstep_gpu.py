@@ -11,8 +11,12 @@ arcq_kv_decode_workspace_bytes, so a change of it is noticed here:
     idle  (300, 260)    S = 2   idle waves; the wave that owns T - 1 is not the last wave
     alone (257, 289)    S = 2   the owning wave's range is the new position alone: it reads nothing from the page
     long  (1100, 700)   S = 7
+    ragged odd five single empty empty1   the ragged batches of tests/kv_reference.CASES: a wave streams 3 - 5 blocks, so the new row lands
+                        in a buffer the loop has reloaded; T = 1 and T = 2 under S > 1; slices in which all four waves idle; sequences
+                        without positions (both spellings), for which the step writes nothing and gives zeros
 
-g = 7 gives two chunks of query heads per kv head, the second with three heads: only chunk 0 may write the row."""
+g = 7 gives two chunks of query heads per kv head, the second with three heads: only chunk 0 may write the row.  g = 2 is the two-head
+instantiation, g = 3 one chunk with a repeated, unstored head, g = 8 two full chunks."""
 import functools
 
 import numpy as np
@@ -27,11 +31,14 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F16, BF16 = torch.float16, torch.bfloat16
 L = 2
+RAGGED = ["ragged", "odd", "five", "single", "empty", "empty1"]
 CASES = {
     "p16a": (16, lens_for(16)[0], 2, 1), "p16b": (16, lens_for(16)[1], 2, 1), "p5a": (5, lens_for(5)[0], 2, 1), "p5b": (5, lens_for(5)[1], 2, 1),
     "idle": (16, (300, 260), 1, 2), "alone": (16, (257, 289), 1, 2), "long": (16, (1100, 700), 1, 7),
+    **{name: (R.CASES[name]["P"], R.CASES[name]["lens"], R.CASES[name]["N"], R.CASES[name]["S"])
+       for name in RAGGED},
 }
-GS = [1, 4, 7]
+GS = [1, 2, 3, 4, 7, 8]
 DTYPES = pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
 
 
@@ -41,12 +48,13 @@ def _mods():
 
 
 def _shorter(lens, P, indptr, indices):
-    """The tables of the same sequences one position shorter (a sequence of one position becomes empty)."""
-    lens0 = [n - 1 for n in lens]
-    cnt0 = [(n + P - 1) // P for n in lens0]
+    """The tables of the same sequences one position shorter (a sequence of one position becomes empty; one without positions stays as
+    it is spelled)."""
+    lens0 = [max(n - 1, 0) for n in lens]
+    cnt0 = [(n0 + P - 1) // P if n else int(indptr[b + 1] - indptr[b]) for b, (n, n0) in enumerate(zip(lens, lens0))]
     ip0 = np.concatenate([[0], np.cumsum(cnt0)]).astype(np.int32)
     idx0 = np.concatenate([indices[indptr[b]:indptr[b] + cnt0[b]] for b in range(len(lens))]).astype(np.int32)
-    last0 = np.array([n - (c - 1) * P for n, c in zip(lens0, cnt0)], dtype=np.int32)
+    last0 = np.array([n0 - (c - 1) * P if n else 0 for n, n0, c in zip(lens, lens0, cnt0)], dtype=np.int32)
     assert (R.seq_lens(ip0, last0, P) == np.asarray(lens0)).all()
     return lens0, ip0, idx0, last0
 
@@ -57,7 +65,7 @@ def _case(name, dtype):
     _, kv, _ = _mods()
     P, lens, n_heads, S = CASES[name]
     B = len(lens)
-    pages, indptr, indices, last = R.make_tables(lens, P, seed=len(name) + P)
+    pages, indptr, indices, last = R.make_tables(lens, P, seed=len(name) + P, empty_pages=R.CASES.get(name, {}).get("empty_pages", 0))
     lens0, ip0, idx0, last0 = _shorter(lens, P, indptr, indices)
     gen = torch.Generator().manual_seed(P + sum(lens))
     sl0 = np.concatenate([[0], np.cumsum(lens0)]).astype(np.int32)
@@ -135,7 +143,16 @@ def test_step_equals_the_chain_bit_for_bit(case, g, dtype):
     _same(_step(c, q, c["k"], c["v"], layer, sliced=True), want, "slices of one projection output")
 
 
-@pytest.mark.parametrize("case", ["p16a", "long"])
+def test_a_case_puts_the_new_row_on_a_reloaded_buffer():
+    """The owning wave's last block is its third or later in ragged, five and single: new_row patches a buffer the loop has refilled."""
+    for name in ("ragged", "five", "single"):
+        P, lens, _, S = CASES[name]
+        T = max(lens)
+        t0 = [a for a, b in R.wave_ranges(T, S, 32).reshape(-1, 2) if a < b and b == T][0]
+        assert (T - 1 - t0) // 32 >= 2, name
+
+
+@pytest.mark.parametrize("case", ["p16a", "long", "ragged", "odd", "empty", "empty1"])
 @pytest.mark.parametrize("g", GS)
 @DTYPES
 def test_step_against_the_references(case, g, dtype):
@@ -160,10 +177,13 @@ def test_step_against_the_references(case, g, dtype):
     got = o.view(dtype).double().numpy()
     bound = R.decode_bound(ref, spa, qa, 2.0 ** -11 if dtype is F16 else 2.0 ** -8)
     err = np.abs(got - ref)
-    print(f"{case} {dtype} g={g}: max err/bound = {float((err / bound).max()):.3f}, max |err| = {err.max():.3e}")
+    worst = float((err[bound > 0] / bound[bound > 0]).max())
+    print(f"{case} {dtype} g={g}: max err/bound = {worst:.3f}, max |err| = {err.max():.3e}")
     assert np.isfinite(got).all()
-    assert (err <= bound).all(), f"max err / bound = {float((err / bound).max())}"
+    assert (err <= bound).all(), f"max err / bound = {worst}"
     for b, T in enumerate(c["lens"]):
+        if T == 0:                                             # (the bound is 0 there: exact zeros)
+            assert not o[b].any(), b
         if T != 1:
             continue
         for h in range(g * n_heads):
@@ -177,12 +197,23 @@ def test_step_against_the_references(case, g, dtype):
 def test_state_is_handed_back_zeroed(g, dtype):
     """One DecodeStepState through three calls: all zero after each, a repeated call gives the same bits (the append is idempotent), and
     a call on another layer matches that layer's chain."""
+    _three_calls_on_one_state("long", g, dtype)
+
+
+@pytest.mark.parametrize("g", GS)
+@DTYPES
+def test_state_is_handed_back_zeroed_by_a_ragged_batch(g, dtype):
+    """The same with slices in which every wave idles and sequences of one and two positions: their workgroups draw tickets as well."""
+    _three_calls_on_one_state("ragged", g, dtype)
+
+
+def _three_calls_on_one_state(case, g, dtype):
     step = _mods()[2]
-    c = _case("long", dtype)
+    c = _case(case, dtype)
     _check_splits(c, g)
     q = _q(c, g, dtype)
     state = step.DecodeStepState(c["B"], g * c["N"], c["N"], DEV)
-    assert state.counters.numel() == c["B"] * c["N"] * (2 if g == 7 else 1)
+    assert state.counters.numel() == c["B"] * c["N"] * R.decode_chunks(g)
     data, param = c["data"].clone(), c["param"].clone()
     first = _step(c, q, c["k"], c["v"], 1, sliced=True, state=state, data=data, param=param)
     assert not state.counters.cpu().any(), "counters left non-zero"
@@ -195,7 +226,7 @@ def test_state_is_handed_back_zeroed(g, dtype):
     _same(third, _chain(c, q, c["v"], c["k"], 0), "third call, another layer")
 
 
-@pytest.mark.parametrize("case", ["p16a", "p5b", "alone", "long"])
+@pytest.mark.parametrize("case", ["p16a", "p5b", "alone", "long", "ragged", "odd"])
 @pytest.mark.parametrize("g", GS)
 @DTYPES
 def test_result_does_not_depend_on_the_old_row(case, g, dtype):
@@ -214,3 +245,32 @@ def test_result_does_not_depend_on_the_old_row(case, g, dtype):
     _same(runs[1], runs[0], "0xFF against 0x00")
     _same(runs[2], runs[0], "0x7F against 0x00")
     _same(runs[0], _chain(c, q, c["k"], c["v"], layer), "against the chain")
+
+
+@pytest.mark.parametrize("case", ["empty", "empty1"])
+@pytest.mark.parametrize("g", GS)
+@DTYPES
+def test_a_sequence_without_positions_is_left_alone(case, g, dtype):
+    """Sequences 1 and 3 hold nothing (no pages | one page, last_page_offset 0): their o rows are zero, the counters come back zero, and
+    the only bytes of the cache and the parameters that changed are the rows of position T - 1 of the other two, in the layer asked for."""
+    step = _mods()[2]
+    c = _case(case, dtype)
+    _check_splits(c, g)
+    assert c["lens"][1] == 0 and c["lens"][3] == 0 and c["S"] > 1
+    q, layer = _q(c, g, dtype), 1
+    state = step.DecodeStepState(c["B"], g * c["N"], c["N"], DEV)
+    o, data, param = _step(c, q, c["k"], c["v"], layer, sliced=True, state=state)
+    assert not state.counters.cpu().any(), "counters left non-zero"
+    assert not o[1].any() and not o[3].any() and o[0].any() and o[2].any()
+    indptr, indices, last = c["np_tables"]
+    touched = np.zeros(tuple(c["data"].shape[:5]), dtype=bool)
+    for b, T in enumerate(c["lens"]):
+        if T:
+            page, e = R.locate(indptr, indices, b, T - 1, c["P"])
+            touched[page, layer, :, :, e] = True
+    keep = torch.from_numpy(~touched)
+    assert torch.equal(data[keep], c["data"].cpu()[keep]), "kv_data changed outside the two new rows"
+    assert torch.equal(param[keep], _ints(c["param"])[keep]), "kv_param changed outside the two new rows"
+    for b in (1, 3):                                           # the page an empty sequence names (empty1) is untouched as a whole
+        for page in indices[indptr[b]:indptr[b + 1]]:
+            assert torch.equal(data[page], c["data"].cpu()[page]) and torch.equal(param[page], _ints(c["param"])[page])
