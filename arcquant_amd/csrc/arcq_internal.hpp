@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/arcq.h"
 
@@ -10,15 +11,42 @@ namespace arcq {
 // Records a formatted message for arcq_last_error() (thread-local) and returns `code`.
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
-// Opt-in to more than 48 KB of dynamic LDS for `kernel` on the CURRENT device.  The attribute is per device and per
-// kernel, and the driver call costs host time, so each launcher keeps one LdsOptIn per kernel instantiation: a small
-// per-device table of the largest size already granted (relaxed atomics: two threads racing both make the same,
+// A tuning knob: the integer value of environment variable `name`, or `dflt` when it is unset.  Callers keep the result in a
+// function-local static, so each knob is read once per process.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// Opt-in to more than 48 KB of dynamic LDS for `kernel` on the CURRENT device (returns at once for less).  The attribute is per
+// device and per kernel, and the driver call costs host time, so launch_kernel keeps one LdsOptIn per kernel instantiation: a
+// small per-device table of the largest size already granted (relaxed atomics: two threads racing both make the same,
 // idempotent driver call).  Returns ARCQ_OK or ARCQ_ERR_LAUNCH (message recorded).
 constexpr int kMaxDevices = 64;
 struct LdsOptIn {
   int granted[kMaxDevices];     // zero-initialised (static storage)
 };
 int ensure_dynamic_lds(const void* kernel, LdsOptIn& cache, int bytes, const char* who);
+
+// Dynamic LDS of a launch.  `optin` is what the kernel is opted in for: the launch's own size, or the largest size the
+// instantiation can ever need (one driver call per device, ever).
+struct LdsBytes {
+  int launch, optin;
+  LdsBytes(int bytes) : launch(bytes), optin(bytes) {}
+  LdsBytes(int bytes, int most) : launch(bytes), optin(most) {}
+};
+
+// The one way a kernel of this library is launched: LDS opt-in, launch, error check.  The kernel is a template argument, so the
+// opt-in record is per kernel instantiation by construction.  Returns ARCQ_OK or ARCQ_ERR_LAUNCH ("<who>: launch failed: ...").
+template <auto Kernel, typename... Args>
+int launch_kernel(dim3 grid, dim3 block, LdsBytes lds, hipStream_t stream, const char* who, const Args&... args) {
+  static LdsOptIn opted;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(Kernel), opted, lds.optin, who)) return rc;
+  hipLaunchKernelGGL(Kernel, grid, block, lds.launch, stream, args...);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
+  return ARCQ_OK;
+}
 
 // c_api.hip: the argument checks of a GEMM-shaped entry point (host only), parameterised by what differs between entry points.
 struct GemmRule {
@@ -85,6 +113,14 @@ struct GemmArgs {
   unsigned int* absmax_slots = nullptr;   // kEpiSiluMul: one max|D| word per workgroup / tile (see gemm_silu_slots)
   int b_layout = 0;                  // kBRef: B / SFB in the reference layout; kBRepacked: B / SFB = RW / RSF of arcq.h (tile, regtile)
 };
+// The GemmArgs fields that every GEMM kernel's parameter block carries under the same names.  The weight operand stays with the
+// caller: B / SFB in some blocks, RW / RSF in others.
+template <typename Params>
+void copy_gemm_fields(Params& p, const GemmArgs& a) {
+  p.A = a.A; p.SFA = a.SFA; p.D = a.D;
+  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual;
+  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
+}
 enum : int { kEpiPlain = 0, kEpiSiluMul = 1 };
 enum : int { kBRef = 0, kBRepacked = 1 };
 int64_t gemm_silu_slots(int64_t M, int64_t N, int64_t K);   // slots the silu-mul epilogue of this shape writes

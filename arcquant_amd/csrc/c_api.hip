@@ -145,7 +145,7 @@ int arcq_absmax_scale(const void* X, int64_t n, float* scale_out, void* stream) 
 // N=4096 7.3 vs 9.3, N=5120 9.2 vs 8.5, N=8192 10.2 vs 9.5, N=14336 16.0 vs 14.6, N=37888 28.7 vs 23.9.
 // ARCQ_DECODE=1|2 forces the 16-row / 32-row kernel (tuning).
 static bool use_decode_v2(int64_t N) {
-  static const int forced = getenv("ARCQ_DECODE") ? atoi(getenv("ARCQ_DECODE")) : 0;
+  static const int forced = env_int("ARCQ_DECODE", 0);
   if (forced == 1) return false;
   if (forced == 2) return true;
   return ((N + 127) / 128) * 4 >= 160;

@@ -318,7 +318,7 @@ static void decode_split(int64_t N, int64_t K, int* splitk, int* slabs_per_split
   if ((N % 4) == 0) {
     while (tiles * s < 192 && nslabs / (s * 2) >= 8 && s < 16) s *= 2;
   }
-  static const int forced = getenv("ARCQ_DECODE_SPLIT") ? atoi(getenv("ARCQ_DECODE_SPLIT")) : 0;   // tuning only
+  static const int forced = env_int("ARCQ_DECODE_SPLIT", 0);   // tuning only
   if (forced > 0 && (N % 4) == 0) s = forced < nslabs ? forced : nslabs;
   const int per = (nslabs + s - 1) / s;
   *splitk = (nslabs + per - 1) / per;          // drop empty splits
@@ -333,18 +333,19 @@ int64_t gemm_decode_workspace_bytes(int64_t M, int64_t N, int64_t K) {
 
 template <int kADw, int kEpi>
 static int launch_decode(const DecodeParams& p, int splitk, hipStream_t stream) {
-  static LdsOptIn lds_opt;             // per kernel instantiation, per device
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm_decode_kernel<kADw, kEpi>), lds_opt, decode_lds_bytes(4 * kADw),
-                                  "arcq_gemm_nvfp4 (decode)"))
-    return rc;
   // persistent workgroups, each walks tiles blockIdx.x, +grid, ...: two 8-wave groups per CU while their LDS fits
-  static const int forced_grid = getenv("ARCQ_DECODE_GRID") ? atoi(getenv("ARCQ_DECODE_GRID")) : 0;
+  static const int forced_grid = env_int("ARCQ_DECODE_GRID", 0);
   const int per_cu = 2 * decode_lds_bytes(p.M) <= 160 * 1024 ? 2 : 1;
   const int max_wg = forced_grid > 0 ? forced_grid : 256 * per_cu;
   const int per_split = max_wg / splitk > 0 ? max_wg / splitk : 1;
   const int gx = p.tiles < per_split ? p.tiles : per_split;
-  hipLaunchKernelGGL((gemm_decode_kernel<kADw, kEpi>), dim3((unsigned)gx, (unsigned)splitk), dim3(kDecThreads), decode_lds_bytes(p.M), stream, p);
-  return ARCQ_OK;
+  // opted in once for the largest M the instantiation takes, not per M
+  return launch_kernel<gemm_decode_kernel<kADw, kEpi>>(dim3((unsigned)gx, (unsigned)splitk), dim3(kDecThreads), {decode_lds_bytes(p.M), decode_lds_bytes(4 * kADw)},
+                                                       stream, "arcq_gemm_nvfp4 (decode)", p);
+}
+template <int kEpi>
+static int launch_decode_epi(const DecodeParams& p, int splitk, hipStream_t stream) {
+  return p.M <= 4 ? launch_decode<1, kEpi>(p, splitk, stream) : p.M <= 8 ? launch_decode<2, kEpi>(p, splitk, stream) : launch_decode<4, kEpi>(p, splitk, stream);
 }
 
 int64_t gemm_decode_silu_slots(int64_t M, int64_t N, int64_t K) {
@@ -360,10 +361,9 @@ int gemm_decode(const GemmArgs& a, hipStream_t stream) {
     per = (int)((a.K + kDecSlabK - 1) / kDecSlabK);
   }
   DecodeParams p;
-  p.A = a.A; p.B = a.B; p.SFA = a.SFA; p.SFB = a.SFB; p.D = a.D;
+  copy_gemm_fields(p, a);
+  p.B = a.B; p.SFB = a.SFB;
   p.partial = reinterpret_cast<float*>(a.workspace);
-  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
   p.tiles = ((a.N + 127) / 128) * 4;
   p.slabs_per_split = per;
   p.epi = a.epilogue; p.slots = a.absmax_slots;
@@ -375,16 +375,8 @@ int gemm_decode(const GemmArgs& a, hipStream_t stream) {
   }
   if ((int64_t)a.N * (a.K / 2) >= ((int64_t)1 << 32) || (int64_t)((a.N + 127) / 128) * 128 * (a.K / 16) >= ((int64_t)1 << 32))
     return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4 (decode): operand larger than 4 GiB");
-  int rc;
-  if (a.epilogue == kEpiSiluMul)
-    rc = a.M <= 4 ? launch_decode<1, kEpiSiluMul>(p, splitk, stream)
-                  : a.M <= 8 ? launch_decode<2, kEpiSiluMul>(p, splitk, stream) : launch_decode<4, kEpiSiluMul>(p, splitk, stream);
-  else
-    rc = a.M <= 4 ? launch_decode<1, kEpiPlain>(p, splitk, stream)
-                  : a.M <= 8 ? launch_decode<2, kEpiPlain>(p, splitk, stream) : launch_decode<4, kEpiPlain>(p, splitk, stream);
+  const int rc = a.epilogue == kEpiSiluMul ? launch_decode_epi<kEpiSiluMul>(p, splitk, stream) : launch_decode_epi<kEpiPlain>(p, splitk, stream);
   if (rc != ARCQ_OK) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4 (decode): launch failed: %s", hipGetErrorString(e));
   if (splitk > 1) return gemm_splitk_finish(a, splitk, stream);
   return ARCQ_OK;
 }

@@ -432,16 +432,12 @@ __global__ __launch_bounds__(64 * kMxSmallWaves) void mx_slice_quant_kernel(MxAr
 template <int kEpi>
 static int mx_launch_gemm(const MxArgs& p, const char* who, hipStream_t stream) {
   if (p.M <= kMxSmallM) {
-    if constexpr (kEpi == kEpiSiluMulQuant)
-      hipLaunchKernelGGL(mx_slice_quant_kernel, dim3((unsigned)(p.N / kMxSliceCols), (unsigned)((p.M + 15) / 16)), dim3(64 * kMxSmallWaves), 0, stream, p);
-    else
-      hipLaunchKernelGGL(mx_small_kernel<kEpi>, dim3((unsigned)(p.N / 16), (unsigned)((p.M + 15) / 16)), dim3(64 * kMxSmallWaves), 0, stream, p);
-  } else
-    hipLaunchKernelGGL(mx_tile_kernel<kEpi>, dim3((unsigned)((p.N + kMxTile - 1) / kMxTile), (unsigned)((p.M + kMxTile - 1) / kMxTile)), dim3(256), 0,
-                       stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return ARCQ_OK;
+    const dim3 block(64 * kMxSmallWaves);
+    const unsigned rows16 = (unsigned)((p.M + 15) / 16);
+    if constexpr (kEpi == kEpiSiluMulQuant) return launch_kernel<mx_slice_quant_kernel>(dim3((unsigned)(p.N / kMxSliceCols), rows16), block, 0, stream, who, p);
+    else return launch_kernel<mx_small_kernel<kEpi>>(dim3((unsigned)(p.N / 16), rows16), block, 0, stream, who, p);
+  }
+  return launch_kernel<mx_tile_kernel<kEpi>>(dim3((unsigned)((p.N + kMxTile - 1) / kMxTile), (unsigned)((p.M + kMxTile - 1) / kMxTile)), dim3(256), 0, stream, who, p);
 }
 
 int gemm_mx(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t Kp,

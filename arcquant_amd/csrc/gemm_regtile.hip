@@ -378,16 +378,15 @@ static constexpr RegCfg kRegCfgs[] = {{1, 64, 64, 8, 4, 4}, {2, 64, 128, 4, 4, 4
                                       {12, 32, 16, 8, 2, 1}, {13, 64, 16, 8, 4, 1}};
 
 static int regtile_override() {              // ARCQ_REGTILE_CFG: 0 = by shape, -1 = never (the tiled kernel), n = forced configuration
-  static const int v = getenv("ARCQ_REGTILE_CFG") ? atoi(getenv("ARCQ_REGTILE_CFG")) : 0;
+  static const int v = env_int("ARCQ_REGTILE_CFG", 0);
   return v;
 }
 
 template <int TM, int TN, int WAVES_M, int WAVES_N, int KSPLIT, int kBLayout>
 static int launch_regtile(const GemmArgs& a, hipStream_t stream) {
   RegTileParams p;
-  p.A = a.A; p.B = a.B; p.SFA = a.SFA; p.SFB = a.SFB; p.D = a.D;
-  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
+  copy_gemm_fields(p, a);
+  p.B = a.B; p.SFB = a.SFB;
   constexpr int BM = 16 * TM * WAVES_M, BN = 16 * TN * WAVES_N, kWaves = WAVES_M * WAVES_N * KSPLIT;
   p.tiles_m = (a.M + BM - 1) / BM;
   p.tiles_n = (a.N + BN - 1) / BN;
@@ -395,14 +394,8 @@ static int launch_regtile(const GemmArgs& a, hipStream_t stream) {
   p.stamps = g_regtile_stamps;
 #endif
   const int lds = KSPLIT > 1 ? kWaves * TM * TN * 64 * 16 : 0;
-  auto kern = gemm_regtile_kernel<TM, TN, WAVES_M, WAVES_N, KSPLIT, kBLayout>;
-  static LdsOptIn lds_opt;
-  if (lds > 0)
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_opt, lds, "arcq_gemm_nvfp4 (regtile)")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(kWaves * 64), lds, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4 (regtile): launch failed: %s", hipGetErrorString(e));
-  return ARCQ_OK;
+  return launch_kernel<gemm_regtile_kernel<TM, TN, WAVES_M, WAVES_N, KSPLIT, kBLayout>>(dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(kWaves * 64), lds, stream,
+                                                                                        "arcq_gemm_nvfp4 (regtile)", p);
 }
 
 // 0 = the tiled kernel serves this shape, else the configuration: the SMALLEST tile whose grid is one round of the chip (<= 256 workgroups;

@@ -392,8 +392,26 @@ static bool rowblock_use_direct(int M, int N, int64_t K) {
   return w >= ((int64_t)8 << 20) && w <= ((int64_t)24 << 20);
 }
 
+static const char* const kRbWho = "arcq_gemm_nvfp4_repacked";
+static dim3 rowblock_grid(const RowblockParams& p) {
+  const int bpw = kRbWaves / p.slices;
+  return dim3((unsigned)((p.row_blocks + bpw - 1) / bpw));
+}
+
+// the image-filling kernels: one arm per kUnits = 16-byte units of the image that a thread fills
+template <bool kSilu>
+static int launch_rowblock(const RowblockParams& p, int lds, hipStream_t stream) {
+  const dim3 grid = rowblock_grid(p), block(kRbThreads);
+  const int units = p.M * p.pairs * 8;
+  const int per_thread = (units + kRbThreads - 1) / kRbThreads;
+  if (per_thread <= 1) return launch_kernel<gemm_rowblock_kernel<1, kSilu>>(grid, block, lds, stream, kRbWho, p);
+  if (per_thread <= 2) return launch_kernel<gemm_rowblock_kernel<2, kSilu>>(grid, block, lds, stream, kRbWho, p);
+  if (per_thread <= 4) return launch_kernel<gemm_rowblock_kernel<4, kSilu>>(grid, block, lds, stream, kRbWho, p);
+  return launch_kernel<gemm_rowblock_kernel<8, kSilu>>(grid, block, lds, stream, kRbWho, p);
+}
+
 int gemm_repacked(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipStream_t stream) {
-  static const int use_stream = getenv("ARCQ_REPACKED_STREAM") ? atoi(getenv("ARCQ_REPACKED_STREAM")) : 0;   // tuning / A-B only
+  static const int use_stream = env_int("ARCQ_REPACKED_STREAM", 0);   // tuning / A-B only
   if (a.M > 16) return gemm_repacked_mid(a, RW, RSF, stream);
   if (use_stream) return gemm_repacked_stream(a, RW, RSF, stream);
   const bool silu = a.epilogue == kEpiSiluMul;              // here: D stays gate|up, absmax_slots gets max |silu(g) * u| per row block
@@ -402,54 +420,25 @@ int gemm_repacked(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipS
   if (!gemm_repacked_supported(a.M, a.N, a.K))
     return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4_repacked: M=%d K=%d outside the repacked path (M <= 16, activation image <= 160 KB)", a.M, a.K);
   RowblockParams p;
-  p.A = a.A; p.SFA = a.SFA; p.RW = RW; p.RSF = RSF; p.D = a.D;
-  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
+  copy_gemm_fields(p, a);
+  p.RW = RW; p.RSF = RSF;
   p.silu_slots = a.absmax_slots;
   p.pairs = (int)rowblock_pairs(a.K);
   p.row_blocks = (a.N + 15) / 16;
-  static const int forced = getenv("ARCQ_ROWBLOCK_SLICES") ? atoi(getenv("ARCQ_ROWBLOCK_SLICES")) : 0;   // tuning only
+  static const int forced = env_int("ARCQ_ROWBLOCK_SLICES", 0);   // tuning only
   int s = rowblock_choose_slices(p.row_blocks, p.pairs);
   if (forced == 1 || forced == 2 || forced == 4 || forced == 8) s = forced;
   p.slices = s;
   const int lds = rowblock_lds_bytes(a.M, a.K, s, &p.a_stride);
-  const int units = a.M * p.pairs * 8;
-  const int per_thread = (units + kRbThreads - 1) / kRbThreads;
-  const int bpw = kRbWaves / s;
-  const int grid = (p.row_blocks + bpw - 1) / bpw;
-  auto launch = [&](auto kernel, LdsOptIn* opt) -> int {
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), *opt, lds, "arcq_gemm_nvfp4_repacked")) return rc;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kRbThreads), lds, stream, p);
-    return ARCQ_OK;
-  };
-  static LdsOptIn lds_set[8];           // one per kernel instantiation, each per device
   // the no-image kernel: ARCQ_ROWBLOCK_DIRECT=0/1 forces (A-B), default by shape (rowblock_use_direct)
-  static const int direct_env = getenv("ARCQ_ROWBLOCK_DIRECT") ? atoi(getenv("ARCQ_ROWBLOCK_DIRECT")) : -1;
+  static const int direct_env = env_int("ARCQ_ROWBLOCK_DIRECT", -1);
   const bool direct = direct_env >= 0 ? direct_env != 0 : rowblock_use_direct(a.M, a.N, a.K);
   if (direct) {
     const int dlds = s > 1 ? kRbWaves * 64 * 4 * (int)sizeof(float) : 0;
-    if (silu) hipLaunchKernelGGL(gemm_rowblock_direct_kernel<true>, dim3((unsigned)grid), dim3(kRbThreads), dlds, stream, p);
-    else hipLaunchKernelGGL(gemm_rowblock_direct_kernel<false>, dim3((unsigned)grid), dim3(kRbThreads), dlds, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4_repacked: launch failed: %s", hipGetErrorString(e));
-    return ARCQ_OK;
+    if (silu) return launch_kernel<gemm_rowblock_direct_kernel<true>>(rowblock_grid(p), dim3(kRbThreads), dlds, stream, kRbWho, p);
+    return launch_kernel<gemm_rowblock_direct_kernel<false>>(rowblock_grid(p), dim3(kRbThreads), dlds, stream, kRbWho, p);
   }
-  int rc;
-  if (silu) {
-    if (per_thread <= 1) rc = launch(gemm_rowblock_kernel<1, true>, &lds_set[4]);
-    else if (per_thread <= 2) rc = launch(gemm_rowblock_kernel<2, true>, &lds_set[5]);
-    else if (per_thread <= 4) rc = launch(gemm_rowblock_kernel<4, true>, &lds_set[6]);
-    else rc = launch(gemm_rowblock_kernel<8, true>, &lds_set[7]);
-  } else {
-    if (per_thread <= 1) rc = launch(gemm_rowblock_kernel<1, false>, &lds_set[0]);
-    else if (per_thread <= 2) rc = launch(gemm_rowblock_kernel<2, false>, &lds_set[1]);
-    else if (per_thread <= 4) rc = launch(gemm_rowblock_kernel<4, false>, &lds_set[2]);
-    else rc = launch(gemm_rowblock_kernel<8, false>, &lds_set[3]);
-  }
-  if (rc != ARCQ_OK) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4_repacked: launch failed: %s", hipGetErrorString(e));
-  return ARCQ_OK;
+  return silu ? launch_rowblock<true>(p, lds, stream) : launch_rowblock<false>(p, lds, stream);
 }
 
 }  // namespace arcq

@@ -355,7 +355,7 @@ static int rowmid_lds_bytes(int M, int64_t K, int slices, int tok, RowmidParams*
 // (one ds_read_b128 instead of a global load per tile) win while they fit, then the tiled GEMM.
 enum : int { kMidNone = 0, kMidLds = 1, kMidTok = 2 };
 static int rowtok_env() {       // ARCQ_ROWTOK (tuning / A-B): 0 = never the no-LDS kernel, 1 = always (16 < M <= 128), unset = by shape
-  static const int v = getenv("ARCQ_ROWTOK") ? atoi(getenv("ARCQ_ROWTOK")) : -1;
+  static const int v = env_int("ARCQ_ROWTOK", -1);
   return v;
 }
 static int mid_kind(int64_t M, int64_t N, int64_t K) {
@@ -372,66 +372,45 @@ static int mid_kind(int64_t M, int64_t N, int64_t K) {
 
 int gemm_repacked_mid_supported(int64_t M, int64_t N, int64_t K) { return mid_kind(M, N, K) != kMidNone ? 1 : 0; }
 
+// both kernels: one workgroup per kRmWaves / slices row blocks
+template <auto Kernel>
+static int launch_rowmid(const RowmidParams& p, int lds, hipStream_t stream) {
+  const int bpw = kRmWaves / p.slices;
+  return launch_kernel<Kernel>(dim3((unsigned)((p.row_blocks + bpw - 1) / bpw)), dim3(kRmThreads), lds, stream, "arcq_gemm_nvfp4_repacked", p);
+}
+
 int gemm_repacked_mid(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipStream_t stream) {
   if (a.epilogue != kEpiPlain) return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4_repacked: M=%d > 16 has no SiLU epilogue", a.M);
   const int kind = mid_kind(a.M, a.N, a.K);
   if (kind == kMidNone)
     return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4_repacked: M=%d N=%d K=%d outside the repacked path (see arcq_gemm_repacked_supported)", a.M, a.N, a.K);
-  const bool tokk = kind == kMidTok;
   RowmidParams p;
-  p.A = a.A; p.SFA = a.SFA; p.RW = RW; p.RSF = RSF; p.D = a.D;
-  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
+  copy_gemm_fields(p, a);
+  p.RW = RW; p.RSF = RSF;
   p.pairs = (int)rowmid_pairs(a.K);
   p.row_blocks = (a.N + 15) / 16;
-  static const int forced = getenv("ARCQ_ROWMID_SLICES") ? atoi(getenv("ARCQ_ROWMID_SLICES")) : 0;   // tuning only
+  static const int forced = env_int("ARCQ_ROWMID_SLICES", 0);   // tuning only
   int s = rowblock_choose_slices(p.row_blocks, p.pairs);
   if (forced == 1 || forced == 2 || forced == 4 || forced == 8) s = forced;
   if (s > p.pairs) s = 1;
   p.slices = s;
   const int tok = (a.M + 15) / 16;
-  if (tokk) {                                               // no activations in LDS: only the slice reduction's scratch
+  if (kind == kMidTok) {                                    // no activations in LDS: only the slice reduction's scratch
     const int ktok = tok <= 4 ? tok : (tok <= 6 ? 6 : 8);
     const int tlds = s > 1 ? kRmWaves * ktok * 64 * 4 * (int)sizeof(float) : 0;
-    const int tbpw = kRmWaves / s;
-    const int tgrid = (p.row_blocks + tbpw - 1) / tbpw;
     p.a_stride = p.s_stride = p.sf_off = 0;
-    static LdsOptIn tok_lds[5];
-    auto tlaunch = [&](auto kernel, LdsOptIn* opt) -> int {
-      if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), *opt, tlds, "arcq_gemm_nvfp4_repacked")) return rc;
-      hipLaunchKernelGGL(kernel, dim3((unsigned)tgrid), dim3(kRmThreads), tlds, stream, p);
-      return ARCQ_OK;
-    };
-    int rc;
     switch (ktok) {
-      case 2: rc = tlaunch(gemm_rowtok_kernel<2>, &tok_lds[0]); break;
-      case 3: rc = tlaunch(gemm_rowtok_kernel<3>, &tok_lds[1]); break;
-      case 4: rc = tlaunch(gemm_rowtok_kernel<4>, &tok_lds[2]); break;
-      case 6: rc = tlaunch(gemm_rowtok_kernel<6>, &tok_lds[3]); break;
-      default: rc = tlaunch(gemm_rowtok_kernel<8>, &tok_lds[4]); break;
+      case 2: return launch_rowmid<gemm_rowtok_kernel<2>>(p, tlds, stream);
+      case 3: return launch_rowmid<gemm_rowtok_kernel<3>>(p, tlds, stream);
+      case 4: return launch_rowmid<gemm_rowtok_kernel<4>>(p, tlds, stream);
+      case 6: return launch_rowmid<gemm_rowtok_kernel<6>>(p, tlds, stream);
+      default: return launch_rowmid<gemm_rowtok_kernel<8>>(p, tlds, stream);
     }
-    if (rc != ARCQ_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4_repacked: launch failed: %s", hipGetErrorString(e));
-    return ARCQ_OK;
   }
   const int lds = rowmid_lds_bytes(a.M, a.K, s, tok, &p);
-  const int bpw = kRmWaves / s;
-  const int grid = (p.row_blocks + bpw - 1) / bpw;
-  auto launch = [&](auto kernel, LdsOptIn* opt) -> int {
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), *opt, lds, "arcq_gemm_nvfp4_repacked")) return rc;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kRmThreads), lds, stream, p);
-    return ARCQ_OK;
-  };
-  static LdsOptIn lds_set[3];           // one per kernel instantiation, each per device
-  int rc;
-  if (tok == 2) rc = launch(gemm_rowmid_kernel<2>, &lds_set[0]);
-  else if (tok == 3) rc = launch(gemm_rowmid_kernel<3>, &lds_set[1]);
-  else rc = launch(gemm_rowmid_kernel<4>, &lds_set[2]);
-  if (rc != ARCQ_OK) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4_repacked: launch failed: %s", hipGetErrorString(e));
-  return ARCQ_OK;
+  if (tok == 2) return launch_rowmid<gemm_rowmid_kernel<2>>(p, lds, stream);
+  if (tok == 3) return launch_rowmid<gemm_rowmid_kernel<3>>(p, lds, stream);
+  return launch_rowmid<gemm_rowmid_kernel<4>>(p, lds, stream);
 }
 
 }  // namespace arcq

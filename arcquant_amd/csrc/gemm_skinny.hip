@@ -265,14 +265,10 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(SkinnyParams p, int 
 
 int gemm_splitk_finish(const GemmArgs& a, int splitk, hipStream_t stream) {
   SkinnyParams p{};
-  p.D = a.D; p.partial = reinterpret_cast<float*>(a.workspace);
-  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
+  copy_gemm_fields(p, a);
+  p.partial = reinterpret_cast<float*>(a.workspace);
   const int64_t quads = ((int64_t)a.M * a.N + 3) / 4;
-  hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, p, splitk);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4 (split-K finish): launch failed: %s", hipGetErrorString(e));
-  return ARCQ_OK;
+  return launch_kernel<splitk_finish_kernel>(dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, "arcq_gemm_nvfp4 (split-K finish)", p, splitk);
 }
 
 // split-K (over whole items) only when the tiles alone leave most CUs idle AND every split keeps >= 8 items: the
@@ -295,7 +291,7 @@ static void choose_split(int64_t N, int64_t K, int slab_k, int* splitk, int* sla
 // fits (M <= 8); 8 waves (two workgroups per CU) otherwise.  Measured on MI355X (tools/decode_bench.py, M = 1..4):
 // N=4096 KQ=4096: 16 waves 7.1 us vs 8 waves 7.2 us;  N=14336 KQ=4096: 8 waves 15.3 us vs 16 waves 19.2 us.
 static int skinny_waves(int64_t M, int64_t N) {
-  static const int forced = getenv("ARCQ_SKINNY_WAVES") ? atoi(getenv("ARCQ_SKINNY_WAVES")) : 0;
+  static const int forced = env_int("ARCQ_SKINNY_WAVES", 0);
   if (forced == 8 || (forced == 16 && M <= 8)) return forced;
   const int64_t tiles = ((N + 127) / 128) * 8;
   return (M <= 8 && tiles <= 256) ? 16 : 8;
@@ -310,18 +306,14 @@ int64_t gemm_skinny_workspace_bytes(int64_t M, int64_t N, int64_t K) {
 template <int kWaves>
 static int launch_skinny(const SkinnyParams& p, int splitk, hipStream_t stream) {
   using C = SkinnyCfg<kWaves>;
-  const int lds = C::lds_bytes(p.M);
-  static LdsOptIn lds_opt;             // per kernel instantiation, per device
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(gemm_skinny_kernel<kWaves>), lds_opt, C::lds_bytes(kWaves == 16 ? 8 : 16),
-                                  "arcq_gemm_nvfp4 (skinny)"))
-    return rc;
   // persistent workgroups, each walks tiles blockIdx.x, +grid, ...; 8-wave groups fit two per CU
-  static const int forced_grid = getenv("ARCQ_SKINNY_GRID") ? atoi(getenv("ARCQ_SKINNY_GRID")) : 0;
+  static const int forced_grid = env_int("ARCQ_SKINNY_GRID", 0);
   const int max_wg = forced_grid > 0 ? forced_grid : (kWaves == 16 ? 256 : 512);
   const int per_split = max_wg / splitk > 0 ? max_wg / splitk : 1;
   const int gx = p.tiles < per_split ? p.tiles : per_split;
-  hipLaunchKernelGGL(gemm_skinny_kernel<kWaves>, dim3((unsigned)gx, (unsigned)splitk), dim3(kWaves * 64), lds, stream, p);
-  return ARCQ_OK;
+  // opted in once for the largest image the instantiation takes, not per M
+  return launch_kernel<gemm_skinny_kernel<kWaves>>(dim3((unsigned)gx, (unsigned)splitk), dim3(kWaves * 64), {C::lds_bytes(p.M), C::lds_bytes(kWaves == 16 ? 8 : 16)},
+                                                   stream, "arcq_gemm_nvfp4 (skinny)", p);
 }
 
 int gemm_skinny(const GemmArgs& a, hipStream_t stream) {
@@ -329,10 +321,9 @@ int gemm_skinny(const GemmArgs& a, hipStream_t stream) {
   int splitk, per;
   choose_split(a.N, a.K, waves * 128, &splitk, &per);
   SkinnyParams p;
-  p.A = a.A; p.B = a.B; p.SFA = a.SFA; p.SFB = a.SFB; p.D = a.D;
+  copy_gemm_fields(p, a);
+  p.B = a.B; p.SFB = a.SFB;
   p.partial = reinterpret_cast<float*>(a.workspace);
-  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
   p.tiles = ((a.N + 127) / 128) * 8;
   p.slabs_per_split = per;
   if (splitk > 1) {
@@ -345,8 +336,6 @@ int gemm_skinny(const GemmArgs& a, hipStream_t stream) {
     return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4 (skinny): operand larger than 4 GiB");
   const int rc = waves == 16 ? launch_skinny<16>(p, splitk, stream) : launch_skinny<8>(p, splitk, stream);
   if (rc != ARCQ_OK) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4 (skinny): launch failed: %s", hipGetErrorString(e));
   if (splitk > 1) return gemm_splitk_finish(a, splitk, stream);
   return ARCQ_OK;
 }

@@ -717,13 +717,7 @@ int gemm_fused_supported(int kind, int64_t M, int64_t N, int64_t KQ, int64_t KE)
 
 template <int kSrc, int kOut, int kVariant>
 static int launch_stream(const StreamParams& p, const StreamGeom& g, hipStream_t stream, const char* who) {
-  static LdsOptIn lds_opt;               // per kernel instantiation, per device
-  auto kern = gemm_stream_kernel<kSrc, kOut, kVariant>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_opt, g.lds, who)) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)g.grid), dim3(kStThreads), g.lds, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return ARCQ_OK;
+  return launch_kernel<gemm_stream_kernel<kSrc, kOut, kVariant>>(dim3((unsigned)g.grid), dim3(kStThreads), g.lds, stream, who, p);
 }
 
 template <int kSrc, int kOut>
@@ -734,9 +728,8 @@ static int launch_stream_variant(const StreamParams& p, const StreamGeom& g, int
 
 static void fill_common(StreamParams& p, const StreamGeom& g, const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF) {
   p = StreamParams{};
-  p.RW = RW; p.RSF = RSF; p.A = a.A; p.SFA = a.SFA; p.D = a.D;
-  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual; p.out_slots = a.absmax_slots;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
+  copy_gemm_fields(p, a);
+  p.RW = RW; p.RSF = RSF; p.out_slots = a.absmax_slots;
   p.pairs = g.pairs; p.row_blocks = g.row_blocks; p.a_stride = g.a_stride; p.img_bytes = g.img_bytes;
   p.stage = g.stage; p.xrow_bytes = g.xrow_bytes; p.slot_off = g.slot_off; p.stage_off = g.stage_off; p.misc_off = g.misc_off;
 #ifdef ARCQ_STREAM_STAMPS

@@ -779,10 +779,6 @@ static const TileCfg& tile_cfg(int id) {
   return kTileCfgs[2];
 }
 
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 static int tile_cfg_override() {                // ARCQ_TILE_CFG (tuning)
   static const int v = env_int("ARCQ_TILE_CFG", 0);
   return v;
@@ -819,9 +815,8 @@ static void tile_split(int64_t M, int64_t N, int64_t K, int BM, int BN, int* spl
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool kMfma32 = false, int kEpi = kEpiPlain, int kBLayout = kBRef>
 static int launch_tile(const GemmArgs& a, hipStream_t stream, bool allow_split = false) {
   TileParams p;
-  p.A = a.A; p.B = a.B; p.SFA = a.SFA; p.SFB = a.SFB; p.D = a.D;
-  p.alpha_dev = a.alpha_dev; p.bias = a.bias; p.residual = a.residual;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.alpha_host = a.alpha_host; p.out_dtype = a.out_dtype;
+  copy_gemm_fields(p, a);
+  p.B = a.B; p.SFB = a.SFB;
   p.tiles_m = (a.M + BM - 1) / BM;
   p.tiles_n = (a.N + BN - 1) / BN;
   p.splits = 1; p.atoms_per_split = a.K / 64; p.partial = nullptr;
@@ -843,18 +838,16 @@ static int launch_tile(const GemmArgs& a, hipStream_t stream, bool allow_split =
   // weight (K rounded up to 256)
   if (((int64_t)a.K + 255) / 256 * 256 * 128 > 0xffffffffll)
     return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4 (tile): K = %lld: a tile's rows of an operand exceed 32-bit offsets", (long long)a.K);
-  const size_t lds = 2 * (size_t)(BM + BN) * kRowBytes;
-  constexpr bool kCanStagger = WAVES_M * WAVES_N == 8 && BM == 256 && BN == 256, kCanPipe = true;
-  auto kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false, kBLayout>;
-  if (kCanPipe && tile_pipe()) kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, kCanPipe, kBLayout>;
-  else if (kCanStagger && tile_stagger()) kern = gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, kCanStagger, false, kBLayout>;
-  // per instantiation and per (pipe, stagger) variant of it, per device: the driver call costs host time on every launch otherwise
-  static LdsOptIn lds_opt[3];
-  const int which = (kCanPipe && tile_pipe()) ? 1 : (kCanStagger && tile_stagger()) ? 2 : 0;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds_opt[which], (int)lds, "arcq_gemm_nvfp4 (tile)")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n * p.splits)), dim3(WAVES_M * WAVES_N * 64), lds, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_gemm_nvfp4 (tile): launch failed: %s", hipGetErrorString(e));
+  const int lds = 2 * (BM + BN) * kRowBytes;
+  const dim3 grid((unsigned)(p.tiles_m * p.tiles_n * p.splits)), block(WAVES_M * WAVES_N * 64);
+  const char* who = "arcq_gemm_nvfp4 (tile)";
+  constexpr bool kCanStagger = WAVES_M * WAVES_N == 8 && BM == 256 && BN == 256;
+  const bool pipe = tile_pipe(), stagger = !pipe && kCanStagger && tile_stagger();      // the variants of the instantiation
+  int rc;
+  if (!pipe && !stagger) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false, kBLayout>>(grid, block, lds, stream, who, p);
+  else if (pipe) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, true, kBLayout>>(grid, block, lds, stream, who, p);
+  else rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, kCanStagger, false, kBLayout>>(grid, block, lds, stream, who, p);
+  if (rc != ARCQ_OK) return rc;
   if (p.splits > 1) return gemm_splitk_finish(a, p.splits, stream);
   return ARCQ_OK;
 }

@@ -389,22 +389,16 @@ static int attn_decode_launch(const void* qkv, void* kcache, void* vcache, void*
   p.S = S; p.chunk = chunk;
   p.scale = 0.08838834764831845f;                           // 128^-0.5
   const int live = (T + chunk - 1) / chunk;
-  if (!sliced) {
-    hipLaunchKernelGGL(attn_decode_fused, dim3((unsigned)(B * H)), dim3(kAttnFusedWaves * 64), 0, (hipStream_t)stream, p);
-    hipError_t e1 = hipGetLastError();
-    if (e1 != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e1));
-    return ARCQ_OK;
-  }
-  hipLaunchKernelGGL(attn_decode_partial, dim3((unsigned)(B * H), (unsigned)live), dim3(kAttnThreads), 0, (hipStream_t)stream, p);
-  if (live > 1) hipLaunchKernelGGL(attn_decode_combine, dim3((unsigned)(B * H)), dim3(kAttnD), 0, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return ARCQ_OK;
+  const dim3 heads((unsigned)(B * H));
+  if (!sliced) return launch_kernel<attn_decode_fused>(heads, dim3(kAttnFusedWaves * 64), 0, (hipStream_t)stream, who, p);
+  const int rc = launch_kernel<attn_decode_partial>(dim3(heads.x, (unsigned)live), dim3(kAttnThreads), 0, (hipStream_t)stream, who, p);
+  if (rc != ARCQ_OK || live <= 1) return rc;
+  return launch_kernel<attn_decode_combine>(heads, dim3(kAttnD), 0, (hipStream_t)stream, who, p);
 }
 
 extern "C" int arcq_harness_attn_decode_window(const void* qkv, void* kcache, void* vcache, void* out, void* workspace, int64_t B, int64_t H,
                                                int64_t Tmax, int64_t pos, int64_t first, void* stream) {
-  static const int sliced = getenv("ARCQ_HARNESS_ATTN_SLICED") ? atoi(getenv("ARCQ_HARNESS_ATTN_SLICED")) : 0;   // A-B: the two-launch slice kernels
+  static const int sliced = env_int("ARCQ_HARNESS_ATTN_SLICED", 0);   // A-B: the two-launch slice kernels
   return attn_decode_launch(qkv, kcache, vcache, out, workspace, B, H, Tmax, pos, first, sliced, stream);
 }
 
@@ -423,9 +417,6 @@ extern "C" int arcq_harness_rmsnorm(const void* X, int64_t ldx, const void* W, v
   if (!X || !W || !out) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
   if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(out)) & 15)
     return fail(ARCQ_ERR_SHAPE, "%s: pointers must be 16-byte aligned", who);
-  hipLaunchKernelGGL(harness_rmsnorm_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)X, ldx, (const uint16_t*)W,
-                     (uint16_t*)out, (int)H, eps);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return ARCQ_OK;
+  return launch_kernel<harness_rmsnorm_kernel>(dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, who, (const uint16_t*)X, ldx, (const uint16_t*)W, (uint16_t*)out,
+                                               (int)H, eps);
 }

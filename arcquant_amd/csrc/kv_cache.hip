@@ -520,12 +520,6 @@ __global__ __launch_bounds__(kKvD) void kv_decode_combine(KvDecodeParams p) {
 }
 
 // ---- launchers (arguments validated by c_api_kv.hip)
-static int launched(const char* who) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return ARCQ_OK;
-}
-
 int kv_write(const KvWriteArgs& a, hipStream_t stream) {
   KvWriteParams p;
   p.data = (uint8_t*)a.kv_data; p.param = (uint32_t*)a.kv_param;
@@ -534,15 +528,11 @@ int kv_write(const KvWriteArgs& a, hipStream_t stream) {
   p.seqlen_indptr = a.seqlen_indptr;
   p.ntok = (int)a.ntok; p.B = (int)a.B; p.L = (int)a.L; p.layer = (int)a.layer; p.N = (int)a.N; p.P = (int)a.P;
   p.row_bytes = a.format == ARCQ_KV_INT4 ? 64 : 256;
-  if (!a.quantize) {
-    hipLaunchKernelGGL(kv_write_kernel, dim3((unsigned)a.ntok), dim3(256), 0, stream, p);
-    return launched("arcq_kv_write");
-  }
+  if (!a.quantize) return launch_kernel<kv_write_kernel>(dim3((unsigned)a.ntok), dim3(256), 0, stream, "arcq_kv_write", p);
   const int64_t rows = a.ntok * 2 * a.N;
   const dim3 grid((unsigned)((rows + 15) / 16));
-  if (a.dtype == ARCQ_KV_BF16) hipLaunchKernelGGL(kv_quantize_kernel<true>, grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL(kv_quantize_kernel<false>, grid, dim3(256), 0, stream, p);
-  return launched("arcq_kv_quantize");
+  if (a.dtype == ARCQ_KV_BF16) return launch_kernel<kv_quantize_kernel<true>>(grid, dim3(256), 0, stream, "arcq_kv_quantize", p);
+  return launch_kernel<kv_quantize_kernel<false>>(grid, dim3(256), 0, stream, "arcq_kv_quantize", p);
 }
 
 // query heads of a kv head that share a workgroup's pass over its rows
@@ -579,44 +569,37 @@ static Params kv_decode_params(const KvDecodeArgs& a) {
   return p;
 }
 
+// the kv_decode_kernel instantiation of a cache format, a 16-bit type and a group chunk
+template <int FMT, bool STEP, int GC>
+static int launch_kv_decode_gc(const typename KvParamsOf<STEP>::type& p, bool bf, const KvDecodeArgs& a, hipStream_t stream, const char* who) {
+  const dim3 grid((unsigned)(a.B * a.N * p.chunks), (unsigned)p.S), block(kKvWaves * 64);
+  if (bf) return launch_kernel<kv_decode_kernel<FMT, true, GC, STEP>>(grid, block, 0, stream, who, p);
+  return launch_kernel<kv_decode_kernel<FMT, false, GC, STEP>>(grid, block, 0, stream, who, p);
+}
+template <int FMT, bool STEP>
+static int launch_kv_decode(const typename KvParamsOf<STEP>::type& p, const KvDecodeArgs& a, hipStream_t stream, const char* who) {
+  const int gc = kv_group_chunk(p.g);
+  const bool bf = a.dtype == ARCQ_KV_BF16;
+  if (gc == 1) return launch_kv_decode_gc<FMT, STEP, 1>(p, bf, a, stream, who);
+  if (gc == 2) return launch_kv_decode_gc<FMT, STEP, 2>(p, bf, a, stream, who);
+  return launch_kv_decode_gc<FMT, STEP, 4>(p, bf, a, stream, who);
+}
+
 int kv_decode_step(const KvDecodeArgs& a, const KvStepArgs& st, hipStream_t stream) {
   KvStepParams p = kv_decode_params<KvStepParams>(a);
   p.k = (const uint16_t*)st.k; p.v = (const uint16_t*)st.v; p.cnt = (int32_t*)st.state;
   p.q_stride = st.q_stride; p.kv_stride = st.kv_stride;
-  const int gc = kv_group_chunk(p.g);
-  const dim3 grid((unsigned)(a.B * a.N * p.chunks), (unsigned)p.S), block(kKvWaves * 64);
-  const bool bf = a.dtype == ARCQ_KV_BF16;
-#define ARCQ_KV_LAUNCH(GC)                                                                                        \
-  do {                                                                                                            \
-    if (bf) hipLaunchKernelGGL((kv_decode_kernel<ARCQ_KV_INT4, true, GC, true>), grid, block, 0, stream, p);      \
-    else hipLaunchKernelGGL((kv_decode_kernel<ARCQ_KV_INT4, false, GC, true>), grid, block, 0, stream, p);        \
-  } while (0)
-  if (gc == 1) ARCQ_KV_LAUNCH(1); else if (gc == 2) ARCQ_KV_LAUNCH(2); else ARCQ_KV_LAUNCH(4);
-#undef ARCQ_KV_LAUNCH
-  return launched("arcq_kv_decode_step");
+  return launch_kv_decode<ARCQ_KV_INT4, true>(p, a, stream, "arcq_kv_decode_step");
 }
 
 int kv_decode(const KvDecodeArgs& a, hipStream_t stream) {
-  KvDecodeParams p = kv_decode_params<KvDecodeParams>(a);
-  const int gc = kv_group_chunk(p.g);
-  const dim3 grid((unsigned)(a.B * a.N * p.chunks), (unsigned)p.S), block(kKvWaves * 64);
-  const bool bf = a.dtype == ARCQ_KV_BF16;
-#define ARCQ_KV_LAUNCH(FMT, GC)                                                                         \
-  do {                                                                                                  \
-    if (bf) hipLaunchKernelGGL((kv_decode_kernel<FMT, true, GC>), grid, block, 0, stream, p);           \
-    else hipLaunchKernelGGL((kv_decode_kernel<FMT, false, GC>), grid, block, 0, stream, p);             \
-  } while (0)
-  if (a.format == ARCQ_KV_INT4) {
-    if (gc == 1) ARCQ_KV_LAUNCH(ARCQ_KV_INT4, 1); else if (gc == 2) ARCQ_KV_LAUNCH(ARCQ_KV_INT4, 2); else ARCQ_KV_LAUNCH(ARCQ_KV_INT4, 4);
-  } else {
-    if (gc == 1) ARCQ_KV_LAUNCH(ARCQ_KV_16BIT, 1); else if (gc == 2) ARCQ_KV_LAUNCH(ARCQ_KV_16BIT, 2); else ARCQ_KV_LAUNCH(ARCQ_KV_16BIT, 4);
-  }
-#undef ARCQ_KV_LAUNCH
-  if (p.S > 1) {
-    if (bf) hipLaunchKernelGGL(kv_decode_combine<true>, dim3((unsigned)(a.B * a.Nq)), dim3(kKvD), 0, stream, p);
-    else hipLaunchKernelGGL(kv_decode_combine<false>, dim3((unsigned)(a.B * a.Nq)), dim3(kKvD), 0, stream, p);
-  }
-  return launched("arcq_kv_batch_decode");
+  const char* who = "arcq_kv_batch_decode";
+  const KvDecodeParams p = kv_decode_params<KvDecodeParams>(a);
+  const int rc = a.format == ARCQ_KV_INT4 ? launch_kv_decode<ARCQ_KV_INT4, false>(p, a, stream, who) : launch_kv_decode<ARCQ_KV_16BIT, false>(p, a, stream, who);
+  if (rc != ARCQ_OK || p.S <= 1) return rc;
+  const dim3 grid((unsigned)(a.B * a.Nq));
+  if (a.dtype == ARCQ_KV_BF16) return launch_kernel<kv_decode_combine<true>>(grid, dim3(kKvD), 0, stream, who, p);
+  return launch_kernel<kv_decode_combine<false>>(grid, dim3(kKvD), 0, stream, who, p);
 }
 
 }  // namespace arcq

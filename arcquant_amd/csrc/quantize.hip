@@ -416,17 +416,14 @@ static int launch_quantize(const void* X, const void* Wn, float eps, const int16
   size_t lds = lds_row_bytes((size_t)KQ) + (kMode == kModeRms ? 512 * sizeof(float) + lds_row_bytes((size_t)KQ) : 0);
   int grid, gsplit;
   quant_grid(rows, KQ, &grid, &gsplit);
-  auto go = [&](auto kern, LdsOptIn& opt) -> int {
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), opt, (int)lds, who)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid, gsplit), dim3(kQuantThreads), lds, stream, (const uint16_t*)X, (const uint16_t*)Xup,
-                       ldx ? ldx : KQ, (const uint16_t*)Wn, eps, idx, Q, SF, (int)rows, (int)KQ, (int)KE, dyn, nslots, scale_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return ARCQ_OK;
-  };
-  static LdsOptIn lds_opt[2];           // per (kMode, kDyn, kSilu) instantiation and variant, each per device
-  if (variant == ARCQ_VARIANT_G16) return go(quantize_rows_kernel<ARCQ_VARIANT_G16, kMode, kDyn, kSilu>, lds_opt[0]);
-  return go(quantize_rows_kernel<ARCQ_VARIANT_G32, kMode, kDyn, kSilu>, lds_opt[1]);
+  const dim3 g2(grid, gsplit), block(kQuantThreads);
+  const uint16_t *x = (const uint16_t*)X, *xup = (const uint16_t*)Xup, *wn = (const uint16_t*)Wn;
+  const int64_t ld = ldx ? ldx : KQ;
+  if (variant == ARCQ_VARIANT_G16)
+    return launch_kernel<quantize_rows_kernel<ARCQ_VARIANT_G16, kMode, kDyn, kSilu>>(g2, block, (int)lds, stream, who, x, xup, ld, wn, eps, idx, Q, SF, (int)rows, (int)KQ,
+                                                                                      (int)KE, dyn, nslots, scale_out);
+  return launch_kernel<quantize_rows_kernel<ARCQ_VARIANT_G32, kMode, kDyn, kSilu>>(g2, block, (int)lds, stream, who, x, xup, ld, wn, eps, idx, Q, SF, (int)rows, (int)KQ,
+                                                                                    (int)KE, dyn, nslots, scale_out);
 }
 
 int quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, int variant,
@@ -473,7 +470,7 @@ int quantize_x_dyn(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX,
   if (n * 2 <= kDynLocalMaxBytes && n * 2 * qg * qs <= kDynLocalMaxTotalBytes)     // decode-sized: one launch, `state` untouched
     return launch_quantize<kModeX, kDynLocal>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, "arcq_quantize_x_dyn", nullptr, 0, scale_out);
   const int grid = absmax_grid(n8);
-  hipLaunchKernelGGL(absmax_bits_kernel<false>, dim3(grid), dim3(kAbsmaxThreads), 0, stream, (const uint16_t*)X, n8, n, st);
+  if (int e = launch_kernel<absmax_bits_kernel<false>>(dim3(grid), dim3(kAbsmaxThreads), 0, stream, "arcq_quantize_x_dyn", (const uint16_t*)X, n8, n, st)) return e;
   return launch_quantize<kModeX, kDynState>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, "arcq_quantize_x_dyn", st, grid, scale_out);
 }
 
@@ -492,15 +489,12 @@ int quantize_x_dyn_slots(const void* X, const int16_t* idx, uint8_t* QX, uint8_t
       return fail(ARCQ_ERR_SHAPE, "%s: X must be 16-byte, QX 8-byte and SFX 4-byte aligned", who);
     const int64_t total = M * (KQ / 16);
     const int grid = (int)((total + kQuantThreads - 1) / kQuantThreads < kMaxQuantBlocks ? (total + kQuantThreads - 1) / kQuantThreads : kMaxQuantBlocks);
+    const uint16_t* x = (const uint16_t*)X;
     if (variant == ARCQ_VARIANT_G16)
-      hipLaunchKernelGGL(quantize_contig_dyn_kernel<ARCQ_VARIANT_G16>, dim3(grid), dim3(kQuantThreads), 0, stream, (const uint16_t*)X, QX, SFX, (int)M,
-                         (int)KQ, (int)KE, slots, (int)nslots, scale_out);
-    else
-      hipLaunchKernelGGL(quantize_contig_dyn_kernel<ARCQ_VARIANT_G32>, dim3(grid), dim3(kQuantThreads), 0, stream, (const uint16_t*)X, QX, SFX, (int)M,
-                         (int)KQ, (int)KE, slots, (int)nslots, scale_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-    return ARCQ_OK;
+      return launch_kernel<quantize_contig_dyn_kernel<ARCQ_VARIANT_G16>>(dim3(grid), dim3(kQuantThreads), 0, stream, who, x, QX, SFX, (int)M, (int)KQ, (int)KE, slots,
+                                                                         (int)nslots, scale_out);
+    return launch_kernel<quantize_contig_dyn_kernel<ARCQ_VARIANT_G32>>(dim3(grid), dim3(kQuantThreads), 0, stream, who, x, QX, SFX, (int)M, (int)KQ, (int)KE, slots,
+                                                                       (int)nslots, scale_out);
   }
   return launch_quantize<kModeX, kDynState>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, who, slots, (int)nslots, scale_out);
 }
@@ -526,10 +520,10 @@ int silu_mul_quantize_x_dyn(const void* GU, const int16_t* idx, uint8_t* QX, uin
   const int64_t want = (total + threads - 1) / threads;
   const int grid = (int)(want > kAbsmaxMaxBlocks ? kAbsmaxMaxBlocks : want);
   if (layout == ARCQ_GU_PAIRS) {
-    hipLaunchKernelGGL(silu_mul_absmax_kernel<kSiluPairs>, dim3(grid), dim3(threads), 0, stream, G, G, 2 * KQ, (int)M, (int)chunks, st);
+    if (int e = launch_kernel<silu_mul_absmax_kernel<kSiluPairs>>(dim3(grid), dim3(threads), 0, stream, who, G, G, 2 * KQ, (int)M, (int)chunks, st)) return e;
     return launch_quantize<kModeX, kDynState, kSiluPairs>(G, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, who, st, grid, scale_out, G, 2 * KQ);
   }
-  hipLaunchKernelGGL(silu_mul_absmax_kernel<kSiluHalves>, dim3(grid), dim3(threads), 0, stream, G, U, 2 * KQ, (int)M, (int)chunks, st);
+  if (int e = launch_kernel<silu_mul_absmax_kernel<kSiluHalves>>(dim3(grid), dim3(threads), 0, stream, who, G, U, 2 * KQ, (int)M, (int)chunks, st)) return e;
   return launch_quantize<kModeX, kDynState, kSiluHalves>(G, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, who, st, grid, scale_out, U, 2 * KQ);
 }
 
@@ -558,11 +552,9 @@ int absmax_scale(const void* X, int64_t n, float* scale_out, hipStream_t stream)
   hipError_t e = hipMemsetAsync(slot, 0, sizeof(unsigned int), stream);
   if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_absmax_scale: memset failed: %s", hipGetErrorString(e));
   const int64_t n8 = n / 8;
-  hipLaunchKernelGGL(absmax_bits_kernel<true>, dim3(absmax_grid(n8)), dim3(kAbsmaxThreads), 0, stream, (const uint16_t*)X, n8, n, slot);
-  hipLaunchKernelGGL(absmax_finish_kernel, dim3(1), dim3(1), 0, stream, slot, scale_out);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "arcq_absmax_scale: launch failed: %s", hipGetErrorString(e));
-  return ARCQ_OK;
+  const char* who = "arcq_absmax_scale";
+  if (int rc = launch_kernel<absmax_bits_kernel<true>>(dim3(absmax_grid(n8)), dim3(kAbsmaxThreads), 0, stream, who, (const uint16_t*)X, n8, n, slot)) return rc;
+  return launch_kernel<absmax_finish_kernel>(dim3(1), dim3(1), 0, stream, who, slot, scale_out);
 }
 
 }  // namespace arcq

@@ -192,13 +192,8 @@ static int mx_launch(const void* X, const int16_t* idx, uint8_t* Q, uint8_t* SF,
   const int grid = (int)(rows < kMxMaxBlocks ? rows : kMxMaxBlocks);
   int split = 1;       // decode: split the row's blocks over up to 16 workgroups of >= 32 blocks each
   while (grid * split < 256 && split < 16 && (KQ / 32) / (split * 2) >= 32) split *= 2;
-  static LdsOptIn opt;
-  auto kern = mx_quantize_rows_kernel<kModeW>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), opt, (int)lds, who)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid, split), dim3(kMxThreads), lds, stream, (const uint16_t*)X, idx, Q, SF, (int)rows, (int)KQ, (int)KE);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return ARCQ_OK;
+  return launch_kernel<mx_quantize_rows_kernel<kModeW>>(dim3(grid, split), dim3(kMxThreads), (int)lds, stream, who, (const uint16_t*)X, idx, Q, SF, (int)rows, (int)KQ,
+                                                        (int)KE);
 }
 
 int mx_quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, hipStream_t stream) {
@@ -234,14 +229,8 @@ template <int kSrc, bool kDirect>
 static int mx_fused_launch(const void* X, const void* Xup, int64_t ldx, const void* Wn, float eps, const int16_t* idx, uint8_t* Q, uint8_t* SF,
                            int64_t rows, int64_t KQ, int64_t KE, int grid, int split, hipStream_t stream, const char* who) {
   const size_t lds = kDirect ? 0 : lds_row_bytes((size_t)KQ) + (kSrc == kMxSrcRms ? 512 * sizeof(float) + lds_row_bytes((size_t)KQ) : 0);
-  static LdsOptIn opt;
-  auto kern = mx_fused_rows_kernel<kSrc, kDirect>;
-  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), opt, (int)lds, who)) return rc;
-  hipLaunchKernelGGL(kern, dim3(grid, split), dim3(kMxThreads), lds, stream, (const uint16_t*)X, (const uint16_t*)Xup, ldx, (const uint16_t*)Wn, eps,
-                     idx, Q, SF, (int)rows, (int)KQ, (int)KE);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(ARCQ_ERR_LAUNCH, "%s: launch failed: %s", who, hipGetErrorString(e));
-  return ARCQ_OK;
+  return launch_kernel<mx_fused_rows_kernel<kSrc, kDirect>>(dim3(grid, split), dim3(kMxThreads), (int)lds, stream, who, (const uint16_t*)X, (const uint16_t*)Xup, ldx,
+                                                            (const uint16_t*)Wn, eps, idx, Q, SF, (int)rows, (int)KQ, (int)KE);
 }
 
 int mx_rmsnorm_quantize_x(const void* X, const void* Wn, float eps, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ,

@@ -511,6 +511,7 @@ def test_repacked_weight_gemm_equals_the_reference_layout_gemm():
     cases = [(1, 512, 256, 64, O.G16), (4, 100, 256, 64, O.G16), (3, 1000, 64, 0, O.G16), (16, 272, 1024, 64, O.G16),
              (8, 777, 512, 64, O.G16), (4, 3584, 3584, 64, O.G32), (2, 52000, 256, 64, O.G16), (5, 5120, 384, 0, O.G16),
              (4, 256, 18944, 64, O.G32),        # a 153.7 KB activation image (Qwen2.5-7B down-projection at bs=4)
+             (16, 64, 2240, 64, O.G16),         # four 16-byte units of the image per thread (the cases above: one, two and eight)
              # decode batches, 16 < M <= 128: the weight is still read once; activations fetched per tile pair (no LDS: small weights, any
              # K) or resident packed in LDS (large weights while they fit) -- gemm_rowmid.hip, mid_kind
              (17, 128, 256, 64, O.G16), (32, 1000, 2048, 64, O.G16), (33, 516, 2048, 0, O.G16), (48, 777, 512, 64, O.G16),
@@ -553,7 +554,9 @@ def test_repacked_gateup_gemm_leaves_the_absmax_of_silu_mul_for_a_one_launch_qua
     two-launch path (one to eight waves per row block, ragged N % 16, M = 1 ... 16)."""
     import torch.nn.functional as F
     ag = _agemm()
-    for (M, IT, KQ, KE) in [(4, 2560, 512, 64), (1, 18, 256, 0), (3, 136, 256, 64), (16, 1000, 1024, 64), (4, 18944, 3584, 64)]:
+    for (M, IT, KQ, KE) in [(4, 2560, 512, 64), (1, 18, 256, 0), (3, 136, 256, 64), (16, 1000, 1024, 64),
+                            # four and eight 16-byte units of the image per thread (the others: one and two); the no-image kernel (N * K = 8 Mi)
+                            (16, 32, 2240, 64), (16, 32, 4800, 64), (4, 2048, 2048, 0), (4, 18944, 3584, 64)]:
         N = 2 * IT
         g = torch.Generator().manual_seed(M + IT)
         x, sx = prescale(outlier_activations(M, KQ, 5 + M))
