@@ -88,6 +88,7 @@ KV_SYMBOLS = {
     "arcq_kv_decode_step_state_bytes": (_i64, [_i64, _i64, _i64]),
     "arcq_kv_decode_step": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p,
                                    _i64, _p]),
+    "arcq_kv_batch_prefill": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p]),
 }
 
 _lib = None

@@ -203,4 +203,16 @@ struct KvStepArgs {                        // what the decode step takes beside 
 int64_t kv_decode_chunks(int64_t Nq, int64_t N);   // workgroups per (sequence, kv head): ceil(g / min(g, 4))
 int kv_decode_step(const KvDecodeArgs& a, const KvStepArgs& st, hipStream_t stream);
 
+// kv_prefill.hip: causal prefill attention over the int4 pages (arguments validated by c_api_kv.hip)
+struct KvPrefillArgs {
+  void* o;
+  const void* q;
+  const int32_t* qo_indptr;                // int32 [B + 1]: the query tokens of sequence b are rows qo_indptr[b] .. qo_indptr[b+1] of q / o
+  const void *kv_data, *kv_param;
+  const int32_t *kv_indptr, *kv_indices, *last_page_offset;
+  int64_t ntok, B, Nq, L, layer, N, P;
+  int dtype;
+};
+int kv_prefill(const KvPrefillArgs& a, hipStream_t stream);
+
 }  // namespace arcq

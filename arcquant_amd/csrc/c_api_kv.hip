@@ -111,6 +111,27 @@ int arcq_kv_batch_decode(void* o, const void* q, const void* kv_data, const void
   return kv_decode(a, (hipStream_t)stream);
 }
 
+int arcq_kv_batch_prefill(void* o, const void* q, const int32_t* qo_indptr, const void* kv_data, const void* kv_param, const int32_t* kv_indptr,
+                          const int32_t* kv_indices, const int32_t* last_page_offset, int64_t ntok, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
+                          int64_t N, int64_t P, int64_t nnz, int format, int dtype, void* stream) {
+  const char* who = "arcq_kv_batch_prefill";
+  int rc = geometry(who, B, L, layer_idx, N, P, format);
+  if (rc != ARCQ_OK) return rc;
+  if ((rc = dtype_ok(who, dtype)) != ARCQ_OK) return rc;
+  if (Nq <= 0 || Nq % N || Nq > 65535)
+    return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (at most 65535)", who, (long long)Nq, (long long)N);
+  if (nnz < 0 || nnz > kMaxDim || nnz * P > INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: nnz=%lld pages of P=%lld entries are out of range", who, (long long)nnz, (long long)P);
+  if (ntok < 0 || ntok > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: ntok=%lld is out of range", who, (long long)ntok);
+  if (format != ARCQ_KV_INT4) return fail(ARCQ_ERR_UNSUPPORTED, "%s: prefill attention reads ARCQ_KV_INT4 caches only", who);
+  if (B == 0 || ntok == 0) return ARCQ_OK;
+  if (!o || !q || !qo_indptr || !kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
+  if (misaligned(o, 16) || misaligned(q, 16) || misaligned(kv_data, 16)) return fail(ARCQ_ERR_SHAPE, "%s: o, q and kv_data must be 16-byte aligned", who);
+  if (misaligned(kv_param, 4) || misaligned(qo_indptr, 4) || misaligned(kv_indptr, 4) || misaligned(kv_indices, 4) || misaligned(last_page_offset, 4))
+    return fail(ARCQ_ERR_SHAPE, "%s: kv_param and the index tensors must be 4-byte aligned", who);
+  KvPrefillArgs a{o, q, qo_indptr, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, ntok, B, Nq, L, layer_idx, N, P, dtype};
+  return kv_prefill(a, (hipStream_t)stream);
+}
+
 int64_t arcq_kv_decode_step_state_bytes(int64_t B, int64_t Nq, int64_t N) {
   if (B <= 0 || Nq <= 0 || N <= 0 || Nq % N) return 0;
   return B * N * kv_decode_chunks(Nq, N) * (int64_t)sizeof(int32_t);

@@ -18,7 +18,8 @@ allocation-free apart from torch's caching allocator).
 ``agemm.mx_reorder_quantize_w`` (no per-tensor scale, alpha = 1), activations with the one-launch operators of ``arcquant_amd.mx``.
 
 ``kv_cache="int4"`` (``--kv-cache int4``) swaps the dense bf16 cache for the reference's int4 paged cache served by ``arcquant_amd.kvcache``
-(``DecoderModel._attention_int4``); the default is the dense cache.
+(``DecoderModel._attention_int4``); the default is the dense cache.  ``kv_paged_prefill=True`` (``--kv-paged-prefill``) on top of it makes
+every multi-token call, at any position, attend over the pages with ``kvcache.batch_prefill_i4`` instead of SDPA over its own k / v.
 """
 from __future__ import annotations
 
@@ -120,7 +121,7 @@ class DecoderModel:
 
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
                  repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False, kv_cache: str = "bf16",
-                 kv_fused_step: bool = False):
+                 kv_fused_step: bool = False, kv_paged_prefill: bool = False):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
@@ -129,13 +130,17 @@ class DecoderModel:
         (mx.matmul_silu_mul_quantize) instead of mx.matmul_silu_mul + mx_reorder_quantize_x, prefill and decode alike; same logits.
         kv_cache="int4" (attention="cache", head dimension 128): the reference's int4 paged cache (arcquant_amd.kvcache)
         instead of the dense bf16 one -- a prefill writes its k / v through init_kv_quantize_i4, a decode step appends with
-        append_kv_quantize_i4 and attends with batch_decode_i4.  "bf16" (default) is the dense cache."""
+        append_kv_quantize_i4 and attends with batch_decode_i4.  "bf16" (default) is the dense cache.
+        kv_paged_prefill (kv_cache="int4" only): a multi-token call at ANY position writes its k / v into the pages and attends over them
+        with batch_prefill_i4 (chunked prefill, a second turn); off, a multi-token call starts at position 0 and attends with SDPA."""
         if kv_cache not in ("bf16", "int4"):
             raise ValueError(f"DecoderModel: kv_cache must be 'bf16' or 'int4', got {kv_cache!r}")
         if kv_cache == "int4" and (attention != "cache" or cfg.hidden_size // cfg.num_heads != kvcache.HEAD_DIM):
             raise ValueError("DecoderModel: kv_cache='int4' needs attention='cache' and a head dimension of 128")
         if kv_fused_step and kv_cache != "int4":
             raise ValueError("DecoderModel: kv_fused_step=True needs kv_cache='int4' (the one-launch decode step is the int4 paged cache's)")
+        if kv_paged_prefill and kv_cache != "int4":
+            raise ValueError("DecoderModel: kv_paged_prefill=True needs kv_cache='int4' (the prefill attention is the int4 paged cache's)")
         if repacked_only and not fused:
             raise ValueError("DecoderModel: repacked_only=True needs fused=True (the unfused model is the reference's call structure)")
         if quant_type not in ("NVFP4", "MXFP4"):
@@ -150,7 +155,7 @@ class DecoderModel:
         self.cfg, self.device, self.batch, self.max_len, self.fused = cfg, device, batch, max_len, fused
         self.repacked_only = repacked_only
         self.attention = attention
-        self.kv_cache, self.kv_fused_step = kv_cache, kv_fused_step
+        self.kv_cache, self.kv_fused_step, self.kv_paged_prefill = kv_cache, kv_fused_step, kv_paged_prefill
         self.kv_trace = None      # a list: _attention_int4 appends (layer, pos, q, k, v, out) of every decode step to it (tests)
         # the down projection's quantiser as its GEMM's prologue: every CU then quantises the whole M x intermediate activation
         # itself, which only pays while that is small (measured: Qwen2.5-7B, 4 x 18944: slower than the separate launch)
@@ -395,12 +400,24 @@ class DecoderModel:
     def _attention_int4(self, li, q, k, v, qkv, pos, bsz, q_len):
         """kv_cache="int4": layer ``li``'s K / V go into the int4 paged cache and a decode step attends over it (arcquant_amd.kvcache).
         Prefill (q_len > 1, from position 0 only): init_kv_quantize_i4 writes the pages; the prompt's own causal attention is torch
-        SDPA over this call's k / v, as with the dense cache -- there is no prefill attention over int4 pages.  Decode:
+        SDPA over this call's k / v, as with the dense cache.  With kv_paged_prefill a multi-token call at any position writes the pages
+        of positions pos .. pos + q_len - 1 and attends over positions 0 .. with batch_prefill_i4: no SDPA, and what the prompt attends
+        over is what the decode steps will read (the call is also traced, with ``n_new`` = q_len).  Decode:
         append_kv_quantize_i4, then batch_decode_i4 over positions [0, pos], on the q, k and v slices of the projection output (one
         transposing copy makes the three contiguous); with kv_fused_step the three become ONE kvstep.decode_step_i4 launch on views of
         the projection output, bit for bit the same.  Harness glue around the operators, like the dense cache's kernel."""
         cfg = self.cfg
         nh, hd, h = cfg.num_heads, cfg.hidden_size // cfg.num_heads, cfg.hidden_size
+        if q_len > 1 and self.kv_paged_prefill:
+            qq, kk, vv = (t.reshape(bsz * q_len, nh, hd).contiguous() for t in (q, k, v))
+            tables = self.kvc.prefill_tables(pos + q_len, q_len)
+            qo_indptr = tables.pop("qo_indptr")
+            kvcache.init_kv_quantize_i4(**tables, k=kk, v=vv, seqlen_indptr=qo_indptr, layer_idx=li)
+            out = torch.empty_like(qq)
+            kvcache.batch_prefill_i4(out, qq, qo_indptr, **tables, layer_idx=li)
+            if self.kv_trace is not None:
+                self.kv_trace.append(dict(layer=li, pos=pos, n_new=q_len, q=qq.clone(), k=kk.clone(), v=vv.clone(), out=out.clone()))
+            return out.view(bsz * q_len, h)
         if q_len > 1:
             if pos != 0:
                 raise ValueError("DecoderModel(kv_cache='int4'): a multi-token call must start at position 0 (no prefill attention over the int4 pages)")
@@ -454,7 +471,7 @@ class DecoderModel:
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
                  attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False, kv_cache="bf16",
-                 kv_fused_step=False):
+                 kv_fused_step=False, kv_paged_prefill=False):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
     weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
@@ -464,7 +481,8 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
     with torch.no_grad():
         mem0 = torch.cuda.memory_allocated(device)
         model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
-                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step)
+                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
+                             kv_paged_prefill=kv_paged_prefill)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -527,12 +545,14 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         res["kv_cache"] = kv_cache
     if kv_fused_step:
         res["kv_fused_step"] = True
+    if kv_paged_prefill:
+        res["kv_paged_prefill"] = True
     return res
 
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
                    fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False,
-                   kv_cache="bf16", kv_fused_step=False):
+                   kv_cache="bf16", kv_fused_step=False, kv_paged_prefill=False):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -562,7 +582,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
 
     with torch.no_grad():
         model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
-                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step)
+                             quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
+                             kv_paged_prefill=kv_paged_prefill)
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -609,6 +630,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         res["kv_cache"] = kv_cache
     if kv_fused_step:
         res["kv_fused_step"] = True
+    if kv_paged_prefill:
+        res["kv_paged_prefill"] = True
     return res
 
 
@@ -757,6 +780,9 @@ if __name__ == "__main__":
     kfs = "--kv-fused-step" in sys.argv      # --kv-cache int4 only: the decode step's append + attention as one launch (kvstep)
     if kfs and kvc != "int4":
         sys.exit("--kv-fused-step needs --kv-cache int4")
+    kpp = "--kv-paged-prefill" in sys.argv   # --kv-cache int4 only: multi-token calls attend over the pages (kvcache.batch_prefill_i4)
+    if kpp and kvc != "int4":
+        sys.exit("--kv-paged-prefill needs --kv-cache int4")
     ro = "--repacked-only" in sys.argv       # one weight copy per linear (the fused model only)
     qe = "--mx-quantised-epilogue" in sys.argv   # MXFP4, the fused model only: the gate|up GEMM quantises the down projection's input
     if qe and qt != "MXFP4":
@@ -764,12 +790,12 @@ if __name__ == "__main__":
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
             print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
-                                            kv_fused_step=kfs)), flush=True)
+                                            kv_fused_step=kfs, kv_paged_prefill=kpp)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
             if ((ro or qe) and not fused) or (kvc == "int4" and att != "cache"):
                 continue
             print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
-                                          kv_fused_step=kfs)), flush=True)
+                                          kv_fused_step=kfs, kv_paged_prefill=kpp)), flush=True)
             torch.cuda.empty_cache()

@@ -11,7 +11,8 @@ functions of these names stay ``NotImplementedError`` stubs.
 Extensions: ``append_kv_quantize_i4`` / ``init_kv_quantize_i4`` quantise fp16 / bf16 rows and write them in one launch (the reference:
 five torch launches per tensor, then the append); ``batch_decode_*`` also takes bf16 and ``Nq = g * N`` query heads (GQA: query head h
 reads kv head h // g).  ``asym_quantize_and_pack_i4`` / ``unpack_i4_and_asym_dequantize`` are the torch formulas for callers that keep the
-reference's flow, ``PagedKVCacheI4`` holds the pages and builds the tables.
+reference's flow, ``PagedKVCacheI4`` holds the pages and builds the tables.  ``batch_prefill_i4`` (kvprefill.py) is the causal attention
+of several query tokens per sequence over the int4 pages: chunked prefill, a second turn, speculative verification.
 
 This module is a ctypes mirror only.  Validation follows the mirror's order (``agemm._need`` ...): dtype / rank / contiguity, then the size
 relations, and LAST where everything lives.  The CONTENTS of the index tensors are the caller's contract, as in the reference.
@@ -220,6 +221,7 @@ class PagedKVCacheI4:
         self._indices = [own[:, :c].reshape(-1).to(device) for c in range(1, per_seq + 1)]
         length = torch.arange(1, max_seq_len + 1, dtype=torch.int32)
         self._last = (length - (length - 1) // page_size * page_size).unsqueeze(1).expand(-1, bs).contiguous().to(device)
+        self._qo = {}         # n_new -> qo_indptr of prefill_tables
 
     def page_cnt_from_length(self, length: int) -> int:
         return (length + self.page_size - 1) // self.page_size
@@ -232,3 +234,20 @@ class PagedKVCacheI4:
         c = self.page_cnt_from_length(length)
         return {"kv_data": self.pages, "kv_param": self.scales, "kv_indptr": self._indptr[c - 1], "kv_indices": self._indices[c - 1],
                 "last_page_offset": self._last[length - 1]}
+
+    def prefill_tables(self, length: int, n_new: int) -> dict:
+        """``tables(length)`` plus ``qo_indptr`` for ``n_new`` query tokens per sequence, the last ``n_new`` of its ``length`` positions
+        (also the ``seqlen_indptr`` of the ``init_kv_*`` call that writes them).  Built once per distinct ``n_new``: nothing is allocated
+        when one comes back."""
+        if not 1 <= n_new <= length:
+            raise RuntimeError(f"kvcache.PagedKVCacheI4: {n_new} new tokens do not fit a sequence of {length} positions")
+        out = self.tables(length)
+        qo = self._qo.get(n_new)
+        if qo is None:
+            qo = self._qo[n_new] = (torch.arange(self.batch_size + 1, dtype=torch.int32) * n_new).to(self.device)
+        out["qo_indptr"] = qo
+        return out
+
+
+# ---- extension: causal prefill attention over the int4 pages, several query tokens per sequence (its own module, as kvstep is)
+from .kvprefill import batch_prefill_i4  # noqa: E402,F401

@@ -6,7 +6,8 @@
  * which is out of scope here -- `agemm.batch_decode_*` / `init_kv_*` / `append_kv_*` stay NotImplementedError stubs.  The
  * harness needs SOME attention between the ARC-NVFP4 linears to time a decoder step; it uses torch SDPA for prefill and, for
  * the one-token decode step over its dense bf16 cache, the streaming kernel below (torch's SDPA / bmm take 45-48 us per layer
- * for the 60 MB they read; this takes what the bytes take).
+ * for the 60 MB they read; this takes what the bytes take).  (The int4 paged cache itself is include/arcq_kv.h; with the
+ * harness's kv_paged_prefill switch a multi-token call attends over its pages with arcq_kv_batch_prefill instead of SDPA.)
  */
 #ifndef ARCQ_HARNESS_H_
 #define ARCQ_HARNESS_H_

@@ -77,6 +77,26 @@ int arcq_kv_batch_decode(void *o, const void *q, const void *kv_data, const void
                          const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
                          int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Causal prefill attention over the pages: several query tokens per sequence, each attending over everything the cache holds up to and
+ * including its own position.  o, q = `dtype` [ntok, Nq, 128], contiguous, Nq = g * N.  qo_indptr = int32 [B + 1] on the device,
+ * non-decreasing from 0 with qo_indptr[B] <= ntok (the caller's contract, like the other tables): sequence b has
+ * n_b = qo_indptr[b+1] - qo_indptr[b] query tokens, rows qo_indptr[b] .. of q and o.  T_b is what the tables say, as everywhere in
+ * this header, and INCLUDES those n_b tokens: the caller has written them with arcq_kv_init* already, as decode reads the row
+ * arcq_kv_append just wrote.  The contract requires n_b <= T_b.  Query i of sequence b sits at position T_b - n_b + i and attends over
+ * positions 0 .. T_b - n_b + i; query head h reads kv head h / g:
+ *     o[qo_indptr[b] + i, h] = softmax_{t <= T_b - n_b + i}(q[qo_indptr[b] + i, h] . K[t] / sqrt(128)) V[t],   no RoPE,
+ * scores on the exact 4-bit codes (K is never rounded to 16 bit), softmax in fp32, the weights p_t s_t rounded once to `dtype` for the
+ * matrix cores (fp16: a weight below 2^-14 is rounded on the subnormal grid, 2^-25 absolute), one rounding of the result to `dtype`.
+ * n_b = 1 for every b is arcq_kv_batch_decode's contract; n_b = 0 writes nothing for that sequence; rows of o at or beyond qo_indptr[B]
+ * are not written, and nothing else is.  B == 0 or ntok == 0 returns ARCQ_OK without a launch.  ARCQ_KV_INT4 only (ARCQ_KV_16BIT:
+ * ARCQ_ERR_UNSUPPORTED).  No workspace, no state, no host read of a device table: the call can be captured into a HIP graph.
+ * nnz = entries of kv_indices (range-checked only).
+ * KNOWN LIMIT: the kv range of a sequence is not split over workgroups.  A launch has one workgroup per (sequence, kv head, 128 / g query
+ * tokens), so a few query tokens over a very long cache (speculative verification at batch size 1) run on B * N workgroups. */
+int arcq_kv_batch_prefill(void *o, const void *q, const int32_t *qo_indptr, const void *kv_data, const void *kv_param,
+                          const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int64_t ntok, int64_t B,
+                          int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *stream);
+
 /* Bytes of the decode step's state: one int32 arrival counter per (sequence, kv head, chunk of <= 4 of its g = Nq / N query heads). */
 int64_t arcq_kv_decode_step_state_bytes(int64_t B, int64_t Nq, int64_t N);
 
