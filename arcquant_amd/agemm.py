@@ -131,6 +131,17 @@ def _same_device(who: str, A: torch.Tensor, *ts):
             raise RuntimeError(f"agemm.{who}: every operand must live on the GPU of the first one ({A.device}), got {t.device}")
 
 
+def _debug_set_tile_overlap_tail(mode: int) -> None:
+    """DEBUG / tests: which launches of the LDS-tiled GEMM take the kernel whose output stores leave under its last K step
+    (arcq_debug_set_tile_overlap_tail): 0 never, 1 the 256 x 256 tile's launches of whole tiles except SiLU * up (the default), 2 whenever
+    legal: SiLU * up too, and every shape made of whole 256 x 256 tiles takes that tile, whatever the routes and heuristics would choose.
+    Process-wide; read at every launch."""
+    fn = _lib.lib().arcq_debug_set_tile_overlap_tail
+    fn.restype, fn.argtypes = None, [_lib._i32]
+    fn(int(mode))
+    rw_route.cache_clear()                          # (the route of a shape depends on the mode)
+
+
 @functools.lru_cache(maxsize=None)
 def variant_for_kq(KQ: int) -> int:
     """Layout variant the reference's dispatch picks for this in_features (bindings.cpp:141-160)."""

@@ -168,6 +168,10 @@ int64_t gemm_decode_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int gemm_decode(const GemmArgs& a, hipStream_t stream);   // M <= 16, many tiles: 32-row tiles, two units per thread and item
 int gemm_tile(const GemmArgs& a, hipStream_t stream);     // general M: LDS-tiled MFMA GEMM (either B layout)
 int gemm_tile_repacked(const GemmArgs& a, hipStream_t stream);   // gemm_tile_rw.hip: its B = RW / RSF instantiations (called by gemm_tile)
+// gemm_tile_ot.hip: the value of arcq_debug_set_tile_overlap_tail (0 never, 1 by launch_tile's rule, 2 whenever legal).  Under 2 a shape
+// made of whole 256 x 256 tiles takes the LDS-tiled kernel's 256 x 256 8-wave tile whatever the routes and heuristics say (tests)
+int tile_overlap_tail_mode();
+inline bool tile_overlap_tail_forced(int64_t M, int64_t N) { return tile_overlap_tail_mode() == 2 && M % 256 == 0 && N % 256 == 0; }
 // gemm_regtile.hip: 16 < M <~ 1024, grids the tiled kernel cannot fill: operand fragments straight into registers, K split over waves
 int gemm_regtile_cfg(int64_t M, int64_t N, int64_t K, int epilogue);   // 0 = not this kernel, else its configuration
 int gemm_regtile(const GemmArgs& a, int cfg, hipStream_t stream);        // either B layout

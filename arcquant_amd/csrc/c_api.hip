@@ -153,6 +153,7 @@ static bool use_decode_v2(int64_t N) {
 
 int64_t arcq_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
+  if (tile_overlap_tail_forced(M, N)) return gemm_tile_workspace_bytes(M, N, K);      // (debug setter: whole 256 x 256 tiles take the LDS-tiled kernel)
   if (gemm_regtile_cfg(M, N, K, kEpiPlain)) return 0;
   if (M <= kSkinnyMaxM) return use_decode_v2(N) ? gemm_decode_workspace_bytes(M, N, K) : gemm_skinny_workspace_bytes(M, N, K);
   return gemm_tile_workspace_bytes(M, N, K);
@@ -165,6 +166,7 @@ int arcq_gemm_nvfp4(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, cons
   const int rc = gemm_checks(r, A, B, SFA, SFB, D, nullptr, M, N, K, bias, residual, out_dtype);
   if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
   const GemmArgs a = gemm_args(A, B, SFA, SFB, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, workspace, workspace_bytes);
+  if (tile_overlap_tail_forced(M, N)) return gemm_tile(a, (hipStream_t)stream);
   if (const int cfg = gemm_regtile_cfg(M, N, K, kEpiPlain)) return gemm_regtile(a, cfg, (hipStream_t)stream);
   if (M <= kSkinnyMaxM) return use_decode_v2(N) ? gemm_decode(a, (hipStream_t)stream) : gemm_skinny(a, (hipStream_t)stream);
   return gemm_tile(a, (hipStream_t)stream);
@@ -241,6 +243,7 @@ static const int kRwDecodeCfg = 9;
 static int rw_route(int64_t M, int64_t N, int64_t K, bool epi_aligned, int* cfg) {
   *cfg = 0;
   if (M <= 0 || N <= 0 || K <= 0 || (K % 64) || M > INT32_MAX / 2 || N > INT32_MAX / 2 || K > INT32_MAX / 2 || M * N > ((int64_t)1 << 40)) return 0;
+  if (tile_overlap_tail_forced(M, N)) return 3;
   if (epi_aligned && gemm_repacked_supported(M, N, K)) return 1;
   *cfg = gemm_regtile_cfg(M, N, K, kEpiPlain);
   if (*cfg == 0 && M <= kSkinnyMaxM) *cfg = kRwDecodeCfg;

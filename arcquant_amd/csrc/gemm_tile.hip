@@ -31,9 +31,11 @@ namespace arcq {
 // (MI355X_MICROARCH.md, "DVFS give-back" item 6) and the phases of a tile, stamped by wave 0 of every workgroup into a buffer
 // nothing else reads (tools/tile_clock.py): kTileStamps (s_memtime, s_memrealtime) pairs per workgroup -- 0 kernel entry, 1 K loop
 // starts, 2 K loop ends, 3 first output store issued, 4 last output store issued.  The product library has no stamps.
+#ifndef ARCQ_TILE_OT_UNIT
 static unsigned long long* g_tile_stamps = nullptr;     // (stays NULL in gemm_tile_rw.hip: its kernels are not stamped)
 #ifndef ARCQ_TILE_REPACKED_UNIT
 extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpret_cast<unsigned long long*>(p); }
+#endif
 #endif
 #define ARCQ_TILE_STAMP(k)                                                                                     \
   do {                                                                                                         \
@@ -73,8 +75,27 @@ extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpre
 // staging block, each taken by one group (every wave still meets one barrier per step): no code is duplicated.
 // kBLayout: kBRef = B / SFB in the reference layout, kBRepacked = the RW / RSF of arcq.h.  Only the addresses of B's staging loads
 // differ: the staged bytes, the LDS image, the K order and every MFMA are the same, so the two produce identical sums.
+//
+// ONE body, two kernels.  gemm_tile_ot.hip compiles this body a second time as gemm_tile_ot_kernel, with kOverlapTail set (interior tiles
+// of the rotated 256 x 256 8-wave step only): the last K step of the range is a FINAL step -- no loads, no staging, no barrier, pair-outer
+// MFMA order -- and the interior epilogue of a pair of row tiles is issued under the MFMAs of the next pair, so that output leaves while
+// the matrix pipe still works.  Every accumulator still takes its K half 0 MFMA before its K half 1 one and the epilogue's operations are
+// interior_epilogue's in its order: identical bits.  kEpiOps: the epilogue operands of such a launch, bit 0 bias, bit 1 residual -- the
+// sibling has ONE epilogue, chosen by the launcher (four straight-line copies of the final step behind uniform branches left hipcc's
+// register allocation with spills).  (The body as a __device__ __forceinline__ function called by both kernels made hipcc generate other
+// code for every kernel of this file, 0.3 - 0.9 % slower on the model's shapes: DESIGN.md 3.2.  Under two headers gemm_tile_kernel's code
+// is what it was.)
+#ifndef ARCQ_TILE_OT_UNIT
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool kMfma32, int kEpi, bool kStagger, bool kPipe, int kBLayout = kBRef>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TileParams p) {
+  constexpr bool kOverlapTail = false;
+  [[maybe_unused]] constexpr int kEpiOps = 0;
+#else
+template <int BM, int BN, int WAVES_M, int WAVES_N, int kEpi, int kBLayout, int kEpiOps>
+__global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(TileParams p) {
+  static_assert(kEpiOps >= 0 && kEpiOps < (kEpi == kEpiSiluMul ? 2 : 4), "bit 0 bias, bit 1 residual (SiLU * up has no residual)");
+  constexpr bool kMfma32 = false, kStagger = false, kPipe = true, kOverlapTail = true;
+#endif
   constexpr int kThreads = WAVES_M * WAVES_N * 64;
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;     // wave tile
   constexpr int kT = kMfma32 ? 32 : 16;                   // MFMA tile edge
@@ -182,12 +203,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
   const int fa_base = kMfma32 ? lds_slot32(wr * WM + (lane & 31), lane >> 5) : lds_slot(wr * WM + (lane & 15), lane >> 4);
   const int fb_base = kMfma32 ? lds_slot32(wc * WN + (lane & 31), lane >> 5) : lds_slot(wc * WN + (lane & 15), lane >> 4);
   acc_t acc[TM][TN];
+  if constexpr (!kOverlapTail) {                // (kOverlapTail: zeroed behind the prologue's loads, while they are in flight)
 #pragma unroll
-  for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
+      for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int r = 0; r < (kMfma32 ? 16 : 4); ++r) acc[i][j][r] = 0.f;
+        for (int r = 0; r < (kMfma32 ? 16 : 4); ++r) acc[i][j][r] = 0.f;
+  }
 
   Staged sa[A_UNITS], sb[B_UNITS];     // registers holding step kt+1 while step kt is multiplied
   auto load_step = [&](int atom) {
@@ -470,6 +493,16 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
   for (int u = 0; u < B_UNITS; ++u) sb0[u] = sb[u];
   load_step(min(a_begin + 1, a_end - 1));
   __builtin_amdgcn_sched_barrier(0);            // keep the second set of loads above the first wait
+  if constexpr (kOverlapTail) {                 // the accumulators are zeroed while the first loads are in flight, not between their arrival and the first MFMA
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        acc[i][j] = acc_t{};
+        asm volatile("" : "+v"(acc[i][j]));     // (written here: left free, the zeros are materialised in front of the loop)
+      }
+    __builtin_amdgcn_sched_barrier(0);
+  }
 #pragma unroll
   for (int u = 0; u < A_UNITS; ++u)
     if (!A_PARTIAL || tid < BM * 2) stage_store(lds_a0, a_slot[u], sa0[u], a_live[u]);
@@ -499,7 +532,20 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
   // priority; a static priority for it (never flipped) measured +0.8 % (1192-1203 -> 1209-1212 TFLOP/s)
   if (WAVES_M * WAVES_N == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
   ARCQ_TILE_STAMP(1);
-  if constexpr (kPipe) {
+  [[maybe_unused]] int tail_buf = 0;            // kOverlapTail: byte offset of the LDS buffer that holds the range's last step
+  if constexpr (kOverlapTail) {
+    // the unchanged step pairs while at least three steps remain, one more unchanged step if two remain; the range's last step is
+    // multiplied by the final step (inside the interior epilogue below) from whichever buffer it was staged into
+    static_assert(kRotate, "the final step is entered with head fragments");
+    for (; kt + 2 < a_end; kt += 2) {
+      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1);
+      k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0);
+    }
+    if (kt + 1 < a_end) {
+      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1);
+      tail_buf = A_TILE + B_TILE;
+    }
+  } else if constexpr (kPipe) {
     for (; kt + 1 < a_end; kt += 2) {
       k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1);
       k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0);
@@ -512,7 +558,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
     }
     if (kt < a_end) k_step(kt, lds_a0, lds_b0, lds_a1, lds_b1);
   }
-  ARCQ_TILE_STAMP(2);
+  if constexpr (!kOverlapTail) ARCQ_TILE_STAMP(2);      // (kOverlapTail: behind the final step's last MFMA)
 
   // ---- epilogue.  16x16 tiles: lane holds D[m = +(lane & 15)][n = +4*(lane >> 4) + r], r = 0..3.
   //      32x32 tiles: lane holds D[m = +(lane & 31)][n = +8*g + 4*(lane >> 5) + r], g = 0..3, r = 0..3.
@@ -546,13 +592,20 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
     [[maybe_unused]] const uint32_t g4 = (t >> 4) & 3;
     [[maybe_unused]] uint32_t off_w = off - 4 * g4 + ((g4 & 1) ? 16 + 4 * (g4 - 1) : 4 * g4);
     [[maybe_unused]] uint2 held = make_uint2(0, 0);
+    // (kOverlapTail with both operands: the bias quads stay packed and are unpacked per use -- 8 registers fewer beside the fragments)
+    constexpr bool kPackedBias = kOverlapTail && kBias && kRes;
     float bias_f[TN][4];
+    [[maybe_unused]] uint2 bias_v[TN];
     if constexpr (kBias) {
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const uint2 b = *reinterpret_cast<const uint2*>(p.bias + n0 + lane_col + j * 16);
-        bias_f[j][0] = bf16_bits_to_f32(b.x & 0xffffu); bias_f[j][1] = bf16_bits_to_f32(b.x >> 16);
-        bias_f[j][2] = bf16_bits_to_f32(b.y & 0xffffu); bias_f[j][3] = bf16_bits_to_f32(b.y >> 16);
+        if constexpr (kPackedBias) {
+          bias_v[j] = b;
+        } else {
+          bias_f[j][0] = bf16_bits_to_f32(b.x & 0xffffu); bias_f[j][1] = bf16_bits_to_f32(b.x >> 16);
+          bias_f[j][2] = bf16_bits_to_f32(b.y & 0xffffu); bias_f[j][3] = bf16_bits_to_f32(b.y >> 16);
+        }
       }
     }
     uint2 res_cur[TN], res_nxt[TN];
@@ -561,11 +614,15 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
       for (int j = 0; j < TN; ++j) r[j] = *reinterpret_cast<const uint2*>(tile_r + (size_t)o * 2 + j * 32);
     };
     if constexpr (kRes) res_load(off, res_cur);
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      if constexpr (kRes) { if (i + 1 < TM) res_load(off + row_step, res_nxt); }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
+    // row tile i is finished and stored as: the residual quads of row tile i + 1 requested, its TN quads, the row offsets advanced
+    auto row_quad = [&](int i, int j) __attribute__((always_inline)) {
+      {
+        if constexpr (kPackedBias) {
+          uint2 b = bias_v[j];
+          asm volatile("" : "+v"(b.x), "+v"(b.y));
+          bias_f[j][0] = bf16_bits_to_f32(b.x & 0xffffu); bias_f[j][1] = bf16_bits_to_f32(b.x >> 16);
+          bias_f[j][2] = bf16_bits_to_f32(b.y & 0xffffu); bias_f[j][3] = bf16_bits_to_f32(b.y >> 16);
+        }
         float d[4] = {alpha * acc[i][j][0], alpha * acc[i][j][1], alpha * acc[i][j][2], alpha * acc[i][j][3]};
         if constexpr (kSilu) {
           if constexpr (kBias) {
@@ -616,12 +673,83 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
         }
         if (i == 0 && j == 0) ARCQ_TILE_STAMP(3);
       }
-      if constexpr (kRes) {
+    };
+    if constexpr (!kOverlapTail) {
 #pragma unroll
-        for (int j = 0; j < TN; ++j) res_cur[j] = res_nxt[j];
+      for (int i = 0; i < TM; ++i) {
+        if constexpr (kRes) { if (i + 1 < TM) res_load(off + row_step, res_nxt); }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) row_quad(i, j);
+        if constexpr (kRes) {
+#pragma unroll
+          for (int j = 0; j < TN; ++j) res_cur[j] = res_nxt[j];
+        }
+        off += row_step;
+        off_w += row_step;
       }
-      off += row_step;
-      off_w += row_step;
+    } else {
+      auto row_open = [&](int i) __attribute__((always_inline)) {
+        if constexpr (kRes) { if (i + 1 < TM) res_load(off + row_step, res_nxt); }
+      };
+      auto row_close = [&]() __attribute__((always_inline)) {
+        if constexpr (kRes) {
+#pragma unroll
+          for (int j = 0; j < TN; ++j) res_cur[j] = res_nxt[j];
+        }
+        off += row_step;
+        off_w += row_step;
+      };
+      // FINAL step: multiplies the range's last K step from the buffer it was staged into (tail_buf) and stages nothing -- no load, no
+      // LDS write, no barrier (nobody writes LDS any more) and no head reads.  Entered like any rotated step, with B's K half 0 and the
+      // first A pair in registers.  Pair-outer: block b = K half (b & 1) of row tiles 2 (b >> 1), 2 (b >> 1) + 1, so a pair of row tiles is
+      // final after its second block, and row tile b - 2 is finished and stored in the shadow of block b's MFMAs: one quad behind every
+      // two MFMAs, fenced, so that no more than a quad's values are live beside the fragments.  Each accumulator still takes K half 0
+      // before K half 1.  Fragment reads: B's K half 1 first, then A one block ahead (counted lgkmcnt waits).
+      // SiLU * up keeps its epilogue behind the final step: under the MFMAs its exp / divide work measured SLOWER than the kept kernel
+      // (DESIGN.md 3.2), so its sibling has the unstaged final step and the early zeroing alone.
+      constexpr int kQ = TM;
+      constexpr bool kUnder = !kSilu;
+      constexpr int kValu = 3 + (kBias ? 5 : 0) + (kRes ? 7 : 0);     // half a quad's vector instructions: between its two MFMAs
+      const unsigned char* const fla = lds_a0 + tail_buf;
+      const unsigned char* const flb = lds_b0 + tail_buf;
+      Frag8 fb1[TN], fq[kQ][2];
+      fq[0][0] = head_a[0];
+      fq[0][1] = head_a[1];
+#pragma unroll
+      for (int j = 0; j < TN; ++j) fb1[j] = rd_frag(flb, fb_base, 1, j);
+#pragma unroll
+      for (int b = 0; b < kQ; ++b) {
+        if (b + 1 < kQ) {
+          fq[b + 1][0] = rd_frag(fla, fa_base, (b + 1) & 1, 2 * ((b + 1) >> 1));
+          fq[b + 1][1] = rd_frag(fla, fa_base, (b + 1) & 1, 2 * ((b + 1) >> 1) + 1);
+        }
+        if (kUnder && b >= 2) row_open(b - 2);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s = 0; s < TN; ++s) {
+#pragma unroll
+          for (int m8 = 2 * s; m8 < 2 * s + 2; ++m8)          // (the block's MFMAs in the order of every step: row tile outer, column tile inner)
+            if constexpr (!kMfma32)
+              acc[2 * (b >> 1) + m8 / TN][m8 % TN] = __builtin_amdgcn_mfma_f32_16x16x32_f16(((b & 1) ? fb1[m8 % TN] : head_b[m8 % TN]).v, fq[b][m8 / TN].v,
+                                                                                             acc[2 * (b >> 1) + m8 / TN][m8 % TN], 0, 0, 0);
+          if (kUnder && b >= 2) {
+            row_quad(b - 2, s);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, kValu, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (kUnder && b >= 2) row_close();
+      }
+      ARCQ_TILE_STAMP(2);
+#pragma unroll
+      for (int i = kUnder ? TM - 2 : 0; i < TM; ++i) {
+        row_open(i);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) row_quad(i, j);
+        row_close();
+      }
     }
   };
   // `pre`: the four bias / residual values of (m, n .. n + 3) already fetched with ONE 8-byte load each (N % 4 == 0), two bf16 per dword;
@@ -675,11 +803,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
 #else
   constexpr bool kInteriorPath = !kMfma32;
 #endif
-  bool interior = false;
-  if constexpr (kInteriorPath)
+  static_assert(!kOverlapTail || kInteriorPath, "the final step carries the interior epilogue");
+  bool interior = false;                      // (kOverlapTail: the launcher sends launches of interior tiles only; no other epilogue is compiled in)
+  if constexpr (kInteriorPath && !kOverlapTail)
     interior = m0 + BM <= p.M && n0 + BN <= p.N && vec_ok && p.splits <= 1 && p.out_dtype == ARCQ_OUT_BF16 && (int64_t)BM * p.N < (1ll << 31) &&
                ((reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.residual)) & 7) == 0;
-  if (interior) {
+  if constexpr (kOverlapTail) {
+    interior_epilogue(std::bool_constant<(kEpiOps & 1) != 0>{}, std::bool_constant<(kEpiOps & 2) != 0>{});
+  } else if (interior) {
     if constexpr (kInteriorPath) {
       using T = std::true_type;
       using F = std::false_type;
@@ -764,6 +895,39 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TilePa
   }
 }
 
+#ifdef ARCQ_TILE_OT_UNIT
+static int g_tile_overlap_tail = 1;
+int tile_overlap_tail_mode() { return g_tile_overlap_tail; }
+// DEBUG / test control, read at every launch: 0 = never take the sibling, 1 = launches of the 256 x 256 8-wave tile whose tiles are all
+// interior (launch_tile; not SiLU * up), 2 = whenever legal: SiLU * up too, and every shape with M % 256 == 0 and N % 256 == 0 takes that
+// tile, whatever the routes and heuristics say
+extern "C" void arcq_debug_set_tile_overlap_tail(int mode) { g_tile_overlap_tail = mode < 0 ? 0 : mode > 2 ? 2 : mode; }
+
+template <int kEpi, int kBLayout, int kEpiOps>
+static int launch_ot(const TileParams& p, dim3 grid, hipStream_t stream) {
+  return launch_kernel<gemm_tile_ot_kernel<256, 256, 2, 4, kEpi, kBLayout, kEpiOps>>(grid, dim3(512), 2 * (256 + 256) * kRowBytes, stream,
+                                                                                   "arcq_gemm_nvfp4 (tile, overlapped tail)", p);
+}
+template <int kEpi, int kBLayout>
+static int launch_ot_ops(const TileParams& p, dim3 grid, hipStream_t stream) {
+  const int ops = (p.bias ? 1 : 0) | (p.residual ? 2 : 0);
+  if constexpr (kEpi == kEpiSiluMul) {
+    return ops & 1 ? launch_ot<kEpi, kBLayout, 1>(p, grid, stream) : launch_ot<kEpi, kBLayout, 0>(p, grid, stream);
+  } else {
+    switch (ops) {
+      case 1: return launch_ot<kEpi, kBLayout, 1>(p, grid, stream);
+      case 2: return launch_ot<kEpi, kBLayout, 2>(p, grid, stream);
+      case 3: return launch_ot<kEpi, kBLayout, 3>(p, grid, stream);
+      default: return launch_ot<kEpi, kBLayout, 0>(p, grid, stream);
+    }
+  }
+}
+int launch_tile_overlap_tail(const TileParams& p, int epi, int b_layout, dim3 grid, hipStream_t stream) {
+  if (epi == kEpiSiluMul) return b_layout == kBRepacked ? launch_ot_ops<kEpiSiluMul, kBRepacked>(p, grid, stream) : launch_ot_ops<kEpiSiluMul, kBRef>(p, grid, stream);
+  return b_layout == kBRepacked ? launch_ot_ops<kEpiPlain, kBRepacked>(p, grid, stream) : launch_ot_ops<kEpiPlain, kBRef>(p, grid, stream);
+}
+#else
+
 // ---- tile configurations --------------------------------------------------------------------------------------------------
 // id = the value of ARCQ_TILE_CFG that forces it (debug / tuning only; 0 = heuristic).
 //   1 = 128x128 (4 waves), 2 = 256x256 (4 waves), 3 = 256x256 (8 waves), 4 = 128x256 (4 waves), 5 / 6 = 32x32x16 MFMA variants of
@@ -844,7 +1008,15 @@ static int launch_tile(const GemmArgs& a, hipStream_t stream, bool allow_split =
   constexpr bool kCanStagger = WAVES_M * WAVES_N == 8 && BM == 256 && BN == 256;
   const bool pipe = tile_pipe(), stagger = !pipe && kCanStagger && tile_stagger();      // the variants of the instantiation
   int rc;
-  if (!pipe && !stagger) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false, kBLayout>>(grid, block, lds, stream, who, p);
+  // the kOverlapTail sibling (gemm_tile_ot.hip) takes the rotated 256 x 256 8-wave step's launches whose tiles are ALL interior: the
+  // kernel's own `interior` test, made once for the launch.  SiLU * up launches take theirs only under the debug setter's 2: it has not
+  // measured faster than the kept kernel
+  bool overlap_tail = false;
+  if constexpr (BM == 256 && BN == 256 && WAVES_M * WAVES_N == 8 && !kMfma32 && !ARCQ_TILE_BARRIER_AT_STEP_END)
+    overlap_tail = pipe && (kEpi == kEpiSiluMul ? tile_overlap_tail_mode() == 2 : tile_overlap_tail_mode() != 0) && a.M % BM == 0 && a.N % BN == 0 && p.splits <= 1 && a.out_dtype == ARCQ_OUT_BF16 &&
+                   (int64_t)BM * a.N < (1ll << 31) && ((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.residual)) & 7) == 0;
+  if (overlap_tail) rc = launch_tile_overlap_tail(p, kEpi, kBLayout, grid, stream);
+  else if (!pipe && !stagger) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false, kBLayout>>(grid, block, lds, stream, who, p);
   else if (pipe) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, true, kBLayout>>(grid, block, lds, stream, who, p);
   else rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, kCanStagger, false, kBLayout>>(grid, block, lds, stream, who, p);
   if (rc != ARCQ_OK) return rc;
@@ -871,7 +1043,7 @@ static int tile_choice(int64_t M, int64_t N, int64_t K) {
 // the configuration a launch uses, and whether it may split K (the silu-mul epilogue never does; 2 - 6 and 9 are the unsplit tuning arms)
 static int effective_cfg(int64_t M, int64_t N, int64_t K, bool* may_split) {
   int id = tile_cfg_override();
-  if (id == 0) id = tile_choice(M, N, K);
+  if (id == 0) id = tile_overlap_tail_forced(M, N) ? 3 : tile_choice(M, N, K);
   id = tile_cfg(id).id;
   *may_split = !(id >= 2 && id <= 6) && id != 9;
   return id;
@@ -928,5 +1100,6 @@ int gemm_tile_repacked(const GemmArgs& a, hipStream_t stream) {
   return a.epilogue == kEpiSiluMul ? gemm_tile_epi<kEpiSiluMul, kBRepacked>(a, stream) : gemm_tile_epi<kEpiPlain, kBRepacked>(a, stream);
 }
 #endif
+#endif  // ARCQ_TILE_OT_UNIT
 
 }  // namespace arcq

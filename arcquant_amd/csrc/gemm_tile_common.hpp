@@ -35,6 +35,8 @@ struct TileParams {
 #endif
 };
 constexpr int kTileStamps = 5;          // kernel entry, K loop starts, K loop ends, first / last output store issued (gemm_tile.hip)
+// gemm_tile_ot.hip: launches gemm_tile_ot_kernel<256, 256, 2, 4, epi, b_layout> (the caller has checked that the launch is eligible)
+int launch_tile_overlap_tail(const TileParams& p, int epi, int b_layout, dim3 grid, hipStream_t stream);
 
 constexpr int kBK = 64;                 // K elements per step = one scale-factor atom column (4 groups)
 constexpr int kRowBytes = kBK * 2;      // fp16 row of a tile in LDS
