@@ -142,6 +142,15 @@ def _debug_set_tile_overlap_tail(mode: int) -> None:
     rw_route.cache_clear()                          # (the route of a shape depends on the mode)
 
 
+def _debug_set_tile_pair_loads(on: int) -> None:
+    """DEBUG / tests: whether a launch that takes the overlapped-tail kernel with the plain epilogue takes its paired-load sibling, which
+    requests a row's two following K atoms back to back (arcq_debug_set_tile_pair_loads): 1 yes (the default), 0 no.  Process-wide; read
+    at every launch.  Which launches are eligible stays _debug_set_tile_overlap_tail's rule."""
+    fn = _lib.lib().arcq_debug_set_tile_pair_loads
+    fn.restype, fn.argtypes = None, [_lib._i32]
+    fn(int(on))
+
+
 @functools.lru_cache(maxsize=None)
 def variant_for_kq(KQ: int) -> int:
     """Layout variant the reference's dispatch picks for this in_features (bindings.cpp:141-160)."""

@@ -172,6 +172,9 @@ int gemm_tile_repacked(const GemmArgs& a, hipStream_t stream);   // gemm_tile_rw
 // made of whole 256 x 256 tiles takes the LDS-tiled kernel's 256 x 256 8-wave tile whatever the routes and heuristics say (tests)
 int tile_overlap_tail_mode();
 inline bool tile_overlap_tail_forced(int64_t M, int64_t N) { return tile_overlap_tail_mode() == 2 && M % 256 == 0 && N % 256 == 0; }
+// gemm_tile_pl.hip: the value of arcq_debug_set_tile_pair_loads (1, the default: a launch that is eligible for the overlapped tail with
+// the plain epilogue takes the paired-load sibling; 0: it takes gemm_tile_ot_kernel)
+int tile_pair_loads_mode();
 // gemm_regtile.hip: 16 < M <~ 1024, grids the tiled kernel cannot fill: operand fragments straight into registers, K split over waves
 int gemm_regtile_cfg(int64_t M, int64_t N, int64_t K, int epilogue);   // 0 = not this kernel, else its configuration
 int gemm_regtile(const GemmArgs& a, int cfg, hipStream_t stream);        // either B layout

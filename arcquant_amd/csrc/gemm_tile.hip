@@ -24,6 +24,10 @@
 #include "gemm_common.hpp"
 #include "gemm_tile_common.hpp"
 
+#if defined(ARCQ_TILE_OT_UNIT) || defined(ARCQ_TILE_PL_UNIT)
+#define ARCQ_TILE_SIBLING_UNIT       // a unit that compiles the body below as ONE sibling kernel with launchers of its own
+#endif
+
 namespace arcq {
 
 #ifdef ARCQ_STREAM_STAMPS
@@ -31,7 +35,7 @@ namespace arcq {
 // (MI355X_MICROARCH.md, "DVFS give-back" item 6) and the phases of a tile, stamped by wave 0 of every workgroup into a buffer
 // nothing else reads (tools/tile_clock.py): kTileStamps (s_memtime, s_memrealtime) pairs per workgroup -- 0 kernel entry, 1 K loop
 // starts, 2 K loop ends, 3 first output store issued, 4 last output store issued.  The product library has no stamps.
-#ifndef ARCQ_TILE_OT_UNIT
+#ifndef ARCQ_TILE_SIBLING_UNIT
 static unsigned long long* g_tile_stamps = nullptr;     // (stays NULL in gemm_tile_rw.hip: its kernels are not stamped)
 #ifndef ARCQ_TILE_REPACKED_UNIT
 extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpret_cast<unsigned long long*>(p); }
@@ -85,16 +89,31 @@ extern "C" void arcq_debug_set_tile_stamps(void* p) { g_tile_stamps = reinterpre
 // register allocation with spills).  (The body as a __device__ __forceinline__ function called by both kernels made hipcc generate other
 // code for every kernel of this file, 0.3 - 0.9 % slower on the model's shapes: DESIGN.md 3.2.  Under two headers gemm_tile_kernel's code
 // is what it was.)
-#ifndef ARCQ_TILE_OT_UNIT
+//
+// A THIRD header, gemm_tile_pl.hip: gemm_tile_pl_kernel is the kOverlapTail sibling with kPairLoads set.  The staging loads of a row
+// take 32 B of a 128-B line per K atom, a row per lane pair, so one wave-instruction touches 32 lines and the next atom of the same
+// rows comes a whole K step later.  With kPairLoads the EVEN step of a pair of steps requests the code bytes of BOTH following atoms
+// (kt + 2 and kt + 3), per unit back to back through the same descriptor and lane offset -- A's pair at the top of the step, B's ahead
+// of block 2, the four scale loads ahead of block 4 -- and the ODD step requests nothing: still 8 loads per two steps, all ahead of the
+// even step's barrier, every address formed the same way (clamped atom, inside the descriptor), but a row's two requests reach the
+// vector L1 together (36 % fewer read requests to L2 per launch: profiles/tile_pair_loads_pmc.json).  A third register set (sa2 / sb2)
+// holds atom kt + 2 across the even step; the odd step stages from it.  The staged bytes, the pieces and their blocks, the barrier, the
+// LDS image, the K and MFMA order, the final step and the epilogue are the sibling's: identical bits.
+#if defined(ARCQ_TILE_PL_UNIT)
+template <int BM, int BN, int WAVES_M, int WAVES_N, int kEpi, int kBLayout, int kEpiOps>
+__global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_pl_kernel(TileParams p) {
+  static_assert(kEpi == kEpiPlain && kEpiOps >= 0 && kEpiOps < 4, "bit 0 bias, bit 1 residual (SiLU * up keeps gemm_tile_ot_kernel)");
+  constexpr bool kMfma32 = false, kStagger = false, kPipe = true, kOverlapTail = true, kPairLoads = true;
+#elif !defined(ARCQ_TILE_OT_UNIT)
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool kMfma32, int kEpi, bool kStagger, bool kPipe, int kBLayout = kBRef>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_kernel(TileParams p) {
-  constexpr bool kOverlapTail = false;
+  constexpr bool kOverlapTail = false, kPairLoads = false;
   [[maybe_unused]] constexpr int kEpiOps = 0;
 #else
 template <int BM, int BN, int WAVES_M, int WAVES_N, int kEpi, int kBLayout, int kEpiOps>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(TileParams p) {
   static_assert(kEpiOps >= 0 && kEpiOps < (kEpi == kEpiSiluMul ? 2 : 4), "bit 0 bias, bit 1 residual (SiLU * up has no residual)");
-  constexpr bool kMfma32 = false, kStagger = false, kPipe = true, kOverlapTail = true;
+  constexpr bool kMfma32 = false, kStagger = false, kPipe = true, kOverlapTail = true, kPairLoads = false;
 #endif
   constexpr int kThreads = WAVES_M * WAVES_N * 64;
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;     // wave tile
@@ -221,6 +240,56 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(Til
 #pragma unroll
     for (int u = 0; u < B_UNITS; ++u) sb[u] = stage_load(b_src, b_q[u], b_sf[u], sb_step);
   };
+#ifdef ARCQ_TILE_PL_UNIT
+  // kPairLoads: two atoms requested together.  Per unit the 16 code bytes of atom0 and directly behind them those of atom1 (the same line
+  // of the row, or the next one), fenced so that hipcc keeps each pair adjacent and in that order.  kParts selects what one call issues:
+  // bit 0 A's code pairs, bit 1 B's, bit 2 the scale loads of both operands -- the prologue issues all of it at once, the even step one
+  // part per place (all eight loads of a wave in ONE burst at the top of the step measured SLOWER than the parent: DESIGN.md 3.2).
+  // (Declared in this unit alone: an unused third register set and lambda moved instructions in the other units' kernels.)
+  Staged sa2[A_UNITS], sb2[B_UNITS];   // atom kt + 2 across the even step (sa / sb receive atom kt + 3)
+  auto load_pair = [&](int atom0, int atom1, Staged (&a0)[A_UNITS], Staged (&b0)[B_UNITS], Staged (&a1)[A_UNITS], Staged (&b1)[B_UNITS], auto parts) {
+    constexpr int kParts = decltype(parts)::value;
+    atom0 = __builtin_amdgcn_readfirstlane(atom0);
+    atom1 = __builtin_amdgcn_readfirstlane(atom1);
+    const StageStep a_s0 = stage_step(atom0), a_s1 = stage_step(atom1);
+    const StageStep b_s0 = kBLayout == kBRepacked ? stage_step_rw(atom0) : a_s0, b_s1 = kBLayout == kBRepacked ? stage_step_rw(atom1) : a_s1;
+    __builtin_amdgcn_sched_barrier(0);            // (the scalar offsets are formed ahead of the first pair, not inside one)
+    if constexpr ((kParts & 1) != 0) {
+#pragma unroll
+      for (int u = 0; u < A_UNITS; ++u) {
+        a0[u].q = stage_load_q(a_src, a_q[u], a_s0);
+        __builtin_amdgcn_sched_barrier(0);
+        a1[u].q = stage_load_q(a_src, a_q[u], a_s1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if constexpr ((kParts & 2) != 0) {
+#pragma unroll
+      for (int u = 0; u < B_UNITS; ++u) {
+        b0[u].q = stage_load_q(b_src, b_q[u], b_s0);
+        __builtin_amdgcn_sched_barrier(0);
+        b1[u].q = stage_load_q(b_src, b_q[u], b_s1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if constexpr ((kParts & 4) != 0) {
+#pragma unroll
+      for (int u = 0; u < A_UNITS; ++u) {
+        a0[u].sf = stage_load_sf(a_src, a_sf[u], a_s0);
+        a1[u].sf = stage_load_sf(a_src, a_sf[u], a_s1);
+      }
+#pragma unroll
+      for (int u = 0; u < B_UNITS; ++u) {
+        b0[u].sf = stage_load_sf(b_src, b_sf[u], b_s0);
+        b1[u].sf = stage_load_sf(b_src, b_sf[u], b_s1);
+      }
+    }
+  };
+  using kPairA = std::integral_constant<int, 1>;
+  using kPairB = std::integral_constant<int, 2>;
+  using kPairSf = std::integral_constant<int, 4>;
+  using kPairAll = std::integral_constant<int, 7>;
+#endif
   auto store_step = [&](unsigned char* la, unsigned char* lb) {
 #pragma unroll
     for (int u = 0; u < A_UNITS; ++u)
@@ -293,14 +362,32 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(Til
   constexpr bool kRotate = !ARCQ_TILE_BARRIER_AT_STEP_END && kPipe && !kMfma32 && TM == 8 && TN == 4 && WAVES_M * WAVES_N == 8 && !A_PARTIAL && !B_PARTIAL;
   auto rd_frag = [&](const unsigned char* tile, int base, int ks, int i) { Frag8 f; f.u = *reinterpret_cast<const uint4*>(tile + (base ^ (ks * 64)) + i * 16 * kRowBytes); return f; };
   [[maybe_unused]] Frag8 head_b[TN], head_a[2];   // kRotate: the fragments a step is entered with, carried across the loop's back-edge
-  auto k_step_pipe = [&](int kt, unsigned char* ca, unsigned char* cb, unsigned char* na, unsigned char* nb) {
+  // what a step requests and which registers it stages from.  kStepOne: atom kt + 2 into sa / sb, staging what they held.  kPairLoads:
+  // kStepPair (even) -- atoms kt + 2 into sa2 / sb2 and kt + 3 into sa / sb, staging what sa / sb held; kStepOdd -- no request, staging
+  // sa2 / sb2; kStepNone (the step behind the loop, whose successor is the final step and stages nothing) -- no request, staging sa / sb
+  using kStepOne = std::integral_constant<int, 0>;
+  using kStepPair = std::integral_constant<int, 1>;
+  using kStepOdd = std::integral_constant<int, 2>;
+  using kStepNone = std::integral_constant<int, 3>;
+  auto k_step_pipe = [&](int kt, unsigned char* ca, unsigned char* cb, unsigned char* na, unsigned char* nb, auto step_kind) {
     static_assert(kMfma32 || TM % 2 == 0, "pairs of A fragments");
+    constexpr int kKind = decltype(step_kind)::value;
+    static_assert(kKind == 0 || kPairLoads, "the paired-load sibling's steps");
     Staged ta[A_UNITS], tb[B_UNITS];
 #pragma unroll
     for (int u = 0; u < A_UNITS; ++u) ta[u] = sa[u];
 #pragma unroll
     for (int u = 0; u < B_UNITS; ++u) tb[u] = sb[u];
-    load_step(min(kt + 2, a_end - 1));            // in flight during this whole step
+    if constexpr (kKind == kStepOne::value) load_step(min(kt + 2, a_end - 1));            // in flight during this whole step
+#ifdef ARCQ_TILE_PL_UNIT
+    if constexpr (kKind == kStepOdd::value) {
+#pragma unroll
+      for (int u = 0; u < A_UNITS; ++u) ta[u] = sa2[u];
+#pragma unroll
+      for (int u = 0; u < B_UNITS; ++u) tb[u] = sb2[u];
+    }
+    if constexpr (kKind == kStepPair::value) load_pair(min(kt + 2, a_end - 1), min(kt + 3, a_end - 1), sa2, sb2, sa, sb, kPairA{});   // ... and the next: A's code pairs here
+#endif
     __builtin_amdgcn_sched_barrier(0);
     constexpr int kPieces = (A_UNITS + B_UNITS) * 4, kBlocks = kMfma32 ? 4 : TM;   // 32x32x16: one block per 16-wide K slice
     auto pieces = [&](int blk) {                  // this block's share of the staging of step kt + 1
@@ -372,6 +459,13 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(Til
         const int ks = q / kHalf, pr = q % kHalf;
         constexpr int kHeadReads = TN + 2;
         int n_pieces = 0, n_reads = 0;
+#ifdef ARCQ_TILE_PL_UNIT
+        if constexpr (kKind == kStepPair::value) {          // ... B's code pairs ahead of block 2, the scale loads of both ahead of block 4
+          if (q == 2) load_pair(min(kt + 2, a_end - 1), min(kt + 3, a_end - 1), sa2, sb2, sa, sb, kPairB{});
+          if (q == 4) load_pair(min(kt + 2, a_end - 1), min(kt + 3, a_end - 1), sa2, sb2, sa, sb, kPairSf{});
+          if (q == 2 || q == 4) __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
         if (q <= kLast) {
           // (1) reads for later blocks
 #pragma unroll
@@ -485,6 +579,10 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(Til
   // ---- prologue: tile 0 into buffer 0, registers <- step 1.  Both steps are requested together and only step 0 is awaited (a
   //      counted vmcnt: loads return in order): one memory round trip before the first MFMA, not two dependent ones.  The second
   //      register set exists only here.
+#ifdef ARCQ_TILE_PL_UNIT                        // (the same two steps, ordered as the even step orders its own)
+  Staged sa0[A_UNITS], sb0[B_UNITS];
+  load_pair(a_begin, min(a_begin + 1, a_end - 1), sa0, sb0, sa, sb, kPairAll{});
+#else
   load_step(a_begin);
   Staged sa0[A_UNITS], sb0[B_UNITS];
 #pragma unroll
@@ -492,6 +590,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(Til
 #pragma unroll
   for (int u = 0; u < B_UNITS; ++u) sb0[u] = sb[u];
   load_step(min(a_begin + 1, a_end - 1));
+#endif
   __builtin_amdgcn_sched_barrier(0);            // keep the second set of loads above the first wait
   if constexpr (kOverlapTail) {                 // the accumulators are zeroed while the first loads are in flight, not between their arrival and the first MFMA
 #pragma unroll
@@ -537,20 +636,23 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(Til
     // the unchanged step pairs while at least three steps remain, one more unchanged step if two remain; the range's last step is
     // multiplied by the final step (inside the interior epilogue below) from whichever buffer it was staged into
     static_assert(kRotate, "the final step is entered with head fragments");
+    using Even = std::conditional_t<kPairLoads, kStepPair, kStepOne>;
+    using Odd = std::conditional_t<kPairLoads, kStepOdd, kStepOne>;
+    using Last = std::conditional_t<kPairLoads, kStepNone, kStepOne>;
     for (; kt + 2 < a_end; kt += 2) {
-      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1);
-      k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0);
+      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, Even{});
+      k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0, Odd{});
     }
     if (kt + 1 < a_end) {
-      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1);
+      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, Last{});
       tail_buf = A_TILE + B_TILE;
     }
   } else if constexpr (kPipe) {
     for (; kt + 1 < a_end; kt += 2) {
-      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1);
-      k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0);
+      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, kStepOne{});
+      k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0, kStepOne{});
     }
-    if (kt < a_end) k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1);
+    if (kt < a_end) k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, kStepOne{});
   } else {
     for (; kt + 1 < a_end; kt += 2) {
       k_step(kt, lds_a0, lds_b0, lds_a1, lds_b1);
@@ -895,7 +997,31 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm_tile_ot_kernel(Til
   }
 }
 
-#ifdef ARCQ_TILE_OT_UNIT
+#if defined(ARCQ_TILE_PL_UNIT)
+static int g_tile_pair_loads = 1;
+int tile_pair_loads_mode() { return g_tile_pair_loads; }
+// DEBUG / test control, read at every launch: 1 = a launch that is eligible for the overlapped tail (arcq_debug_set_tile_overlap_tail's
+// rule) with the plain epilogue takes gemm_tile_pl_kernel, 0 = it takes gemm_tile_ot_kernel
+extern "C" void arcq_debug_set_tile_pair_loads(int on) { g_tile_pair_loads = on != 0; }
+
+template <int kBLayout, int kEpiOps>
+static int launch_pl(const TileParams& p, dim3 grid, hipStream_t stream) {
+  return launch_kernel<gemm_tile_pl_kernel<256, 256, 2, 4, kEpiPlain, kBLayout, kEpiOps>>(grid, dim3(512), 2 * (256 + 256) * kRowBytes, stream,
+                                                                                        "arcq_gemm_nvfp4 (tile, paired loads)", p);
+}
+template <int kBLayout>
+static int launch_pl_ops(const TileParams& p, dim3 grid, hipStream_t stream) {
+  switch ((p.bias ? 1 : 0) | (p.residual ? 2 : 0)) {
+    case 1: return launch_pl<kBLayout, 1>(p, grid, stream);
+    case 2: return launch_pl<kBLayout, 2>(p, grid, stream);
+    case 3: return launch_pl<kBLayout, 3>(p, grid, stream);
+    default: return launch_pl<kBLayout, 0>(p, grid, stream);
+  }
+}
+int launch_tile_pair_loads(const TileParams& p, int b_layout, dim3 grid, hipStream_t stream) {
+  return b_layout == kBRepacked ? launch_pl_ops<kBRepacked>(p, grid, stream) : launch_pl_ops<kBRef>(p, grid, stream);
+}
+#elif defined(ARCQ_TILE_OT_UNIT)
 static int g_tile_overlap_tail = 1;
 int tile_overlap_tail_mode() { return g_tile_overlap_tail; }
 // DEBUG / test control, read at every launch: 0 = never take the sibling, 1 = launches of the 256 x 256 8-wave tile whose tiles are all
@@ -1015,7 +1141,9 @@ static int launch_tile(const GemmArgs& a, hipStream_t stream, bool allow_split =
   if constexpr (BM == 256 && BN == 256 && WAVES_M * WAVES_N == 8 && !kMfma32 && !ARCQ_TILE_BARRIER_AT_STEP_END)
     overlap_tail = pipe && (kEpi == kEpiSiluMul ? tile_overlap_tail_mode() == 2 : tile_overlap_tail_mode() != 0) && a.M % BM == 0 && a.N % BN == 0 && p.splits <= 1 && a.out_dtype == ARCQ_OUT_BF16 &&
                    (int64_t)BM * a.N < (1ll << 31) && ((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.residual)) & 7) == 0;
-  if (overlap_tail) rc = launch_tile_overlap_tail(p, kEpi, kBLayout, grid, stream);
+  // ... and of those the plain-epilogue launches take its paired-load sibling (gemm_tile_pl.hip) unless the debug setter says 0
+  if (overlap_tail && kEpi == kEpiPlain && tile_pair_loads_mode() != 0) rc = launch_tile_pair_loads(p, kBLayout, grid, stream);
+  else if (overlap_tail) rc = launch_tile_overlap_tail(p, kEpi, kBLayout, grid, stream);
   else if (!pipe && !stagger) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false, kBLayout>>(grid, block, lds, stream, who, p);
   else if (pipe) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, true, kBLayout>>(grid, block, lds, stream, who, p);
   else rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, kCanStagger, false, kBLayout>>(grid, block, lds, stream, who, p);
@@ -1100,6 +1228,6 @@ int gemm_tile_repacked(const GemmArgs& a, hipStream_t stream) {
   return a.epilogue == kEpiSiluMul ? gemm_tile_epi<kEpiSiluMul, kBRepacked>(a, stream) : gemm_tile_epi<kEpiPlain, kBRepacked>(a, stream);
 }
 #endif
-#endif  // ARCQ_TILE_OT_UNIT
+#endif  // ARCQ_TILE_PL_UNIT / ARCQ_TILE_OT_UNIT
 
 }  // namespace arcq

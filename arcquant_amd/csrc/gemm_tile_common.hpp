@@ -37,6 +37,8 @@ struct TileParams {
 constexpr int kTileStamps = 5;          // kernel entry, K loop starts, K loop ends, first / last output store issued (gemm_tile.hip)
 // gemm_tile_ot.hip: launches gemm_tile_ot_kernel<256, 256, 2, 4, epi, b_layout> (the caller has checked that the launch is eligible)
 int launch_tile_overlap_tail(const TileParams& p, int epi, int b_layout, dim3 grid, hipStream_t stream);
+// gemm_tile_pl.hip: launches gemm_tile_pl_kernel<256, 256, 2, 4, kEpiPlain, b_layout> (a launch eligible for the overlapped tail, plain epilogue)
+int launch_tile_pair_loads(const TileParams& p, int b_layout, dim3 grid, hipStream_t stream);
 
 constexpr int kBK = 64;                 // K elements per step = one scale-factor atom column (4 groups)
 constexpr int kRowBytes = kBK * 2;      // fp16 row of a tile in LDS
@@ -97,6 +99,14 @@ __device__ __forceinline__ Staged stage_load(const StageSrc& src, uint32_t q_lan
   s.q = make_uint4(q.x, q.y, q.z, q.w);
   s.sf = (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(src.sf, (int)sf_lane, (int)step.sf, 0);
   return s;
+}
+// the two halves of stage_load on their own (gemm_tile_pl.hip orders the code loads of two atoms ahead of their scale loads)
+__device__ __forceinline__ uint4 stage_load_q(const StageSrc& src, uint32_t q_lane, StageStep step) {
+  const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(src.q, (int)q_lane, (int)step.q, 0);
+  return make_uint4(q.x, q.y, q.z, q.w);
+}
+__device__ __forceinline__ uint32_t stage_load_sf(const StageSrc& src, uint32_t sf_lane, StageStep step) {
+  return (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(src.sf, (int)sf_lane, (int)step.sf, 0);
 }
 
 // The two scale bytes of a unit -> ONE register: the fp16 pair (s0', s1') of sf_pair's values (byte << 7 in each half).  Shifting the

@@ -2,7 +2,8 @@
 """A-B of two builds of the library on the tile GEMM (tuning aid): steady-state time per launch (bench.py's sustained-clock protocol),
 each build in its own subprocess, rounds interleaved; per shape and build the values of every round, their median and their
 run-to-run band (max - min).  usage: tile_lib_ab.py [--rounds N] name=path[:ENV=VAL] ...     (the comparator first)
-ENV ARCQ_AB_OVERLAP_TAIL=0|1|2 calls arcq_debug_set_tile_overlap_tail with that value first (a library that has the setter)."""
+ENV ARCQ_AB_OVERLAP_TAIL=0|1|2 calls arcq_debug_set_tile_overlap_tail with that value first (a library that has the setter),
+ARCQ_AB_PAIR_LOADS=0|1 arcq_debug_set_tile_pair_loads."""
 import json
 import os
 import statistics
@@ -11,10 +12,10 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# M, N, KQ, epilogue: "" plain, "silu" SiLU * up, "bias", "residual"[, KE = 64]      (the model shapes: down, gate|up, q|k|v with its bias, o with
-# its residual; KE = 0: an even number of K steps; M = 1024: the 128 x 256 tile)
+# M, N, KQ, epilogue: "" plain, "silu" SiLU * up, "bias", "residual", "rw" plain over the repacked weight[, KE = 64]      (the model shapes:
+# down, gate|up, q|k|v with its bias, o with its residual; KE = 0: an even number of K steps; M = 1024: the 128 x 256 tile)
 SHAPES = [(4096, 4096, 4096, ""), (8192, 8192, 8192, ""), (4096, 4096, 4096, "", 0), (4096, 3584, 18944, ""), (4096, 37888, 3584, "silu"),
-          (4096, 10752, 3584, "bias"), (4096, 3584, 3584, "residual"), (1024, 4096, 4096, "")]
+          (4096, 10752, 3584, "bias"), (4096, 3584, 3584, "residual"), (4096, 4096, 4096, "rw"), (1024, 4096, 4096, "")]
 
 CODE = """
 import json, os, sys, torch
@@ -23,6 +24,8 @@ import bench
 from arcquant_amd import agemm
 if os.environ.get('ARCQ_AB_OVERLAP_TAIL'):
     agemm._debug_set_tile_overlap_tail(int(os.environ['ARCQ_AB_OVERLAP_TAIL']))
+if os.environ.get('ARCQ_AB_PAIR_LOADS'):
+    agemm._debug_set_tile_pair_loads(int(os.environ['ARCQ_AB_PAIR_LOADS']))
 dev = torch.device('cuda:0')
 out = []
 for (M, N, KQ, epi, *ke) in {shapes!r}:
@@ -32,6 +35,10 @@ for (M, N, KQ, epi, *ke) in {shapes!r}:
     res = torch.randn(M, N, generator=g).to(torch.bfloat16).to(dev) if epi == 'residual' else None
     if epi == 'silu':
         f = lambda: agemm.matmul_silu_mul(p['qx'], p['qw'], p['sfx'], p['sfw'], p['alpha'])
+    elif epi == 'rw':
+        rw, rsf = agemm.repack_w(p['qw'], p['sfw'])
+        o = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
+        f = lambda: agemm.matmul_rw(p['qx'], rw, p['sfx'], rsf, p['alpha'], N, out=o)
     else:
         o = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
         f = lambda: agemm.matmul(p['qx'], p['qw'], p['sfx'], p['sfw'], p['alpha'], bias=bias, residual=res, out=o)
