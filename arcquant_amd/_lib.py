@@ -89,6 +89,11 @@ KV_SYMBOLS = {
     "arcq_kv_decode_step": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p,
                                    _i64, _p]),
     "arcq_kv_batch_prefill": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p]),
+    "arcq_rope_qk": (_i32, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i64, _i32, _p]),
+    "arcq_kv_rope_append_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
+                                            _p]),
+    "arcq_kv_rope_init_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32,
+                                          _i32, _p]),
 }
 
 _lib = None

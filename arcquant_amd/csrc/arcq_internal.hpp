@@ -222,4 +222,23 @@ struct KvPrefillArgs {
 };
 int kv_prefill(const KvPrefillArgs& a, hipStream_t stream);
 
+// kv_rope.hip: rotary position embedding in front of the quantising writers, and alone (arguments validated by c_api_kv.hip)
+struct KvRopeArgs {
+  KvWriteArgs w;                           // quantize = true; k, v: 16-bit rows [ntok, N, 128], tokens kv_stride elements apart
+  void* q_out;                             // 16-bit [ntok, Nq, 128], contiguous
+  const void* q;                           // 16-bit [ntok, Nq, 128], tokens q_stride elements apart
+  const void *cos, *sin;                   // 16-bit [rope_len, 128]
+  int64_t q_stride, kv_stride, Nq;
+  const char* who;
+};
+int kv_rope_write(const KvRopeArgs& a, hipStream_t stream);
+struct RopeQkArgs {
+  void *q, *k;                             // rotated in place; k may be NULL when N == 0
+  const int32_t* positions;                // int32 [n_pos]: token i takes positions[i % n_pos]
+  const void *cos, *sin;
+  int64_t q_stride, k_stride, ntok, n_pos, Nq, N;
+  int dtype;
+};
+int kv_rope_qk(const RopeQkArgs& a, hipStream_t stream);
+
 }  // namespace arcq

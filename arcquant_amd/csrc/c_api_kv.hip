@@ -45,9 +45,89 @@ int write_call(const char* who, KvWriteArgs& a, bool init, void* stream) {
   return kv_write(a, (hipStream_t)stream);
 }
 
+// a contiguous [ntok, heads, 128] result and a strided source of the same rows: the same tensor, or apart
+bool overlaps(const void* out, const void* in, int64_t ntok, int64_t heads, int64_t in_stride) {
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (uintptr_t)(ntok * heads * 256);
+  const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (uintptr_t)(((ntok - 1) * in_stride + heads * 128) * 2);
+  return o0 < i1 && i0 < o1;
+}
+
+int rope_write_call(const char* who, KvRopeArgs& a, bool init, int64_t rope_len, void* stream) {
+  KvWriteArgs& w = a.w;
+  int rc = geometry(who, w.B, w.L, w.layer, w.N, w.P, w.format);
+  if (rc != ARCQ_OK) return rc;
+  if ((rc = dtype_ok(who, w.dtype)) != ARCQ_OK) return rc;
+  if (w.ntok < 0 || w.ntok > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: ntok=%lld is out of range", who, (long long)w.ntok);
+  if (a.Nq <= 0 || a.Nq % w.N || a.Nq > 65535)
+    return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (at most 65535)", who, (long long)a.Nq, (long long)w.N);
+  if (w.format != ARCQ_KV_INT4) return fail(ARCQ_ERR_UNSUPPORTED, "%s: the quantiser writes ARCQ_KV_INT4 caches only", who);
+  if (rope_len < 1 || rope_len > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: rope_len=%lld must be at least 1", who, (long long)rope_len);
+  if (a.q_stride < a.Nq * 128 || a.kv_stride < w.N * 128 || a.q_stride % 8 || a.kv_stride % 8 || a.q_stride > kMaxDim || a.kv_stride > kMaxDim)
+    return fail(ARCQ_ERR_SHAPE, "%s: q_stride=%lld >= Nq * 128 = %lld and kv_stride=%lld >= N * 128 = %lld must be multiples of 8 elements", who,
+                (long long)a.q_stride, (long long)(a.Nq * 128), (long long)a.kv_stride, (long long)(w.N * 128));
+  if (w.ntok * (a.Nq + 2 * w.N) > 16 * (int64_t)INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: ntok * (Nq + 2 N) rows are out of range", who);
+  if (w.B == 0 || w.ntok == 0) return ARCQ_OK;
+  if (!w.kv_data || !w.kv_param || !w.kv_indptr || !w.kv_indices || !w.last_page_offset || !w.k || !w.v || (init && !w.seqlen_indptr) || !a.q_out ||
+      !a.q || !a.cos || !a.sin)
+    return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
+  if (misaligned(w.kv_data, 16) || misaligned(w.k, 16) || misaligned(w.v, 16) || misaligned(a.q, 16) || misaligned(a.q_out, 16) ||
+      misaligned(a.cos, 16) || misaligned(a.sin, 16))
+    return fail(ARCQ_ERR_SHAPE, "%s: kv_data, q_out, q, k, v, cos and sin must be 16-byte aligned", who);
+  if (misaligned(w.kv_param, 4) || misaligned(w.kv_indptr, 4) || misaligned(w.kv_indices, 4) || misaligned(w.last_page_offset, 4) ||
+      misaligned(w.seqlen_indptr, 4))
+    return fail(ARCQ_ERR_SHAPE, "%s: kv_param and the index tensors must be 4-byte aligned", who);
+  if (overlaps(a.q_out, a.q, w.ntok, a.Nq, a.q_stride) && !(a.q_out == a.q && (a.q_stride == a.Nq * 128 || w.ntok == 1)))
+    return fail(ARCQ_ERR_SHAPE, "%s: q_out must be q itself (q contiguous) or must not overlap it", who);
+  a.who = who;
+  return kv_rope_write(a, (hipStream_t)stream);
+}
+
 }  // namespace
 
 extern "C" {
+
+int arcq_rope_qk(void* q, void* k, int64_t q_stride, int64_t k_stride, const int32_t* positions, int64_t n_pos, const void* cos, const void* sin,
+                 int64_t rope_len, int64_t ntok, int64_t Nq, int64_t N, int dtype, void* stream) {
+  const char* who = "arcq_rope_qk";
+  int rc = dtype_ok(who, dtype);
+  if (rc != ARCQ_OK) return rc;
+  if (ntok < 0 || ntok > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: ntok=%lld is out of range", who, (long long)ntok);
+  if (Nq <= 0 || Nq > 65535 || N < 0 || N > 65535 || (N > 0 && Nq % N))
+    return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (N = 0: no k; at most 65535 each)", who, (long long)Nq, (long long)N);
+  if (rope_len < 1 || rope_len > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: rope_len=%lld must be at least 1", who, (long long)rope_len);
+  if (n_pos < 1 || n_pos > kMaxDim || ntok % n_pos)
+    return fail(ARCQ_ERR_SHAPE, "%s: n_pos=%lld must be at least 1 and divide ntok=%lld", who, (long long)n_pos, (long long)ntok);
+  if (q_stride < Nq * 128 || q_stride % 8 || q_stride > kMaxDim || (N > 0 && (k_stride < N * 128 || k_stride % 8 || k_stride > kMaxDim)))
+    return fail(ARCQ_ERR_SHAPE, "%s: q_stride=%lld >= Nq * 128 = %lld and k_stride=%lld >= N * 128 = %lld must be multiples of 8 elements", who,
+                (long long)q_stride, (long long)(Nq * 128), (long long)k_stride, (long long)(N * 128));
+  if (ntok * (Nq + N) > 16 * (int64_t)INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: ntok * (Nq + N) rows are out of range", who);
+  if (ntok == 0) return ARCQ_OK;
+  if (!q || (N > 0 && !k) || !positions || !cos || !sin) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
+  if (misaligned(q, 16) || (N > 0 && misaligned(k, 16)) || misaligned(cos, 16) || misaligned(sin, 16))
+    return fail(ARCQ_ERR_SHAPE, "%s: q, k, cos and sin must be 16-byte aligned", who);
+  if (misaligned(positions, 4)) return fail(ARCQ_ERR_SHAPE, "%s: positions must be 4-byte aligned", who);
+  RopeQkArgs a{q, N > 0 ? k : nullptr, positions, cos, sin, q_stride, k_stride, ntok, n_pos, Nq, N, dtype};
+  return kv_rope_qk(a, (hipStream_t)stream);
+}
+
+int arcq_kv_rope_append_quantize(void* kv_data, void* kv_param, const int32_t* kv_indptr, const int32_t* kv_indices, const int32_t* last_page_offset,
+                                 void* q_out, const void* q, const void* k, const void* v, int64_t q_stride, int64_t kv_stride, const void* cos,
+                                 const void* sin, int64_t rope_len, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int format,
+                                 int dtype, void* stream) {
+  KvRopeArgs a{{kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, k, v, nullptr, nullptr, nullptr, B, B, L, layer_idx, N, P, format, dtype, true},
+               q_out, q, cos, sin, q_stride, kv_stride, Nq, nullptr};
+  return rope_write_call("arcq_kv_rope_append_quantize", a, false, rope_len, stream);
+}
+
+int arcq_kv_rope_init_quantize(void* kv_data, void* kv_param, const int32_t* kv_indptr, const int32_t* kv_indices, const int32_t* last_page_offset,
+                               void* q_out, const void* q, const void* k, const void* v, int64_t q_stride, int64_t kv_stride, const void* cos,
+                               const void* sin, int64_t rope_len, const int32_t* seqlen_indptr, int64_t ntok, int64_t B, int64_t Nq, int64_t L,
+                               int64_t layer_idx, int64_t N, int64_t P, int format, int dtype, void* stream) {
+  KvRopeArgs a{{kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, k, v, nullptr, nullptr, seqlen_indptr, ntok, B, L, layer_idx, N, P, format, dtype,
+                true},
+               q_out, q, cos, sin, q_stride, kv_stride, Nq, nullptr};
+  return rope_write_call("arcq_kv_rope_init_quantize", a, true, rope_len, stream);
+}
 
 int arcq_kv_init(void* kv_data, void* kv_param, const int32_t* kv_indptr, const int32_t* kv_indices, const int32_t* last_page_offset, const void* k,
                  const void* v, const void* k_param, const void* v_param, const int32_t* seqlen_indptr, int64_t ntok, int64_t B, int64_t L,

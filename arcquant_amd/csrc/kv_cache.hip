@@ -36,37 +36,7 @@ namespace arcq {
 constexpr int kKvRec = kKvD + 2;         // a merge record: max, sum, 128 accumulators
 constexpr int kKvWaves = 4;
 
-// ---- writers
-struct KvWriteParams {
-  uint8_t* data;
-  uint32_t* param;
-  KvTables t;
-  const uint8_t* k;
-  const uint8_t* v;
-  const uint32_t* kp;             // fp16 (scale, zero) pairs [ntok, N] (copy kernel only)
-  const uint32_t* vp;
-  const int32_t* seqlen_indptr;   // NULL: append -- token b is the last position of sequence b
-  int ntok, B, L, layer, N, P, row_bytes;
-};
-
-// token -> (sequence, position); false: the token belongs to no sequence
-__device__ __forceinline__ bool kv_locate(const KvWriteParams& p, int tok, int& b, int& pos) {
-  if (p.seqlen_indptr == nullptr) {
-    b = tok;
-    pos = kv_seq_len(p.t, b, p.P) - 1;
-    return pos >= 0;
-  }
-  if (tok >= p.seqlen_indptr[p.B]) return false;
-  int lo = 0, hi = p.B;           // the last b with seqlen_indptr[b] <= tok
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (p.seqlen_indptr[mid] <= tok) lo = mid; else hi = mid;
-  }
-  b = lo;
-  pos = kv_seq_len(p.t, b, p.P) - (p.seqlen_indptr[b + 1] - p.seqlen_indptr[b]) + (tok - p.seqlen_indptr[b]);
-  return pos >= 0;
-}
-
+// ---- writers (KvWriteParams, kv_locate and kv_quantize_row: kv_device.hpp)
 __global__ __launch_bounds__(256) void kv_write_kernel(KvWriteParams p) {
   const int tok = blockIdx.x, tid = threadIdx.x;
   int b, pos;
@@ -85,40 +55,6 @@ __global__ __launch_bounds__(256) void kv_write_kernel(KvWriteParams p) {
     const int which = i >= p.N, n = i - which * p.N;
     p.param[row0 + which * vrows + (size_t)n * p.P] = (which ? p.vp : p.kp)[(size_t)tok * p.N + n];
   }
-}
-
-// The quantiser of a row of 128 values held NE per lane by 128 / NE adjacent lanes (lane c: elements c * NE ..): this lane's codes, element
-// j in nibble j % 8 of word j / 8, and the row's fp16 (scale, zero) pair.  torch eager on a tensor of the input dtype: every operation's
-// result is rounded to that dtype (the Scalar 1e-5 too).
-template <bool BF16, int NE>
-__device__ __forceinline__ uint32_t kv_quantize_row(const float (&x)[NE], uint32_t (&codes)[NE / 8]) {
-  float xmax = x[0], xmin = x[0];
-#pragma unroll
-  for (int j = 1; j < NE; ++j) {
-    xmax = fmaxf(xmax, x[j]);
-    xmin = fminf(xmin, x[j]);
-  }
-#pragma unroll
-  for (int sh = kKvD / NE / 2; sh > 0; sh >>= 1) {
-    xmax = fmaxf(xmax, __shfl_xor(xmax, sh, 64));
-    xmin = fminf(xmin, __shfl_xor(xmin, sh, 64));
-  }
-  const float range = fmaxf(kv_round<BF16>(xmax - xmin), kv_round<BF16>(1e-5f));
-  const float scale = kv_round<BF16>(range / 15.0f);
-  const float zero = -xmin;
-#pragma unroll
-  for (int w = 0; w < NE / 8; ++w) {
-    uint32_t cw = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float a = kv_round<BF16>(x[w * 8 + j] + zero);
-      const float qv = kv_round<BF16>(a / scale);
-      const float rc = fminf(fmaxf(__builtin_rintf(qv), 0.0f), 15.0f);      // (NaN -- inf / inf of an overflowing fp16 range -- becomes code 0)
-      cw |= (uint32_t)rc << (4 * j);
-    }
-    codes[w] = cw;
-  }
-  return kv_from_f32<false>(scale) | (kv_from_f32<false>(zero) << 16);
 }
 
 // rows = (token, K | V, head); four rows per wave, 16 lanes x 8 values each

@@ -20,6 +20,9 @@ allocation-free apart from torch's caching allocator).
 ``kv_cache="int4"`` (``--kv-cache int4``) swaps the dense bf16 cache for the reference's int4 paged cache served by ``arcquant_amd.kvcache``
 (``DecoderModel._attention_int4``); the default is the dense cache.  ``kv_paged_prefill=True`` (``--kv-paged-prefill``) on top of it makes
 every multi-token call, at any position, attend over the pages with ``kvcache.batch_prefill_i4`` instead of SDPA over its own k / v.
+
+``rope=True`` (``--rope``, ``--rope-theta``) rotates q and k to their positions before the cache write and attention, on every call path
+(``arcquant_amd.kvrope``, DESIGN.md 11 "RoPE"); the default is the RoPE-free layer every published figure was measured on.
 """
 from __future__ import annotations
 
@@ -121,7 +124,7 @@ class DecoderModel:
 
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
                  repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False, kv_cache: str = "bf16",
-                 kv_fused_step: bool = False, kv_paged_prefill: bool = False):
+                 kv_fused_step: bool = False, kv_paged_prefill: bool = False, rope: bool = False, rope_theta: float = 1e6, rope_tables=None):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
@@ -132,7 +135,11 @@ class DecoderModel:
         instead of the dense bf16 one -- a prefill writes its k / v through init_kv_quantize_i4, a decode step appends with
         append_kv_quantize_i4 and attends with batch_decode_i4.  "bf16" (default) is the dense cache.
         kv_paged_prefill (kv_cache="int4" only): a multi-token call at ANY position writes its k / v into the pages and attends over them
-        with batch_prefill_i4 (chunked prefill, a second turn); off, a multi-token call starts at position 0 and attends with SDPA."""
+        with batch_prefill_i4 (chunked prefill, a second turn); off, a multi-token call starts at position 0 and attends with SDPA.
+        rope (head dimension 128): q and k are rotated to their positions (rotate-half, the Hugging Face tables of ``rope_theta`` for
+        ``max_len`` positions, or the caller's ``rope_tables`` = (cos, sin), bfloat16 [>= max_len, 128]) before the cache write and
+        attention: kvrope.rope_qk_ in place on the dense paths, SDPA prefill and the one-launch step; kvrope.rope_append_kv_quantize_i4 /
+        rope_init_kv_quantize_i4 in place of the quantising writers on the int4 chain and the paged prefill."""
         if kv_cache not in ("bf16", "int4"):
             raise ValueError(f"DecoderModel: kv_cache must be 'bf16' or 'int4', got {kv_cache!r}")
         if kv_cache == "int4" and (attention != "cache" or cfg.hidden_size // cfg.num_heads != kvcache.HEAD_DIM):
@@ -141,6 +148,17 @@ class DecoderModel:
             raise ValueError("DecoderModel: kv_fused_step=True needs kv_cache='int4' (the one-launch decode step is the int4 paged cache's)")
         if kv_paged_prefill and kv_cache != "int4":
             raise ValueError("DecoderModel: kv_paged_prefill=True needs kv_cache='int4' (the prefill attention is the int4 paged cache's)")
+        if rope_tables is not None and not rope:
+            raise ValueError("DecoderModel: rope_tables needs rope=True")
+        if rope and cfg.hidden_size // cfg.num_heads != kvcache.HEAD_DIM:
+            raise ValueError("DecoderModel: rope=True needs a head dimension of 128")
+        if rope_tables is not None:
+            if not (isinstance(rope_tables, (tuple, list)) and len(rope_tables) == 2):
+                raise ValueError("DecoderModel: rope_tables must be a (cos, sin) pair")
+            for t in rope_tables:
+                if getattr(t, "dtype", None) is not torch.bfloat16 or t.dim() != 2 or t.shape[1] != kvcache.HEAD_DIM or t.shape[0] < max_len:
+                    raise ValueError(f"DecoderModel: rope_tables must be two bfloat16 tensors [>= {max_len}, {kvcache.HEAD_DIM}], got "
+                                     f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
         if repacked_only and not fused:
             raise ValueError("DecoderModel: repacked_only=True needs fused=True (the unfused model is the reference's call structure)")
         if quant_type not in ("NVFP4", "MXFP4"):
@@ -206,10 +224,27 @@ class DecoderModel:
         # every layer's pages in one paged cache, with the page tables of every length built here -- before any graph capture
         self.kvc = kvcache.PagedKVCacheI4(batch, self.kv_page_size, max_len, device, cfg.num_layers, cfg.num_heads) if kv_cache == "int4" else None
         self.kv_step_state = kvstep.DecodeStepState(batch, cfg.num_heads, cfg.num_heads, device) if kv_fused_step else None
+        # RoPE: the tables and the positions of every call are built here, once -- nothing is allocated per step (graph capture)
+        self.rope = bool(rope)
+        self.rope_cos = self.rope_sin = self.rope_pos = None
+        if self.rope:
+            if rope_tables is None:
+                rope_tables = kvcache.rope_tables(max_len, rope_theta, torch.bfloat16)
+            self.rope_cos, self.rope_sin = (t.to(device).contiguous() for t in rope_tables)
+            self.rope_pos = torch.arange(max_len, dtype=torch.int32, device=device)
 
     def weight_bytes(self):
         per_layer = sum(v.bytes() for v in self.layers[0].values() if isinstance(v, QLinear))
         return per_layer * self.cfg.num_layers + self.lm_head.numel() * 2
+
+    def _rope_(self, q, k, pos, q_len):
+        """rope=True: q (and k, unless None) -- [tokens, heads * 128] rows, views included -- rotated in place to positions pos .. pos + q_len - 1
+        (token i of a call is position pos + i % q_len); returns the [tokens, heads, 128] views."""
+        hd = kvcache.HEAD_DIM
+        q3 = q.unflatten(-1, (-1, hd))
+        k3 = None if k is None else k.unflatten(-1, (-1, hd))
+        kvcache.rope_qk_(q3, k3, self.rope_pos[pos:pos + q_len], self.rope_cos, self.rope_sin)
+        return q3, k3
 
     @staticmethod
     def _quant_x(x, idx, ke):
@@ -379,6 +414,8 @@ class DecoderModel:
         """KV append + attention with torch ops (prefill always; decode when the streaming kernel is switched off)."""
         cfg = self.cfg
         nh, hd, h = cfg.num_heads, cfg.hidden_size // cfg.num_heads, cfg.hidden_size
+        if self.rope:           # in place on the projection output (or its q, k views): the cache write below stores the rotated k
+            self._rope_(q, k, pos, q_len)
         q = q.reshape(bsz, q_len, nh, hd).transpose(1, 2)
         if qkv is not None:     # k|v are adjacent columns of the fused projection: ONE strided copy appends both to the cache
             L["kv"][:, :, :, pos:pos + q_len] = qkv[:, h:].reshape(bsz, q_len, 2, nh, hd).permute(2, 0, 3, 1, 4)
@@ -405,14 +442,23 @@ class DecoderModel:
         over is what the decode steps will read (the call is also traced, with ``n_new`` = q_len).  Decode:
         append_kv_quantize_i4, then batch_decode_i4 over positions [0, pos], on the q, k and v slices of the projection output (one
         transposing copy makes the three contiguous); with kv_fused_step the three become ONE kvstep.decode_step_i4 launch on views of
-        the projection output, bit for bit the same.  Harness glue around the operators, like the dense cache's kernel."""
+        the projection output, bit for bit the same.  Harness glue around the operators, like the dense cache's kernel.
+        rope=True: the two quantising writers become kvrope's (rotation, contiguous q and write in one launch, on views: no transposing
+        copy), the SDPA prefill and the one-launch step rotate q and k in place first; the trace records the rotated q and k."""
         cfg = self.cfg
         nh, hd, h = cfg.num_heads, cfg.hidden_size // cfg.num_heads, cfg.hidden_size
         if q_len > 1 and self.kv_paged_prefill:
-            qq, kk, vv = (t.reshape(bsz * q_len, nh, hd).contiguous() for t in (q, k, v))
             tables = self.kvc.prefill_tables(pos + q_len, q_len)
             qo_indptr = tables.pop("qo_indptr")
-            kvcache.init_kv_quantize_i4(**tables, k=kk, v=vv, seqlen_indptr=qo_indptr, layer_idx=li)
+            if self.rope:       # rotation, the contiguous q and the quantising write in one launch, on the views of the projection output
+                qs, kk, vv = (t.unflatten(-1, (nh, hd)) for t in (q, k, v))
+                qq = torch.empty((bsz * q_len, nh, hd), dtype=q.dtype, device=q.device)
+                kvcache.rope_init_kv_quantize_i4(qq, qs, kk, vv, self.rope_cos, self.rope_sin, **tables, seqlen_indptr=qo_indptr, layer_idx=li)
+                if self.kv_trace is not None:       # (the rotated k exists only as codes: the trace rotates a copy)
+                    kk = self._rope_(kk.clone(memory_format=torch.contiguous_format).view(bsz * q_len, h), None, pos, q_len)[0]
+            else:
+                qq, kk, vv = (t.reshape(bsz * q_len, nh, hd).contiguous() for t in (q, k, v))
+                kvcache.init_kv_quantize_i4(**tables, k=kk, v=vv, seqlen_indptr=qo_indptr, layer_idx=li)
             out = torch.empty_like(qq)
             kvcache.batch_prefill_i4(out, qq, qo_indptr, **tables, layer_idx=li)
             if self.kv_trace is not None:
@@ -421,6 +467,8 @@ class DecoderModel:
         if q_len > 1:
             if pos != 0:
                 raise ValueError("DecoderModel(kv_cache='int4'): a multi-token call must start at position 0 (no prefill attention over the int4 pages)")
+            if self.rope:       # SDPA below needs the rotated k in 16 bit
+                self._rope_(q, k, pos, q_len)
             kk, vv = k.reshape(bsz * q_len, nh, hd).contiguous(), v.reshape(bsz * q_len, nh, hd).contiguous()
             seqlens = torch.arange(bsz + 1, dtype=torch.int32, device=kk.device) * q_len
             kvcache.init_kv_quantize_i4(**self.kvc.tables(q_len), k=kk, v=vv, seqlen_indptr=seqlens, layer_idx=li)
@@ -430,8 +478,18 @@ class DecoderModel:
         tables = self.kvc.tables(pos + 1)
         if self.kv_fused_step:      # one launch on views of the projection output (kvstep, DESIGN.md 11 "Decode step")
             qq, kk, vv = (qkv.view(bsz, 3 * nh, hd).split(nh, dim=1) if qkv is not None else (t.reshape(bsz, nh, hd) for t in (q, k, v)))
+            if self.rope:
+                kvcache.rope_qk_(qq, kk, self.rope_pos[pos:pos + 1], self.rope_cos, self.rope_sin)
             out = torch.empty((bsz, nh, hd), dtype=qq.dtype, device=qq.device)
             kvstep.decode_step_i4(out, qq, kk, vv, **tables, layer_idx=li, state=self.kv_step_state)
+        elif self.rope:             # the rotation, the contiguous q and the quantising append in one launch: no transposing copy
+            qs, kk, vv = (qkv.view(bsz, 3 * nh, hd).split(nh, dim=1) if qkv is not None else (t.reshape(bsz, nh, hd) for t in (q, k, v)))
+            qq = torch.empty((bsz, nh, hd), dtype=qs.dtype, device=qs.device)
+            kvcache.rope_append_kv_quantize_i4(qq, qs, kk, vv, self.rope_cos, self.rope_sin, **tables, layer_idx=li)
+            out = torch.empty_like(qq)
+            kvcache.batch_decode_i4(out, qq, **tables, layer_idx=li)
+            if self.kv_trace is not None:           # (the rotated k exists only as codes: the trace rotates a copy)
+                kk = self._rope_(kk.clone(memory_format=torch.contiguous_format).view(bsz, h), None, pos, 1)[0]
         else:
             if qkv is not None:
                 qq, kk, vv = qkv.view(bsz, 3, nh, hd).transpose(0, 1).contiguous().unbind(0)
@@ -451,6 +509,9 @@ class DecoderModel:
         from . import _lib
         lib = _lib.lib()
         bsz, nh = qkv.shape[0], self.cfg.num_heads
+        if self.rope:           # one launch more: q and k rotated in place in the projection output, the kernel below as it is
+            h = self.cfg.hidden_size
+            self._rope_(qkv[:, :h], qkv[:, h:2 * h], pos, 1)
         tmax = L["kc"].shape[2]
         if self._attn_ws is None:
             self._attn_ws = torch.empty(int(lib.arcq_harness_attn_workspace_bytes(bsz, nh, tmax)) // 4, dtype=torch.float32, device=qkv.device)
@@ -471,7 +532,7 @@ class DecoderModel:
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
                  attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False, kv_cache="bf16",
-                 kv_fused_step=False, kv_paged_prefill=False):
+                 kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
     weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
@@ -482,7 +543,7 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         mem0 = torch.cuda.memory_allocated(device)
         model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
                              quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
-                             kv_paged_prefill=kv_paged_prefill)
+                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -547,12 +608,14 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         res["kv_fused_step"] = True
     if kv_paged_prefill:
         res["kv_paged_prefill"] = True
+    if rope:
+        res["rope"] = True
     return res
 
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
                    fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False,
-                   kv_cache="bf16", kv_fused_step=False, kv_paged_prefill=False):
+                   kv_cache="bf16", kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -583,7 +646,7 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
     with torch.no_grad():
         model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
                              quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
-                             kv_paged_prefill=kv_paged_prefill)
+                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta)
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -632,6 +695,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         res["kv_fused_step"] = True
     if kv_paged_prefill:
         res["kv_paged_prefill"] = True
+    if rope:
+        res["rope"] = True
     return res
 
 
@@ -775,6 +840,15 @@ if __name__ == "__main__":
         if kvc not in ("bf16", "int4"):
             sys.exit("--kv-cache takes bf16 or int4")
         del argv[i:i + 2]
+    rope_theta = 1e6
+    if "--rope-theta" in argv:        # --rope-theta BASE (with --rope)
+        i = argv.index("--rope-theta")
+        try:
+            rope_theta = float(argv[i + 1])
+        except (IndexError, ValueError):
+            sys.exit("--rope-theta takes a number")
+        del argv[i:i + 2]
+    rope = "--rope" in argv           # q and k rotated to their positions before the cache write and attention (kvrope)
     args = [a for a in argv if not a.startswith("--")]
     name = args[0] if args else "qwen2.5-7b"
     kfs = "--kv-fused-step" in sys.argv      # --kv-cache int4 only: the decode step's append + attention as one launch (kvstep)
@@ -790,12 +864,12 @@ if __name__ == "__main__":
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
             print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
-                                            kv_fused_step=kfs, kv_paged_prefill=kpp)), flush=True)
+                                            kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
             if ((ro or qe) and not fused) or (kvc == "int4" and att != "cache"):
                 continue
             print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
-                                          kv_fused_step=kfs, kv_paged_prefill=kpp)), flush=True)
+                                          kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta)), flush=True)
             torch.cuda.empty_cache()

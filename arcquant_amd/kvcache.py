@@ -251,3 +251,5 @@ class PagedKVCacheI4:
 
 # ---- extension: causal prefill attention over the int4 pages, several query tokens per sequence (its own module, as kvstep is)
 from .kvprefill import batch_prefill_i4  # noqa: E402,F401
+# ---- extension: rotary position embedding at write time, fused into the quantising writers (its own module too)
+from .kvrope import rope_append_kv_quantize_i4, rope_init_kv_quantize_i4, rope_qk_, rope_tables  # noqa: E402,F401

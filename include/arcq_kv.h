@@ -70,8 +70,8 @@ int64_t arcq_kv_decode_workspace_bytes(int64_t B, int64_t Nq, int64_t N, int64_t
 
 /* Decode attention: o, q = `dtype` [B, Nq, 128], Nq = g * N; query head h reads kv head h / g (g == 1 is the reference's contract),
  * and the g query heads of a kv head share one pass over its rows.
- *     o[b, h] = softmax_t(q[b, h] . K[t] / sqrt(128)) V[t]   over the positions of sequence b, no RoPE (flashinfer.cu:26-31),
- * fp32 accumulation, rounded once to `dtype`.  A sequence without positions gives zeros.  nnz = entries of kv_indices: it sizes the
+ *     o[b, h] = softmax_t(q[b, h] . K[t] / sqrt(128)) V[t]   over the positions of sequence b, no RoPE (flashinfer.cu:26-31; a model
+ * that rotates does so when it writes: arcq_kv_rope_append_quantize / arcq_kv_rope_init_quantize / arcq_rope_qk below), fp32 accumulation, rounded once to `dtype`.  A sequence without positions gives zeros.  nnz = entries of kv_indices: it sizes the
  * slices, so pass what arcq_kv_decode_workspace_bytes was asked with; workspace_bytes >= that query's answer (0: workspace may be NULL). */
 int arcq_kv_batch_decode(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
                          const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
@@ -114,6 +114,46 @@ int arcq_kv_decode_step(void *o, const void *q, const void *k, const void *v, in
                         void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B,
                         int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *workspace,
                         int64_t workspace_bytes, void *state, int64_t state_bytes, void *stream);
+
+/* ---- Rotary position embedding (RoPE) on the KV path.  The attention entry points above apply none ("no RoPE"): the rotation is done
+ * at WRITE time, as the reference's model path does (apply_rotary_pos_emb, then past_key_value.update): the cache holds rotated keys and
+ * attention reads them as they are.  Head dimension 128, full rotation, rotate-half pairing.
+ *   cos, sin  `dtype` [rope_len, 128], contiguous, 16-byte aligned: the Hugging Face tables (emb = cat(freqs, freqs); emb.cos().to(dtype)).
+ *             Element i of a row at position p reads cos[p, i] and sin[p, i]; the two halves of a table row are not assumed equal and
+ *             no trigonometry is computed here (NTK / YaRN / Llama-3.1 scaling live in the caller's table).
+ *   result    rot(x)[i] = -x[i + 64] for i < 64, x[i - 64] otherwise, and
+ *                 out[i] = dtype(dtype(x[i] * cos[p, i]) + dtype(rot(x)[i] * sin[p, i]))
+ *             with the products and the sum in fp32: THREE roundings, bit for bit what torch eager gives on a CPU tensor of `dtype` for
+ *             x * cos + rotate_half(x) * sin.  Inputs and results are finite.
+ * Every position used is < rope_len: the caller's contract, like the index tables; it is not read on the host.
+ * No workspace, no state, no host read of a device table: the three calls can be captured into a HIP graph. */
+
+/* The rotation alone, IN PLACE: q = `dtype` rows [ntok, Nq, 128] and k = rows [ntok, N, 128] whose heads are contiguous and whose tokens lie
+ * q_stride / k_stride ELEMENTS apart (>= Nq * 128 / N * 128, multiples of 8), as for arcq_kv_decode_step.  Token i is rotated to
+ * positions[i % n_pos]; positions = int32 [n_pos] on the device, n_pos >= 1 divides ntok (n_pos = ntok: the general case; n_pos = q_len:
+ * a batch of equal-length sequences; n_pos = 1: a decode step).  N == 0: k is not touched and may be NULL; otherwise Nq % N == 0.
+ * ntok == 0 returns ARCQ_OK without a launch.  No two rows may overlap. */
+int arcq_rope_qk(void *q, void *k, int64_t q_stride, int64_t k_stride, const int32_t *positions, int64_t n_pos, const void *cos,
+                 const void *sin, int64_t rope_len, int64_t ntok, int64_t Nq, int64_t N, int dtype, void *stream);
+
+/* arcq_kv_append_quantize with the rotation in front, and the query's rotation with it, ONE launch: token b is written at position
+ * seq_len(b) - 1 and that is the position its q and k rows are rotated to (no position tensor).  q = rows [B, Nq, 128], k, v = rows
+ * [B, N, 128] with token strides q_stride / kv_stride as above (the three may be slices of one [B, (Nq + 2 N) * 128] projection output);
+ * q_out = `dtype` [B, Nq, 128], contiguous: the rotated q.  It may be exactly q when q is contiguous; otherwise it must not overlap q
+ * (nor k, v).  k is rotated and then quantised, v is quantised as it is.  A sequence without positions writes nothing, its q_out rows
+ * included.  GUARANTEED: pages, parameters and q_out equal, byte for byte, arcq_rope_qk (positions = seq_len - 1) followed by
+ * arcq_kv_append_quantize and a copy of q.  ARCQ_KV_16BIT: ARCQ_ERR_UNSUPPORTED.  B == 0 returns ARCQ_OK without a launch. */
+int arcq_kv_rope_append_quantize(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                 const int32_t *last_page_offset, void *q_out, const void *q, const void *k, const void *v, int64_t q_stride,
+                                 int64_t kv_stride, const void *cos, const void *sin, int64_t rope_len, int64_t B, int64_t Nq, int64_t L,
+                                 int64_t layer_idx, int64_t N, int64_t P, int format, int dtype, void *stream);
+
+/* The same in front of arcq_kv_init_quantize: tokens seqlen_indptr[b] .. seqlen_indptr[b+1] become the last positions of sequence b and
+ * are rotated to them.  Rows of q_out at or beyond seqlen_indptr[B] are not written.  B == 0 or ntok == 0 returns ARCQ_OK without a launch. */
+int arcq_kv_rope_init_quantize(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                               const int32_t *last_page_offset, void *q_out, const void *q, const void *k, const void *v, int64_t q_stride,
+                               int64_t kv_stride, const void *cos, const void *sin, int64_t rope_len, const int32_t *seqlen_indptr, int64_t ntok,
+                               int64_t B, int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int format, int dtype, void *stream);
 
 #ifdef __cplusplus
 }
