@@ -1,5 +1,29 @@
-// Pieces shared by the tile GEMM kernels (gemm_tile.hip, gemm_tile_ws.hip): parameter block, LDS tile
-// addressing, the register staging unit and its dequantising store.
+// ARC-NVFP4 GEMM for prefill shapes (M > 16): LDS-tiled fp16-MFMA kernel for gfx950.
+//
+// Replaces the CUTLASS sm120 block-scaled GEMM instantiation of the reference
+// (kernels/src/nvfp4.cu:10-33,48-74: 128x128x128 tiles, mma.sync block_scale) with a CDNA4 design:
+//
+//   HBM/L2 --(packed e2m1 + ue4m3 bytes, 16 B per lane)--> VGPR --dequantise once per block-->
+//   fp16 tiles in LDS (XOR-swizzled 128-byte rows) --ds_read_b128--> v_mfma_f32_16x16x32_f16
+//
+// Each operand byte crosses HBM/L2 in its 4.5-bit form (3.6x less traffic than an fp16 GEMM) and is
+// expanded exactly once per workgroup; the MFMA mainloop is then an ordinary fp16 contraction whose
+// products are exact (gemm_common.hpp), fp32 accumulate, alpha / bias / bf16 rounding fused in the
+// epilogue.  The bound is the dense fp16/bf16 MFMA rate (~2.5 PFLOP/s), see DESIGN.md.
+//
+// Tile: BM x BN x 64, kThreads = 256 (2x2 wave64, each 64x64 = 4x4 MFMA tiles) or 512 (2x4 waves on
+// 128x256).  Double-buffered LDS, one barrier per K step: the global loads of step k+1 are issued
+// before the MFMAs of step k and written to the other buffer after them.
+//
+// The files:
+//   gemm_tile_common.hpp  (this one) parameter block, LDS tile addressing, the register staging unit and its dequantising store, the
+//                         declarations of the host dispatch
+//   gemm_tile_body.inc    the kernel's statements, included inside the braces of each kernel definition
+//   gemm_tile_launch.hpp  gemm_tile_kernel (the kept kernel) and the templates that launch a configuration of it
+//   gemm_tile.hip         the host dispatch (shape -> tile, split-K, knobs), defined ONCE, and the reference-layout instantiations
+//   gemm_tile_rw.hip      the repacked-weight instantiations (a unit of its own: the two long compiles run in parallel)
+//   gemm_tile_ot.hip      gemm_tile_ot_kernel, the overlapped-tail kernel of the 256 x 256 8-wave tile, and its launchers
+//   gemm_tile_pl.hip      gemm_tile_pl_kernel, its paired-load sibling, and its launchers
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,11 +58,43 @@ struct TileParams {
   unsigned long long* stamps;
 #endif
 };
-constexpr int kTileStamps = 5;          // kernel entry, K loop starts, K loop ends, first / last output store issued (gemm_tile.hip)
+constexpr int kTileStamps = 5;          // kernel entry, K loop starts, K loop ends, first / last output store issued (gemm_tile_body.inc)
 // gemm_tile_ot.hip: launches gemm_tile_ot_kernel<256, 256, 2, 4, epi, b_layout> (the caller has checked that the launch is eligible)
 int launch_tile_overlap_tail(const TileParams& p, int epi, int b_layout, dim3 grid, hipStream_t stream);
 // gemm_tile_pl.hip: launches gemm_tile_pl_kernel<256, 256, 2, 4, kEpiPlain, b_layout> (a launch eligible for the overlapped tail, plain epilogue)
 int launch_tile_pair_loads(const TileParams& p, int b_layout, dim3 grid, hipStream_t stream);
+
+// ---- the host dispatch, defined once in gemm_tile.hip (library-internal: not among the exported names) ----------------------------
+#pragma GCC visibility push(hidden)
+struct TileCfg { int id, bm, bn, waves; };
+const TileCfg& tile_cfg(int id);        // the configuration ARCQ_TILE_CFG = id forces; an unknown id gives 256 x 256 with 8 waves
+bool tile_stagger();                    // ARCQ_TILE_STAGGER=0|1 (tuning)
+bool tile_pipe();                       // ARCQ_TILE_PIPE=0|1 (tuning)
+void tile_split(int64_t M, int64_t N, int64_t K, int BM, int BN, int* splits, int* atoms_per_split);
+// the configuration a launch uses, and whether it may split K (the silu-mul epilogue never does; 2 - 6 and 9 are the unsplit tuning arms)
+int effective_cfg(int64_t M, int64_t N, int64_t K, bool* may_split);
+#ifdef ARCQ_STREAM_STAMPS
+extern unsigned long long* g_tile_stamps;     // arcq_debug_set_tile_stamps; NULL: no launch is stamped
+#endif
+#pragma GCC visibility pop
+
+#ifdef ARCQ_STREAM_STAMPS
+// DIAGNOSTIC build only: the in-kernel clock of the K loop = delta s_memtime / delta s_memrealtime x 100 MHz
+// (MI355X_MICROARCH.md, "DVFS give-back" item 6) and the phases of a tile, stamped by wave 0 of every workgroup into a buffer
+// nothing else reads (tools/tile_clock.py): kTileStamps (s_memtime, s_memrealtime) pairs per workgroup -- 0 kernel entry, 1 K loop
+// starts, 2 K loop ends, 3 first output store issued, 4 last output store issued.  The product library has no stamps.
+#define ARCQ_TILE_STAMP(k)                                                                                     \
+  do {                                                                                                         \
+    if (p.stamps && tid == 0) {                                                                                \
+      unsigned long long t0_, t1_;                                                                             \
+      asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0_), "=s"(t1_)::"memory"); \
+      p.stamps[(size_t)blockIdx.x * (2 * kTileStamps) + 2 * (k)] = t0_;                                        \
+      p.stamps[(size_t)blockIdx.x * (2 * kTileStamps) + 2 * (k) + 1] = t1_;                                    \
+    }                                                                                                          \
+  } while (0)
+#else
+#define ARCQ_TILE_STAMP(k) do { } while (0)
+#endif
 
 constexpr int kBK = 64;                 // K elements per step = one scale-factor atom column (4 groups)
 constexpr int kRowBytes = kBK * 2;      // fp16 row of a tile in LDS
@@ -131,15 +187,6 @@ __device__ __forceinline__ void stage_piece(unsigned char* tile, int slot, const
   const Frag8 f = dequant8(w, j < 2 ? sf_splat<0>(sf) : sf_splat<1>(sf));
   *reinterpret_cast<uint4*>(tile + slot) = f.u;
 }
-
-#if defined(ARCQ_EXPERIMENT_A_RAW) || defined(ARCQ_EXPERIMENT_B_RAW)
-// TIMING EXPERIMENT ONLY (tools/scripts/build_variant_lib.sh; results are WRONG): the A panel (activations) staged WITHOUT its
-// dequantisation -- what a tile GEMM reading pre-dequantised fp16 activations (emitted by the quantiser) could gain at most
-__device__ __forceinline__ void stage_piece_raw(unsigned char* tile, int slot, const Staged& s, uint32_t live_mask, int j) {
-  const uint32_t w = (j == 0 ? s.q.x : j == 1 ? s.q.y : j == 2 ? s.q.z : s.q.w) & (live_mask ? 0x3bff3bffu : 0u);   // finite fp16 patterns
-  *reinterpret_cast<uint4*>(tile + slot) = make_uint4(w, w, w, w);
-}
-#endif
 
 __device__ __forceinline__ void stage_store(unsigned char* tile, const int (&slot)[4], const Staged& s, uint32_t live_mask) {
   const f16x2 sf = sf_pair_both(s.sf, live_mask);

@@ -4,25 +4,20 @@ instantiation runs without a private segment, i.e. the new position's quantiser 
 scratch.  The allocated VGPRs and the LDS of each instance are printed."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "arcquant_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+from tests.isa import HIPCC, assembly
+
 STEP = re.compile(r"kv_decode_kernelILi0ELb[01]ELi[124]ELb1EE")        # <ARCQ_KV_INT4, bf16?, GC, STEP = true> in the mangled name
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
 
 @pytest.fixture(scope="module")
-def metadata(tmp_path_factory):
+def metadata():
     """{mangled name: metadata directives} of every kernel in kv_cache.hip."""
-    asm = tmp_path_factory.mktemp("isa") / "kv_cache.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only",
-                           "-I", CSRC, os.path.join(CSRC, "kv_cache.hip"), "-o", str(asm)], stderr=subprocess.DEVNULL)
-    text = asm.read_text()
+    text = assembly("kv_cache.hip")
     return {m.group(1): text[m.start():text.index(".end_amdhsa_kernel", m.start())] for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)$", text, flags=re.M)}
 
 

@@ -7,25 +7,20 @@ Occupancy classes of the plain kernels, from a compile of the commit before this
 = 3 waves per SIMD, mx_small_kernel 52 VGPRs = 8 waves per SIMD.  Register counts may move inside a class."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "arcquant_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+from tests.isa import HIPCC, assembly
+
 PLAIN, SILU = "ILi0E", "ILi1E"          # the kEpi template argument in the mangled kernel names
 PARENT_WAVES = {"mx_tile_kernel": 3, "mx_small_kernel": 8}
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
 
-def _kernels(tmp_path, src):
+def _kernels(src):
     """{mangled name: (code text, metadata directives)} of every kernel in one source file."""
-    asm = tmp_path / (src + ".s")
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only",
-                           "-I", CSRC, os.path.join(CSRC, src), "-o", str(asm)], stderr=subprocess.DEVNULL)
-    text = asm.read_text()
+    text = assembly(src)
     out = {}
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)$", text, flags=re.M):
         name = m.group(1)
@@ -54,8 +49,8 @@ def _one(kernels, stem, tag=""):
     return hit[0]
 
 
-def test_fused_quantiser_kernels_use_no_scratch(tmp_path):
-    ks = _kernels(tmp_path, "quantize_mx.hip")
+def test_fused_quantiser_kernels_use_no_scratch():
+    ks = _kernels("quantize_mx.hip")
     fused = [n for n in ks if "mx_fused_rows_kernel" in n]
     assert len(fused) == 5, fused           # RMSNorm; SiLU*up in two layouts, each staged and direct
     for n in fused:
@@ -65,8 +60,8 @@ def test_fused_quantiser_kernels_use_no_scratch(tmp_path):
             _no_scratch(n, *ks[n])
 
 
-def test_silu_mul_gemm_variants_and_the_plain_kernels(tmp_path):
-    ks = _kernels(tmp_path, "gemm_mx.hip")
+def test_silu_mul_gemm_variants_and_the_plain_kernels():
+    ks = _kernels("gemm_mx.hip")
     for stem in ("mx_tile_kernel", "mx_small_kernel"):
         silu = _one(ks, stem, SILU)
         code, meta = ks[silu]

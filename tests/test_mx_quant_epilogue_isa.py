@@ -4,25 +4,20 @@ without VGPR spills, are block-scaled fp4 MFMA kernels (v_mfma_scale_f32, no fp4
 more LDS than the plain tile kernel: its activation image lives in the staging buffers the K loop has finished with."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "arcquant_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+from tests.isa import HIPCC, assembly
+
 PLAIN, QUANT = "ILi0E", "ILi2E"         # the kEpi template argument in the mangled kernel names
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
+def kernels():
     """{mangled name: (code text, metadata directives)} of every kernel in gemm_mx.hip."""
-    asm = tmp_path_factory.mktemp("isa") / "gemm_mx.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only",
-                           "-I", CSRC, os.path.join(CSRC, "gemm_mx.hip"), "-o", str(asm)], stderr=subprocess.DEVNULL)
-    text = asm.read_text()
+    text = assembly("gemm_mx.hip")
     out = {}
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)$", text, flags=re.M):
         name = m.group(1)

@@ -1,4 +1,4 @@
-"""The tile GEMM's epilogues (arcquant_amd/csrc/gemm_tile.hip) on shapes that take its straight-line interior-tile path, its general
+"""The tile GEMM's epilogues (arcquant_amd/csrc/gemm_tile_body.inc) on shapes that take its straight-line interior-tile path, its general
 path, or both in one launch (``-m gpu``).
 
 Which kernel each shape runs BY DEFAULT (tile_choice / the dispatch of c_api.hip; seen in a kernel trace of this file):

@@ -1,5 +1,5 @@
-"""Audit of the tile GEMM's interior-tile epilogue in the generated code (arcquant_amd/csrc/gemm_tile.hip, one compile to gfx950
-assembly, product flags).
+"""Audit of the tile GEMM's interior-tile epilogue in the generated code (arcquant_amd/csrc/gemm_tile.hip as tests/isa.py compiles it:
+gfx950 assembly, product flags).
 
 The headline instantiation, gemm_tile_kernel<256, 256, 2, 4, false, kEpiPlain, false, true> (bench.py's 4096 x 4096 x 4160), holds 8 x 4
 MFMA tiles = 32 output quads per lane.  After its last v_mfma there must be a BRANCH-FREE run of instructions that
@@ -13,28 +13,19 @@ scratch and at most 235 VGPRs (what the K loop was tuned with)."""
 import collections
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "arcquant_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+from tests.isa import HIPCC, kernel
+
 HEADLINE = "_ZN4arcq16gemm_tile_kernelILi256ELi256ELi2ELi4ELb0ELi0ELb0ELb1ELi0EEEvNS_10TileParamsE"
 QUADS = 32                          # 8 x 4 MFMA tiles of 16 x 16 per wave, 4 columns per lane each
 MAX_PER_QUAD = 8
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_headline_has_a_straight_line_interior_epilogue(tmp_path):
-    asm = tmp_path / "gemm_tile.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only",
-                           "-I", CSRC, os.path.join(CSRC, "gemm_tile.hip"), "-o", str(asm)], stderr=subprocess.DEVNULL)
-    text = asm.read_text()
-    a = text.index("\n" + HEADLINE + ":")
-    body = text[a:text.index(".end_amdhsa_kernel", a)]
-    meta = body[body.rindex(".amdhsa_kernel"):]
-    code = body[:body.rindex(".amdhsa_kernel")]
+def test_headline_has_a_straight_line_interior_epilogue():
+    code, meta = kernel("gemm_tile.hip", HEADLINE)
 
     # instruction stream with block boundaries (labels, branches) kept as None
     stream = []

@@ -1,4 +1,4 @@
-"""The K loop of the 256 x 256 8-wave tile GEMM (arcquant_amd/csrc/gemm_tile.hip, k_step_pipe) on EXACT sums (``-m gpu``).
+"""The K loop of the 256 x 256 8-wave tile GEMM (arcquant_amd/csrc/gemm_tile_body.inc, k_step_pipe) on EXACT sums (``-m gpu``).
 
 The loop keeps two LDS buffers and one barrier per K step; fragments of the next step are read behind that barrier while the current
 step is still being multiplied.  A fragment read that runs ahead of the barrier that publishes it, or a staging write that lands in a

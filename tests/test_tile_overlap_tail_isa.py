@@ -1,5 +1,5 @@
-"""Audit of the tile GEMM's overlapped tail in the generated code (arcquant_amd/csrc/gemm_tile_ot.hip, one compile to gfx950 assembly,
-product flags: the compile line of tests/test_tile_kloop_isa.py).
+"""Audit of the tile GEMM's overlapped tail in the generated code (arcquant_amd/csrc/gemm_tile_ot.hip as tests/isa.py compiles it: gfx950 assembly,
+product flags).
 
 gemm_tile_ot_kernel<256, 256, 2, 4, kEpiPlain, kBRef, 0> (no bias, no residual) is the headline kernel with another tail: the K loop is the audited one, the last
 K step of the range is multiplied without staging anything, and output stores leave under its MFMAs.  In the generated code:
@@ -11,29 +11,19 @@ K step of the range is multiplied without staging anything, and output stores le
   * at most 235 VGPRs, no scratch."""
 import os
 import re
-import subprocess
 
 import pytest
 
-from tests.test_tile_kloop_isa import _innermost_loop
+from tests.isa import HIPCC, _innermost_loop, kernel
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "arcquant_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 SIBLING = "_ZN4arcq19gemm_tile_ot_kernelILi256ELi256ELi2ELi4ELi0ELi0ELi0EEEvNS_10TileParamsE"
 ACC_REGISTERS = 128                 # 8 x 4 MFMA tiles of 16 x 16: four fp32 per lane each
 
 
 @pytest.fixture(scope="module")
-def sibling(tmp_path_factory):
+def sibling():
     """(instructions and labels of the kernel, its metadata)"""
-    asm = tmp_path_factory.mktemp("tile_overlap_tail_isa") / "gemm_tile_ot.s"
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only",
-                           "-I", CSRC, os.path.join(CSRC, "gemm_tile_ot.hip"), "-o", str(asm)], stderr=subprocess.DEVNULL)
-    text = asm.read_text()
-    a = text.index("\n" + SIBLING + ":")
-    body = text[a:text.index(".end_amdhsa_kernel", a)]
-    return body[:body.rindex(".amdhsa_kernel")], body[body.rindex(".amdhsa_kernel"):]
+    return kernel("gemm_tile_ot.hip", SIBLING)
 
 
 def _blocks(code):

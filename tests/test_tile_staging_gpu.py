@@ -1,4 +1,4 @@
-"""The tile GEMM's operand staging (arcquant_amd/csrc/gemm_tile.hip, gemm_tile_common.hpp) on EXACT results (``-m gpu``).
+"""The tile GEMM's operand staging (arcquant_amd/csrc/gemm_tile_body.inc, gemm_tile_common.hpp) on EXACT results (``-m gpu``).
 
 The staging loads address an operand as [descriptor at the tile origin] + [32-bit lane offset] + [scalar byte offset of the K step], and
 the two scale bytes of a staging unit become ONE packed fp16 pair whose halves the dequantising multiplies select.  A wrong half, a

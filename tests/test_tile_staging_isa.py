@@ -1,5 +1,5 @@
-"""Audit of the tile GEMM's operand staging in the generated code (arcquant_amd/csrc/gemm_tile.hip and gemm_tile_rw.hip, each compiled
-once to gfx950 assembly with the product flags: the compile line of tests/test_tile_kloop_isa.py; the two compiles run side by side).
+"""Audit of the tile GEMM's operand staging in the generated code (arcquant_amd/csrc/gemm_tile.hip and gemm_tile_rw.hip, as tests/isa.py
+compiles them: gfx950 assembly, product flags; the two compiles run side by side).
 
 The K loop of the 256 x 256 8-wave tile is bound by vector-instruction issue, so it must hold no vector instruction the result does not
 need.  A staging address is [tile origin, workgroup-uniform] + [lane offset, fixed for the launch] + [byte offset of the K step,
@@ -14,37 +14,21 @@ gemm_tile_kernel<256, 256, 2, 4, false, kEpiPlain, false, true> and of the same 
 and the kernels use at most 235 VGPRs and no scratch."""
 import os
 import re
-import subprocess
 
 import pytest
 
-from tests.test_tile_kloop_isa import _innermost_loop
+from tests.isa import HIPCC, _innermost_loop, assembly, kernel
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "arcquant_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 KERNEL = "_ZN4arcq16gemm_tile_kernelILi256ELi256ELi2ELi4ELb0ELi0ELb0ELb1ELi%dEEEvNS_10TileParamsE"      # %d: kBLayout
 UNITS = [("gemm_tile.hip", KERNEL % 0), ("gemm_tile_rw.hip", KERNEL % 1)]
 MAX_OTHER_VALU = 12
 
 
 @pytest.fixture(scope="module")
-def kernels(tmp_path_factory):
+def kernels():
     """(code, metadata) of the two kernels."""
-    out = tmp_path_factory.mktemp("tile_staging_isa")
-    procs = []
-    for src, _ in UNITS:
-        asm = out / (src + ".s")
-        procs.append((asm, subprocess.Popen([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-S", "--cuda-device-only",
-                                             "-I", CSRC, os.path.join(CSRC, src), "-o", str(asm)], stderr=subprocess.DEVNULL)))
-    found = {}
-    for (asm, proc), (src, name) in zip(procs, UNITS):
-        assert proc.wait() == 0, src
-        text = asm.read_text()
-        a = text.index("\n" + name + ":")
-        body = text[a:text.index(".end_amdhsa_kernel", a)]
-        found[src] = (body[:body.rindex(".amdhsa_kernel")], body[body.rindex(".amdhsa_kernel"):])
-    return found
+    assembly(*[src for src, _ in UNITS])
+    return {src: kernel(src, name) for src, name in UNITS}
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")

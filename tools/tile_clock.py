@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """In-kernel clock and phases of the tile GEMM (MI355X_MICROARCH.md "DVFS give-back" item 6): DIAGNOSTIC library only
 (make -C arcquant_amd/csrc diag), >= 2 s of back-to-back launches on random data, then per workgroup the five stamps of
-gemm_tile.hip (kernel entry, K loop starts, K loop ends, first output store issued, last output store issued; s_memtime and
+gemm_tile_body.inc (kernel entry, K loop starts, K loop ends, first output store issued, last output store issued; s_memtime and
 s_memrealtime each): delta s_memtime / delta s_memrealtime x 100 MHz over the K loop = the shader clock, and the phases in
 microseconds of the 100 MHz counter, median / p10 / p90 over the workgroups of the stamped launches.  The fp16 library GEMM cannot be
 stamped; its clock is read from GRBM_GUI_ACTIVE in a separate rocprofv3 pass (profiles/).
