@@ -7,12 +7,22 @@ decode_bound is the decode tests' (tests/kv_reference.py) with n = T_b, the any-
 here knows the kernel's partition; 2 U spa covers one rounding of each weight p s to the 16-bit type, on the numerator and on a row sum
 taken from the rounded or the unrounded weights.
 
-Measured on MI355X, max err / bound over the cases and g in {1, 2, 4, 7}: 0.056 - 0.122 in fp16, 0.124 - 0.241 in bf16; spikes 0 (diagonal)
+Measured on MI355X, max err / bound over the cases and g in {1, 2, 4, 7}: 0.056 - 0.122 in fp16, 0.124 - 0.252 in bf16; spikes 0 (diagonal)
 and 0.05 - 0.21 (first masked position) (DESIGN.md 11 "Prefill").
 
 The cases are (T, n) pairs chosen so that n and T - n straddle multiples of 16 / 32 / 64 / 128 (tests/test_kv_prefill_reference.py);
 inputs with controlled scores (the spike profile) turn one position too many -- the first masked one -- or too few -- the query's own --
-into an O(1) error."""
+into an O(1) error.
+
+What reaches below the diagonal and into the wide groups (the teeth of each are measured on the CPU against a numpy
+restatement of the algorithm, tests/test_kv_prefill_reference.py):
+  uniform   q = 0: exact fp32 sums, held to (U + 2^-21) |ref| + 2^-25 with no room for a position dropped or doubled anywhere.
+            Measured max err / bound 0.977 - 0.991 in fp16, 0.978 - 0.996 in bf16: the rounding of the result alone.
+  probes    a spike at every block edge at or below every query's own position, another target for every head: the V row, error 0 on
+            all 16 runs; "group" takes them through g = 8 .. 130 (16, 8, 4, 2, 1 tokens per tile; two chunks).
+  randn     "group" at the same g: 0.114 - 0.137 in fp16, 0.227 - 0.269 in bf16.
+  ramps     the running maximum rises in every block (up: 0.017 - 0.115 fp16, 0.094 - 0.182 bf16) or settles in block 0 while the fp16
+            weights go subnormal (down: 0.010 - 0.068, 0.057 - 0.149), under the bound above unchanged."""
 import numpy as np
 import pytest
 import torch
@@ -104,6 +114,59 @@ def test_batch_prefill_controlled_scores(case, mode, g, dtype):
                 for h in range(g * c["N"]):
                     want = torch.from_numpy(c["V"][c["start"][b] + c["own"][r], h // g]).to(dtype).double().numpy()
                     assert np.abs(got[r, h] - want).max() <= 2 * U[dtype] * np.abs(want).max() + 1e-6, (b, i, h)
+
+
+@pytest.mark.parametrize("case,g", PR.UNIFORM_RUNS)
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_batch_prefill_uniform_exact_sums(case, g, dtype):
+    """q = 0: every allowed score is exactly 0 and every weight 1, so the numerator, the zero sum and the row sum are sums of multiples
+    of 1/8, 1/16 and 1 below 2^24 units -- exact in fp32 in ANY order (premises asserted on the pages) -- and what is left is 1 / l, one
+    product and the store:  |got - ref| <= (U + 2^-21) |ref| + 2^-25  (kv_prefill_reference.uniform_bound), no spa term and no n term.
+    One position dropped, doubled, let through or masked early, or V codes in the unswapped position order, overshoots it by
+    5e5 - 4e7 (tests/test_kv_prefill_reference.py)."""
+    c = PR.profile_case(case, "uniform", dtype, g)
+    PR.uniform_premises(c)
+    o = _prefill(c)
+    _check(c, o, dtype, f"uniform {case} {dtype} g={g} (any-order bound)")
+    n_rows = int(c["qo"][-1])
+    got, ref = o.double().cpu().numpy()[:n_rows], c["ref"][:n_rows]
+    err, bound = np.abs(got - ref), PR.uniform_bound(ref, U[dtype])
+    worst = float((err / bound).max())
+    print(f"uniform {case} {dtype} g={g}: max err/exact-sum bound = {worst:.3f}")
+    assert (err <= bound).all(), f"uniform {case} {dtype} g={g}: max err / bound = {worst}"
+
+
+@pytest.mark.parametrize("case,g", PR.PROBE_RUNS)
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_batch_prefill_interior_probes(case, g, dtype):
+    """A spike at every block edge below the diagonal (kv_prefill_reference.probe_case): head h of query row i points at another of
+    0, the multiples of 32, the position before each, own - 1 and own, so neighbouring heads (and mostly neighbouring tokens) expect different V rows.  Every
+    (row, head) is its target's V row."""
+    c = PR.probe_case(case, dtype, g)
+    assert c["gap"] > 60.0, "the target's score must lead by more than 60 for the case to test what it claims"
+    assert torch.equal(c["q"].double().to(dtype).double(), c["q"].double())
+    o = _prefill(c)
+    _check(c, o, dtype, f"probes {case} {dtype} g={g}")
+    ok = PR.probe_rows_ok(o.double().cpu().numpy(), c, dtype, U[dtype])
+    assert ok.all(), f"{int((~ok).sum())} of {ok.size} (row, head) pairs are not their target's V row, first {np.argwhere(~ok)[:4].tolist()}"
+
+
+@pytest.mark.parametrize("g", PR.WIDE_GS)
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_batch_prefill_wide_groups_within_the_bound(g, dtype):
+    """randn rows under the wide groups: 16, 8, 4, 2 and 1 tokens per tile, and at g = 130 two chunks, the second with 2 live heads."""
+    c = PR.case_inputs("group", dtype, g)
+    _check(c, _prefill(c), dtype, f"group {dtype} g={g}")
+
+
+@pytest.mark.parametrize("case,profile,g", PR.RAMP_RUNS)
+@pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
+def test_batch_prefill_ramps(case, profile, g, dtype):
+    """ramp_up: a query's running maximum rises in every block, so l, the zero sum and the 64 accumulators rescale on each trip.
+    ramp_down: it settles in block 0, the rescale is skipped for the rest of the loop and the fp16 weights pass through the subnormal
+    range.  Under prefill_bound as it is."""
+    c = PR.profile_case(case, profile, dtype, g)
+    _check(c, _prefill(c), dtype, f"{profile} {case} {dtype} g={g}")
 
 
 @pytest.mark.parametrize("dtype", [F16, BF16], ids=["f16", "bf16"])
