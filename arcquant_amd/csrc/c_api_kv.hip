@@ -1,6 +1,10 @@
 // extern "C" entry points of the paged KV cache (declared in include/arcq_kv.h): argument validation.  Every shape, NULL and
-// alignment check runs before the first HIP call; the contents of the index tensors are the caller's contract (arcq_kv.h).
+// alignment check runs before the first HIP call; the contents of the index tensors are the caller's contract (arcq_kv.h).  Each
+// relation and each message is written once, as a named check below; the ORDER of the checks inside an entry point decides which of two
+// faults a call reports, is part of the contract, and is recorded case by case in tests/golden/cabi_kv_rejections.json.
 #include <hip/hip_runtime.h>
+
+#include <initializer_list>
 
 #include "../../include/arcq_kv.h"
 #include "arcq_internal.hpp"
@@ -10,10 +14,10 @@ using namespace arcq;
 namespace {
 
 constexpr int64_t kMaxDim = INT32_MAX / 2;
+constexpr const char* kQuantiserWrites = "the quantiser writes";
 
-bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-// the geometry every entry point shares; returns ARCQ_OK to go on
+// Every check returns ARCQ_OK (0) to go on, so an entry point chains them with ||: the first that fails is the one reported.
+// The geometry every entry point but arcq_rope_qk shares:
 int geometry(const char* who, int64_t B, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int format) {
   if (format != ARCQ_KV_INT4 && format != ARCQ_KV_16BIT) return fail(ARCQ_ERR_SHAPE, "%s: format must be ARCQ_KV_INT4 or ARCQ_KV_16BIT, got %d", who, format);
   if (B < 0 || L <= 0 || N <= 0 || P <= 0 || B > kMaxDim || L > kMaxDim || N > 65535 || P > kMaxDim)
@@ -23,25 +27,74 @@ int geometry(const char* who, int64_t B, int64_t L, int64_t layer_idx, int64_t N
   return ARCQ_OK;
 }
 
+// ---- the ranges and relations, each with its message
 int dtype_ok(const char* who, int dtype) {
-  if (dtype != ARCQ_KV_F16 && dtype != ARCQ_KV_BF16) return fail(ARCQ_ERR_SHAPE, "%s: dtype must be ARCQ_KV_F16 or ARCQ_KV_BF16, got %d", who, dtype);
+  return dtype != ARCQ_KV_F16 && dtype != ARCQ_KV_BF16 ? fail(ARCQ_ERR_SHAPE, "%s: dtype must be ARCQ_KV_F16 or ARCQ_KV_BF16, got %d", who, dtype) : ARCQ_OK;
+}
+int int4_only(const char* who, int format, const char* what) {          // what the entry point does with the cache: "the quantiser writes", ...
+  return format != ARCQ_KV_INT4 ? fail(ARCQ_ERR_UNSUPPORTED, "%s: %s ARCQ_KV_INT4 caches only", who, what) : ARCQ_OK;
+}
+int heads_ok(const char* who, int64_t Nq, int64_t N) {                    // the query heads of a cache of N kv heads (geometry has checked N)
+  if (Nq > 0 && Nq % N == 0 && Nq <= 65535) return ARCQ_OK;
+  return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (at most 65535)", who, (long long)Nq, (long long)N);
+}
+int pages_ok(const char* who, int64_t nnz, int64_t P) {
+  if (nnz >= 0 && nnz <= kMaxDim && nnz * P <= INT32_MAX) return ARCQ_OK;
+  return fail(ARCQ_ERR_SHAPE, "%s: nnz=%lld pages of P=%lld entries are out of range", who, (long long)nnz, (long long)P);
+}
+int ntok_ok(const char* who, int64_t ntok) {
+  return ntok < 0 || ntok > kMaxDim ? fail(ARCQ_ERR_SHAPE, "%s: ntok=%lld is out of range", who, (long long)ntok) : ARCQ_OK;
+}
+int rope_len_ok(const char* who, int64_t rope_len) {
+  return rope_len < 1 || rope_len > kMaxDim ? fail(ARCQ_ERR_SHAPE, "%s: rope_len=%lld must be at least 1", who, (long long)rope_len) : ARCQ_OK;
+}
+int strides_ok(const char* who, int64_t q_stride, int64_t Nq, int64_t kv_stride, int64_t N) {      // token strides, in elements
+  if (q_stride >= Nq * 128 && kv_stride >= N * 128 && q_stride % 8 == 0 && kv_stride % 8 == 0 && q_stride <= kMaxDim && kv_stride <= kMaxDim) return ARCQ_OK;
+  return fail(ARCQ_ERR_SHAPE, "%s: q_stride=%lld >= Nq * 128 = %lld and kv_stride=%lld >= N * 128 = %lld must be multiples of 8 elements", who,
+              (long long)q_stride, (long long)(Nq * 128), (long long)kv_stride, (long long)(N * 128));
+}
+int batch_heads_ok(const char* who, int64_t B, int64_t Nq) {
+  return B * Nq > kMaxDim ? fail(ARCQ_ERR_SHAPE, "%s: B * Nq = %lld is out of range", who, (long long)(B * Nq)) : ARCQ_OK;
+}
+int workspace_ok(const char* who, const void* workspace, int64_t workspace_bytes, int64_t need) {  // the slices' records: none without slices
+  if (need <= 0 || (workspace && workspace_bytes >= need)) return ARCQ_OK;
+  return fail(ARCQ_ERR_WORKSPACE, "%s: workspace of %lld bytes, need %lld (arcq_kv_decode_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
+}
+
+// ---- pointer lists.  A pointer that a call does not need goes in as when(false, p): neither NULL nor misaligned.  NULL is aligned, so
+// an optional pointer goes into the alignment lists as it is.  `names`: the entry point's own words for the list.
+using Ptrs = std::initializer_list<const void*>;
+alignas(16) const char kNotNeeded[16] = {};
+const void* when(bool needed, const void* p) { return needed ? p : kNotNeeded; }
+int none_null(const char* who, Ptrs ps) {
+  for (const void* p : ps)
+    if (!p) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
   return ARCQ_OK;
+}
+bool any_misaligned(Ptrs ps, uintptr_t a) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) & (a - 1)) return true;
+  return false;
+}
+int aligned16(const char* who, Ptrs ps, const char* names) {
+  return any_misaligned(ps, 16) ? fail(ARCQ_ERR_SHAPE, "%s: %s must be 16-byte aligned", who, names) : ARCQ_OK;
+}
+int aligned4(const char* who, Ptrs ps, const char* names) {
+  return any_misaligned(ps, 4) ? fail(ARCQ_ERR_SHAPE, "%s: %s must be 4-byte aligned", who, names) : ARCQ_OK;
 }
 
 int write_call(const char* who, KvWriteArgs& a, bool init, void* stream) {
-  int rc = geometry(who, a.B, a.L, a.layer, a.N, a.P, a.format);
-  if (rc != ARCQ_OK) return rc;
-  if (a.quantize && (rc = dtype_ok(who, a.dtype)) != ARCQ_OK) return rc;
-  if (a.ntok < 0 || a.ntok > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: ntok=%lld is out of range", who, (long long)a.ntok);
-  if (a.quantize && a.format != ARCQ_KV_INT4) return fail(ARCQ_ERR_UNSUPPORTED, "%s: the quantiser writes ARCQ_KV_INT4 caches only", who);
+  int rc;
+  if ((rc = geometry(who, a.B, a.L, a.layer, a.N, a.P, a.format)) || (a.quantize && (rc = dtype_ok(who, a.dtype))) || (rc = ntok_ok(who, a.ntok)) ||
+      (a.quantize && (rc = int4_only(who, a.format, kQuantiserWrites))))
+    return rc;
   if (a.B == 0 || a.ntok == 0) return ARCQ_OK;
-  if (!a.kv_data || !a.kv_param || !a.kv_indptr || !a.kv_indices || !a.last_page_offset || !a.k || !a.v || (init && !a.seqlen_indptr) ||
-      (!a.quantize && (!a.k_param || !a.v_param)))
-    return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (misaligned(a.kv_data, 16) || misaligned(a.k, 16) || misaligned(a.v, 16)) return fail(ARCQ_ERR_SHAPE, "%s: kv_data, k and v must be 16-byte aligned", who);
-  if (misaligned(a.kv_param, 4) || misaligned(a.kv_indptr, 4) || misaligned(a.kv_indices, 4) || misaligned(a.last_page_offset, 4) ||
-      misaligned(a.seqlen_indptr, 4) || misaligned(a.k_param, 4) || misaligned(a.v_param, 4))
-    return fail(ARCQ_ERR_SHAPE, "%s: kv_param, k_param, v_param and the index tensors must be 4-byte aligned", who);
+  if ((rc = none_null(who, {a.kv_data, a.kv_param, a.kv_indptr, a.kv_indices, a.last_page_offset, a.k, a.v, when(init, a.seqlen_indptr),
+                            when(!a.quantize, a.k_param), when(!a.quantize, a.v_param)})) ||
+      (rc = aligned16(who, {a.kv_data, a.k, a.v}, "kv_data, k and v")) ||
+      (rc = aligned4(who, {a.kv_param, a.kv_indptr, a.kv_indices, a.last_page_offset, a.seqlen_indptr, a.k_param, a.v_param},
+                     "kv_param, k_param, v_param and the index tensors")))
+    return rc;
   return kv_write(a, (hipStream_t)stream);
 }
 
@@ -54,28 +107,18 @@ bool overlaps(const void* out, const void* in, int64_t ntok, int64_t heads, int6
 
 int rope_write_call(const char* who, KvRopeArgs& a, bool init, int64_t rope_len, void* stream) {
   KvWriteArgs& w = a.w;
-  int rc = geometry(who, w.B, w.L, w.layer, w.N, w.P, w.format);
-  if (rc != ARCQ_OK) return rc;
-  if ((rc = dtype_ok(who, w.dtype)) != ARCQ_OK) return rc;
-  if (w.ntok < 0 || w.ntok > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: ntok=%lld is out of range", who, (long long)w.ntok);
-  if (a.Nq <= 0 || a.Nq % w.N || a.Nq > 65535)
-    return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (at most 65535)", who, (long long)a.Nq, (long long)w.N);
-  if (w.format != ARCQ_KV_INT4) return fail(ARCQ_ERR_UNSUPPORTED, "%s: the quantiser writes ARCQ_KV_INT4 caches only", who);
-  if (rope_len < 1 || rope_len > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: rope_len=%lld must be at least 1", who, (long long)rope_len);
-  if (a.q_stride < a.Nq * 128 || a.kv_stride < w.N * 128 || a.q_stride % 8 || a.kv_stride % 8 || a.q_stride > kMaxDim || a.kv_stride > kMaxDim)
-    return fail(ARCQ_ERR_SHAPE, "%s: q_stride=%lld >= Nq * 128 = %lld and kv_stride=%lld >= N * 128 = %lld must be multiples of 8 elements", who,
-                (long long)a.q_stride, (long long)(a.Nq * 128), (long long)a.kv_stride, (long long)(w.N * 128));
+  int rc;
+  if ((rc = geometry(who, w.B, w.L, w.layer, w.N, w.P, w.format)) || (rc = dtype_ok(who, w.dtype)) || (rc = ntok_ok(who, w.ntok)) ||
+      (rc = heads_ok(who, a.Nq, w.N)) || (rc = int4_only(who, w.format, kQuantiserWrites)) || (rc = rope_len_ok(who, rope_len)) ||
+      (rc = strides_ok(who, a.q_stride, a.Nq, a.kv_stride, w.N)))
+    return rc;
   if (w.ntok * (a.Nq + 2 * w.N) > 16 * (int64_t)INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: ntok * (Nq + 2 N) rows are out of range", who);
   if (w.B == 0 || w.ntok == 0) return ARCQ_OK;
-  if (!w.kv_data || !w.kv_param || !w.kv_indptr || !w.kv_indices || !w.last_page_offset || !w.k || !w.v || (init && !w.seqlen_indptr) || !a.q_out ||
-      !a.q || !a.cos || !a.sin)
-    return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (misaligned(w.kv_data, 16) || misaligned(w.k, 16) || misaligned(w.v, 16) || misaligned(a.q, 16) || misaligned(a.q_out, 16) ||
-      misaligned(a.cos, 16) || misaligned(a.sin, 16))
-    return fail(ARCQ_ERR_SHAPE, "%s: kv_data, q_out, q, k, v, cos and sin must be 16-byte aligned", who);
-  if (misaligned(w.kv_param, 4) || misaligned(w.kv_indptr, 4) || misaligned(w.kv_indices, 4) || misaligned(w.last_page_offset, 4) ||
-      misaligned(w.seqlen_indptr, 4))
-    return fail(ARCQ_ERR_SHAPE, "%s: kv_param and the index tensors must be 4-byte aligned", who);
+  if ((rc = none_null(who, {w.kv_data, w.kv_param, w.kv_indptr, w.kv_indices, w.last_page_offset, w.k, w.v, when(init, w.seqlen_indptr), a.q_out, a.q,
+                            a.cos, a.sin})) ||
+      (rc = aligned16(who, {w.kv_data, w.k, w.v, a.q, a.q_out, a.cos, a.sin}, "kv_data, q_out, q, k, v, cos and sin")) ||
+      (rc = aligned4(who, {w.kv_param, w.kv_indptr, w.kv_indices, w.last_page_offset, w.seqlen_indptr}, "kv_param and the index tensors")))
+    return rc;
   if (overlaps(a.q_out, a.q, w.ntok, a.Nq, a.q_stride) && !(a.q_out == a.q && (a.q_stride == a.Nq * 128 || w.ntok == 1)))
     return fail(ARCQ_ERR_SHAPE, "%s: q_out must be q itself (q contiguous) or must not overlap it", who);
   a.who = who;
@@ -86,15 +129,15 @@ int rope_write_call(const char* who, KvRopeArgs& a, bool init, int64_t rope_len,
 
 extern "C" {
 
+// (its head relation lets N = 0 through -- no k -- and its stride rule looks at k's only then: both stay its own)
 int arcq_rope_qk(void* q, void* k, int64_t q_stride, int64_t k_stride, const int32_t* positions, int64_t n_pos, const void* cos, const void* sin,
                  int64_t rope_len, int64_t ntok, int64_t Nq, int64_t N, int dtype, void* stream) {
   const char* who = "arcq_rope_qk";
-  int rc = dtype_ok(who, dtype);
-  if (rc != ARCQ_OK) return rc;
-  if (ntok < 0 || ntok > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: ntok=%lld is out of range", who, (long long)ntok);
+  int rc;
+  if ((rc = dtype_ok(who, dtype)) || (rc = ntok_ok(who, ntok))) return rc;
   if (Nq <= 0 || Nq > 65535 || N < 0 || N > 65535 || (N > 0 && Nq % N))
     return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (N = 0: no k; at most 65535 each)", who, (long long)Nq, (long long)N);
-  if (rope_len < 1 || rope_len > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: rope_len=%lld must be at least 1", who, (long long)rope_len);
+  if ((rc = rope_len_ok(who, rope_len))) return rc;
   if (n_pos < 1 || n_pos > kMaxDim || ntok % n_pos)
     return fail(ARCQ_ERR_SHAPE, "%s: n_pos=%lld must be at least 1 and divide ntok=%lld", who, (long long)n_pos, (long long)ntok);
   if (q_stride < Nq * 128 || q_stride % 8 || q_stride > kMaxDim || (N > 0 && (k_stride < N * 128 || k_stride % 8 || k_stride > kMaxDim)))
@@ -102,10 +145,9 @@ int arcq_rope_qk(void* q, void* k, int64_t q_stride, int64_t k_stride, const int
                 (long long)q_stride, (long long)(Nq * 128), (long long)k_stride, (long long)(N * 128));
   if (ntok * (Nq + N) > 16 * (int64_t)INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: ntok * (Nq + N) rows are out of range", who);
   if (ntok == 0) return ARCQ_OK;
-  if (!q || (N > 0 && !k) || !positions || !cos || !sin) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (misaligned(q, 16) || (N > 0 && misaligned(k, 16)) || misaligned(cos, 16) || misaligned(sin, 16))
-    return fail(ARCQ_ERR_SHAPE, "%s: q, k, cos and sin must be 16-byte aligned", who);
-  if (misaligned(positions, 4)) return fail(ARCQ_ERR_SHAPE, "%s: positions must be 4-byte aligned", who);
+  if ((rc = none_null(who, {q, when(N > 0, k), positions, cos, sin})) || (rc = aligned16(who, {q, when(N > 0, k), cos, sin}, "q, k, cos and sin")) ||
+      (rc = aligned4(who, {positions}, "positions")))
+    return rc;
   RopeQkArgs a{q, N > 0 ? k : nullptr, positions, cos, sin, q_stride, k_stride, ntok, n_pos, Nq, N, dtype};
   return kv_rope_qk(a, (hipStream_t)stream);
 }
@@ -171,22 +213,16 @@ int arcq_kv_batch_decode(void* o, const void* q, const void* kv_data, const void
                          const int32_t* last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int64_t nnz,
                          int format, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
   const char* who = "arcq_kv_batch_decode";
-  int rc = geometry(who, B, L, layer_idx, N, P, format);
-  if (rc != ARCQ_OK) return rc;
-  if ((rc = dtype_ok(who, dtype)) != ARCQ_OK) return rc;
-  if (Nq <= 0 || Nq % N || Nq > 65535)
-    return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (at most 65535)", who, (long long)Nq, (long long)N);
-  if (nnz < 0 || nnz > kMaxDim || nnz * P > INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: nnz=%lld pages of P=%lld entries are out of range", who, (long long)nnz, (long long)P);
-  if (B * Nq > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: B * Nq = %lld is out of range", who, (long long)(B * Nq));
+  int rc;
+  if ((rc = geometry(who, B, L, layer_idx, N, P, format)) || (rc = dtype_ok(who, dtype)) || (rc = heads_ok(who, Nq, N)) || (rc = pages_ok(who, nnz, P)) ||
+      (rc = batch_heads_ok(who, B, Nq)))
+    return rc;
   if (B == 0) return ARCQ_OK;
-  if (!o || !q || !kv_data || !kv_indptr || !kv_indices || !last_page_offset || (format == ARCQ_KV_INT4 && !kv_param))
-    return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (misaligned(o, 16) || misaligned(q, 16) || misaligned(kv_data, 16)) return fail(ARCQ_ERR_SHAPE, "%s: o, q and kv_data must be 16-byte aligned", who);
-  if (misaligned(kv_param, 4) || misaligned(kv_indptr, 4) || misaligned(kv_indices, 4) || misaligned(last_page_offset, 4) || misaligned(workspace, 4))
-    return fail(ARCQ_ERR_SHAPE, "%s: kv_param, the index tensors and the workspace must be 4-byte aligned", who);
-  const int64_t need = arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P);
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return fail(ARCQ_ERR_WORKSPACE, "%s: workspace of %lld bytes, need %lld (arcq_kv_decode_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
+  if ((rc = none_null(who, {o, q, kv_data, kv_indptr, kv_indices, last_page_offset, when(format == ARCQ_KV_INT4, kv_param)})) ||
+      (rc = aligned16(who, {o, q, kv_data}, "o, q and kv_data")) ||
+      (rc = aligned4(who, {kv_param, kv_indptr, kv_indices, last_page_offset, workspace}, "kv_param, the index tensors and the workspace")) ||
+      (rc = workspace_ok(who, workspace, workspace_bytes, arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P))))
+    return rc;
   KvDecodeArgs a{o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, B, Nq, L, layer_idx, N, P, nnz, format, dtype, workspace};
   return kv_decode(a, (hipStream_t)stream);
 }
@@ -195,19 +231,15 @@ int arcq_kv_batch_prefill(void* o, const void* q, const int32_t* qo_indptr, cons
                           const int32_t* kv_indices, const int32_t* last_page_offset, int64_t ntok, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
                           int64_t N, int64_t P, int64_t nnz, int format, int dtype, void* stream) {
   const char* who = "arcq_kv_batch_prefill";
-  int rc = geometry(who, B, L, layer_idx, N, P, format);
-  if (rc != ARCQ_OK) return rc;
-  if ((rc = dtype_ok(who, dtype)) != ARCQ_OK) return rc;
-  if (Nq <= 0 || Nq % N || Nq > 65535)
-    return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (at most 65535)", who, (long long)Nq, (long long)N);
-  if (nnz < 0 || nnz > kMaxDim || nnz * P > INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: nnz=%lld pages of P=%lld entries are out of range", who, (long long)nnz, (long long)P);
-  if (ntok < 0 || ntok > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: ntok=%lld is out of range", who, (long long)ntok);
-  if (format != ARCQ_KV_INT4) return fail(ARCQ_ERR_UNSUPPORTED, "%s: prefill attention reads ARCQ_KV_INT4 caches only", who);
+  int rc;
+  if ((rc = geometry(who, B, L, layer_idx, N, P, format)) || (rc = dtype_ok(who, dtype)) || (rc = heads_ok(who, Nq, N)) || (rc = pages_ok(who, nnz, P)) ||
+      (rc = ntok_ok(who, ntok)) || (rc = int4_only(who, format, "prefill attention reads")))
+    return rc;
   if (B == 0 || ntok == 0) return ARCQ_OK;
-  if (!o || !q || !qo_indptr || !kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (misaligned(o, 16) || misaligned(q, 16) || misaligned(kv_data, 16)) return fail(ARCQ_ERR_SHAPE, "%s: o, q and kv_data must be 16-byte aligned", who);
-  if (misaligned(kv_param, 4) || misaligned(qo_indptr, 4) || misaligned(kv_indptr, 4) || misaligned(kv_indices, 4) || misaligned(last_page_offset, 4))
-    return fail(ARCQ_ERR_SHAPE, "%s: kv_param and the index tensors must be 4-byte aligned", who);
+  if ((rc = none_null(who, {o, q, qo_indptr, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset})) ||
+      (rc = aligned16(who, {o, q, kv_data}, "o, q and kv_data")) ||
+      (rc = aligned4(who, {kv_param, qo_indptr, kv_indptr, kv_indices, last_page_offset}, "kv_param and the index tensors")))
+    return rc;
   KvPrefillArgs a{o, q, qo_indptr, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, ntok, B, Nq, L, layer_idx, N, P, dtype};
   return kv_prefill(a, (hipStream_t)stream);
 }
@@ -222,29 +254,20 @@ int arcq_kv_decode_step(void* o, const void* q, const void* k, const void* v, in
                         int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int format, int dtype, void* workspace, int64_t workspace_bytes,
                         void* state, int64_t state_bytes, void* stream) {
   const char* who = "arcq_kv_decode_step";
-  int rc = geometry(who, B, L, layer_idx, N, P, format);
-  if (rc != ARCQ_OK) return rc;
-  if ((rc = dtype_ok(who, dtype)) != ARCQ_OK) return rc;
-  if (Nq <= 0 || Nq % N || Nq > 65535)
-    return fail(ARCQ_ERR_SHAPE, "%s: Nq=%lld must be a positive multiple of N=%lld (at most 65535)", who, (long long)Nq, (long long)N);
-  if (nnz < 0 || nnz > kMaxDim || nnz * P > INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: nnz=%lld pages of P=%lld entries are out of range", who, (long long)nnz, (long long)P);
-  if (B * Nq > kMaxDim) return fail(ARCQ_ERR_SHAPE, "%s: B * Nq = %lld is out of range", who, (long long)(B * Nq));
-  if (format != ARCQ_KV_INT4) return fail(ARCQ_ERR_UNSUPPORTED, "%s: the decode step quantises into ARCQ_KV_INT4 caches only", who);
-  if (q_stride < Nq * 128 || kv_stride < N * 128 || q_stride % 8 || kv_stride % 8 || q_stride > kMaxDim || kv_stride > kMaxDim)
-    return fail(ARCQ_ERR_SHAPE, "%s: q_stride=%lld >= Nq * 128 = %lld and kv_stride=%lld >= N * 128 = %lld must be multiples of 8 elements", who,
-                (long long)q_stride, (long long)(Nq * 128), (long long)kv_stride, (long long)(N * 128));
+  int rc;
+  if ((rc = geometry(who, B, L, layer_idx, N, P, format)) || (rc = dtype_ok(who, dtype)) || (rc = heads_ok(who, Nq, N)) || (rc = pages_ok(who, nnz, P)) ||
+      (rc = batch_heads_ok(who, B, Nq)) || (rc = int4_only(who, format, "the decode step quantises into")) ||
+      (rc = strides_ok(who, q_stride, Nq, kv_stride, N)))
+    return rc;
   if (B == 0) return ARCQ_OK;
-  if (!o || !q || !k || !v || !kv_data || !kv_param || !kv_indptr || !kv_indices || !last_page_offset) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (misaligned(o, 16) || misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(kv_data, 16))
-    return fail(ARCQ_ERR_SHAPE, "%s: o, q, k, v and kv_data must be 16-byte aligned", who);
-  if (misaligned(kv_param, 4) || misaligned(kv_indptr, 4) || misaligned(kv_indices, 4) || misaligned(last_page_offset, 4) || misaligned(workspace, 4) ||
-      misaligned(state, 4))
-    return fail(ARCQ_ERR_SHAPE, "%s: kv_param, the index tensors, the workspace and the state must be 4-byte aligned", who);
-  const int64_t need = arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P);
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return fail(ARCQ_ERR_WORKSPACE, "%s: workspace of %lld bytes, need %lld (arcq_kv_decode_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
-  const int64_t need_state = arcq_kv_decode_step_state_bytes(B, Nq, N);
-  if (need > 0 && (!state || state_bytes < need_state))
+  const int64_t need = arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P), need_state = arcq_kv_decode_step_state_bytes(B, Nq, N);
+  if ((rc = none_null(who, {o, q, k, v, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset})) ||
+      (rc = aligned16(who, {o, q, k, v, kv_data}, "o, q, k, v and kv_data")) ||
+      (rc = aligned4(who, {kv_param, kv_indptr, kv_indices, last_page_offset, workspace, state},
+                     "kv_param, the index tensors, the workspace and the state")) ||
+      (rc = workspace_ok(who, workspace, workspace_bytes, need)))
+    return rc;
+  if (need > 0 && (!state || state_bytes < need_state))       // (the arrival counters: no slices, no state)
     return fail(ARCQ_ERR_WORKSPACE, "%s: state of %lld bytes, need %lld (arcq_kv_decode_step_state_bytes)", who, (long long)state_bytes, (long long)need_state);
   KvDecodeArgs a{o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, B, Nq, L, layer_idx, N, P, nnz, format, dtype, workspace};
   KvStepArgs st{k, v, q_stride, kv_stride, state};

@@ -22,10 +22,12 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._kvargs import _DTYPES, HEAD_DIM, _cache, _dtype_of, _heads, _params, _rows, _seqlens
 from .agemm import _need, _on, _same_device, _stream
-
-HEAD_DIM = 128
-_DTYPES = {torch.float16: _lib.KV_F16, torch.bfloat16: _lib.KV_BF16}
+# extensions in modules of their own, as kvstep is: causal prefill attention over the int4 pages (several query tokens per sequence), and
+# rotary position embedding at write time, fused into the quantising writers
+from .kvprefill import batch_prefill_i4  # noqa: F401
+from .kvrope import rope_append_kv_quantize_i4, rope_init_kv_quantize_i4, rope_qk_, rope_tables  # noqa: F401
 
 
 # ---- the quantiser as torch ops (model/kv_cache.py:22-40 computes the same)
@@ -48,62 +50,9 @@ def unpack_i4_and_asym_dequantize(q: torch.Tensor, scale: torch.Tensor, zero: to
     return codes * scale - zero
 
 
-# ---- validation
-def _cache(who, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, layer_idx, i4, dtype16=None):
-    """dtype / rank / contiguity of the cache and its tables, then their size relations -> (L, N, P, B, layer_idx)."""
-    if i4:
-        _need(kv_data, torch.uint8, "kv_data", 6)
-    else:
-        if dtype16 is None:
-            dtype16 = kv_data.dtype if getattr(kv_data, "dtype", None) in _DTYPES else torch.float16
-        _need(kv_data, dtype16, "kv_data", 6)
-    _need(kv_param, torch.float16, "kv_param", 6)
-    _need(kv_indptr, torch.int32, "kv_indptr", 1)
-    _need(kv_indices, torch.int32, "kv_indices", 1)
-    _need(last_page_offset, torch.int32, "last_page_offset", 1)
-    pages, L, two, N, P, row = kv_data.shape
-    if two != 2 or row != (HEAD_DIM // 2 if i4 else HEAD_DIM):
-        raise RuntimeError(f"kvcache.{who}: kv_data must be [pages, L, 2, N, P, {HEAD_DIM // 2 if i4 else HEAD_DIM}] (head dimension {HEAD_DIM} "
-                           f"only), got {tuple(kv_data.shape)}")
-    if tuple(kv_param.shape) != (pages, L, 2, N, P, 2):
-        raise RuntimeError(f"kvcache.{who}: kv_param must be {(pages, L, 2, N, P, 2)}, got {tuple(kv_param.shape)}")
-    if L < 1 or N < 1 or P < 1:
-        raise RuntimeError(f"kvcache.{who}: the cache needs at least one layer, head and page entry, got {tuple(kv_data.shape)}")
-    layer_idx = int(layer_idx)
-    if not 0 <= layer_idx < L:
-        raise RuntimeError(f"kvcache.{who}: layer_idx={layer_idx} is not a layer of a cache with {L}")
-    B = last_page_offset.numel()
-    if kv_indptr.numel() != B + 1:
-        raise RuntimeError(f"kvcache.{who}: kv_indptr has {kv_indptr.numel()} entries for {B} sequences (last_page_offset), expected {B + 1}")
-    return L, N, P, B, layer_idx
-
-
-def _rows(who, k, v, dtype, N, row, ntok=None):
-    for t, name in ((k, "k"), (v, "v")):
-        _need(t, dtype, name, 3)
-    if k.shape != v.shape or tuple(k.shape[1:]) != (N, row) or (ntok is not None and k.shape[0] != ntok):
-        raise RuntimeError(f"kvcache.{who}: k and v must be [{'tokens' if ntok is None else ntok}, {N}, {row}], got {tuple(k.shape)} / {tuple(v.shape)}")
-
-
-def _params(who, k_param, v_param, ntok, N):
-    for t, name in ((k_param, "k_param"), (v_param, "v_param")):
-        _need(t, torch.float16, name, 3)
-        if tuple(t.shape) != (ntok, N, 2):
-            raise RuntimeError(f"kvcache.{who}: {name} must be [{ntok}, {N}, 2], got {tuple(t.shape)}")
-
-
-def _seqlens(who, seqlen_indptr, B):
-    _need(seqlen_indptr, torch.int32, "seqlen_indptr", 1)
-    if seqlen_indptr.numel() != B + 1:
-        raise RuntimeError(f"kvcache.{who}: seqlen_indptr has {seqlen_indptr.numel()} entries for {B} sequences, expected {B + 1}")
-
-
+# ---- the calls (the argument checks they share with kvstep, kvprefill and kvrope: _kvargs.py)
 def _write(who, i4, quantize, init, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, k, v, k_param, v_param, seqlen_indptr, layer_idx):
-    row_dtype = None
-    if quantize:
-        row_dtype = getattr(k, "dtype", None)
-        if row_dtype not in _DTYPES:
-            raise RuntimeError(f"kvcache.{who}: k must be a float16 or bfloat16 tensor, got {getattr(k, 'dtype', type(k))}")
+    row_dtype = _dtype_of(f"kvcache.{who}", k, "k") if quantize else None
     L, N, P, B, layer_idx = _cache(who, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, layer_idx, i4)
     if init:
         _seqlens(who, seqlen_indptr, B)
@@ -132,17 +81,14 @@ def _write(who, i4, quantize, init, kv_data, kv_param, kv_indptr, kv_indices, la
 
 
 def _decode(who, i4, o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, layer_idx):
-    dtype = getattr(q, "dtype", None)
-    if dtype not in _DTYPES:
-        raise RuntimeError(f"kvcache.{who}: q must be a float16 or bfloat16 tensor, got {getattr(q, 'dtype', type(q))}")
+    dtype = _dtype_of(f"kvcache.{who}", q)
     _need(q, dtype, "q", 3)
     _need(o, dtype, "o", 3)
     L, N, P, B, layer_idx = _cache(who, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, layer_idx, i4, dtype)
     if q.shape != o.shape or q.shape[0] != B or q.shape[2] != HEAD_DIM:
         raise RuntimeError(f"kvcache.{who}: o and q must be [{B}, Nq, {HEAD_DIM}], got {tuple(o.shape)} / {tuple(q.shape)}")
     Nq = q.shape[1]
-    if Nq < 1 or Nq % N:
-        raise RuntimeError(f"kvcache.{who}: {Nq} query heads are not a multiple of the cache's {N} kv heads")
+    _heads(f"kvcache.{who}", Nq, N)
     _same_device(f"kvcache.{who}", q, o, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset)
     lib, nnz = _lib.lib(), kv_indices.numel()
     ws_bytes = int(lib.arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P))
@@ -247,9 +193,3 @@ class PagedKVCacheI4:
             qo = self._qo[n_new] = (torch.arange(self.batch_size + 1, dtype=torch.int32) * n_new).to(self.device)
         out["qo_indptr"] = qo
         return out
-
-
-# ---- extension: causal prefill attention over the int4 pages, several query tokens per sequence (its own module, as kvstep is)
-from .kvprefill import batch_prefill_i4  # noqa: E402,F401
-# ---- extension: rotary position embedding at write time, fused into the quantising writers (its own module too)
-from .kvrope import rope_append_kv_quantize_i4, rope_init_kv_quantize_i4, rope_qk_, rope_tables  # noqa: E402,F401

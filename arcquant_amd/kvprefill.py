@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._kvargs import _DTYPES, HEAD_DIM, _cache, _dtype_of, _heads
 from .agemm import _need, _on, _same_device, _stream
 
 
@@ -19,11 +20,8 @@ def batch_prefill_i4(o, q, qo_indptr, kv_data, kv_param, kv_indptr, kv_indices, 
     query tokens of sequence b are its LAST positions, already written (``init_kv_*``) and counted by the tables (n_b <= T_b); o, q
     float16 or bfloat16 [tokens, Nq, 128], qo_indptr int32 [B + 1], query head h reads kv head h // g.  n_b = 1 everywhere is
     ``batch_decode_i4``; n_b = 0 and rows at or beyond qo_indptr[B] are not written.  Returns o."""
-    from .kvcache import _DTYPES, HEAD_DIM, _cache
     who = "batch_prefill_i4"
-    dtype = getattr(q, "dtype", None)
-    if dtype not in _DTYPES:
-        raise RuntimeError(f"kvcache.{who}: q must be a float16 or bfloat16 tensor, got {getattr(q, 'dtype', type(q))}")
+    dtype = _dtype_of(f"kvcache.{who}", q)
     _need(q, dtype, "q", 3)
     _need(o, dtype, "o", 3)
     _need(qo_indptr, torch.int32, "qo_indptr", 1)
@@ -33,8 +31,7 @@ def batch_prefill_i4(o, q, qo_indptr, kv_data, kv_param, kv_indptr, kv_indices, 
     if q.shape != o.shape or q.shape[2] != HEAD_DIM:
         raise RuntimeError(f"kvcache.{who}: o and q must be [tokens, Nq, {HEAD_DIM}], got {tuple(o.shape)} / {tuple(q.shape)}")
     ntok, Nq = q.shape[0], q.shape[1]
-    if Nq < 1 or Nq % N:
-        raise RuntimeError(f"kvcache.{who}: {Nq} query heads are not a multiple of the cache's {N} kv heads")
+    _heads(f"kvcache.{who}", Nq, N)
     _same_device(f"kvcache.{who}", q, o, qo_indptr, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset)
     with _on(q.device):
         st = _lib.lib().arcq_kv_batch_prefill(o.data_ptr(), q.data_ptr(), qo_indptr.data_ptr(), kv_data.data_ptr(), kv_param.data_ptr(),

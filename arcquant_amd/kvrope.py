@@ -17,12 +17,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._kvargs import _DTYPES, HEAD_DIM, _cache, _dtype_of, _heads, _qkv_rows, _rope_tables, _row, _seqlens, _token_stride
 from .agemm import _need, _on, _same_device, _stream
-
-HEAD_DIM = 128
-_DTYPES = {torch.float16: _lib.KV_F16, torch.bfloat16: _lib.KV_BF16}
-# (kvcache re-exports this module's functions, so its validators -- and kvstep's, which imports kvcache -- are imported inside the calls,
-# as kvprefill does)
 
 
 def rope_tables(rope_len: int, theta: float = 10000.0, dtype=torch.bfloat16, device=None):
@@ -40,33 +36,17 @@ def rope_tables(rope_len: int, theta: float = 10000.0, dtype=torch.bfloat16, dev
     return (cos, sin) if device is None else (cos.to(device), sin.to(device))
 
 
-def _tables(who, cos, sin, dtype):
-    _need(cos, dtype, "cos", 2)
-    _need(sin, dtype, "sin", 2)
-    if cos.shape != sin.shape or cos.shape[1] != HEAD_DIM or cos.shape[0] < 1:
-        raise RuntimeError(f"kvrope.{who}: cos and sin must be [rope_len, {HEAD_DIM}] with rope_len >= 1, got {tuple(cos.shape)} / {tuple(sin.shape)}")
-    return cos.shape[0]
-
-
-def _dtype_of(who, q):
-    dtype = getattr(q, "dtype", None)
-    if dtype not in _DTYPES:
-        raise RuntimeError(f"kvrope.{who}: q must be a float16 or bfloat16 tensor, got {getattr(q, 'dtype', type(q))}")
-    return dtype
-
-
 def rope_qk_(q, k, positions, cos, sin):
     """Rotate q ([tokens, Nq, 128]) and k ([tokens, N, 128], or None) IN PLACE: token i to ``positions[i % n_pos]``, positions int32
     [n_pos] with n_pos dividing the token count (n_pos = tokens: one position per token; q_len: a batch of equal-length sequences; 1: a
     decode step).  q and k may be views whose heads are contiguous and whose token strides are multiples of 8 elements.  Returns (q, k)."""
-    from .kvstep import _row, _token_stride
     who = "rope_qk_"
-    dtype = _dtype_of(who, q)
+    dtype = _dtype_of(f"kvrope.{who}", q)
     _row(q, dtype, "q")
     if k is not None:
         _row(k, dtype, "k")
     _need(positions, torch.int32, "positions", 1)
-    rope_len = _tables(who, cos, sin, dtype)
+    rope_len = _rope_tables(who, cos, sin, dtype)
     ntok, Nq = q.shape[0], q.shape[1]
     N = 0 if k is None else k.shape[1]
     if Nq < 1 or (k is not None and (k.shape[0] != ntok or N < 1 or Nq % N)):
@@ -84,16 +64,10 @@ def rope_qk_(q, k, positions, cos, sin):
 
 
 def _rope_write(who, init, q_out, q, k, v, cos, sin, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, seqlen_indptr, layer_idx):
-    from .kvcache import _cache, _seqlens
-    from .kvstep import _row, _token_stride
-    dtype = _dtype_of(who, q)
+    dtype = _dtype_of(f"kvrope.{who}", q)
     _need(q_out, dtype, "q_out", 3)
-    _row(q, dtype, "q")
-    _row(k, dtype, "k")
-    _row(v, dtype, "v")
-    if _token_stride(k) != _token_stride(v):
-        raise RuntimeError(f"kvrope.{who}: k and v must have one token stride, got {k.stride(0)} / {v.stride(0)}")
-    rope_len = _tables(who, cos, sin, dtype)
+    _qkv_rows(f"kvrope.{who}", q, k, v, dtype)
+    rope_len = _rope_tables(who, cos, sin, dtype)
     L, N, P, B, layer_idx = _cache(who, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, layer_idx, True)
     if init:
         _seqlens(who, seqlen_indptr, B)
@@ -102,8 +76,7 @@ def _rope_write(who, init, q_out, q, k, v, cos, sin, kv_data, kv_param, kv_indpt
         raise RuntimeError(f"kvrope.{who}: q_out and q must be [{'tokens' if init else B}, Nq, {HEAD_DIM}], got {tuple(q_out.shape)} / {tuple(q.shape)}")
     if k.shape != v.shape or tuple(k.shape[:2]) != (ntok, N):
         raise RuntimeError(f"kvrope.{who}: k and v must be [{ntok}, {N}, {HEAD_DIM}], got {tuple(k.shape)} / {tuple(v.shape)}")
-    if Nq < 1 or Nq % N:
-        raise RuntimeError(f"kvrope.{who}: {Nq} query heads are not a multiple of the cache's {N} kv heads")
+    _heads(f"kvrope.{who}", Nq, N)
     _same_device(f"kvrope.{who}", q, q_out, k, v, cos, sin, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, seqlen_indptr)
     lib = _lib.lib()
     with _on(q.device):

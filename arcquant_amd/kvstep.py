@@ -11,8 +11,8 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._kvargs import _DTYPES, HEAD_DIM, _cache, _dtype_of, _heads, _qkv_rows, _token_stride
 from .agemm import _need, _on, _same_device, _stream
-from .kvcache import _DTYPES, HEAD_DIM, _cache
 
 _MAX_SLICES = 32          # the most slices per sequence arcq_kv_decode_workspace_bytes ever answers for (kv_decode_splits' cap, kv_cache.hip)
 _RECORD = HEAD_DIM + 2    # floats of a slice's record: max, sum, 128 accumulators
@@ -33,23 +33,6 @@ class DecodeStepState:
         self.workspace = torch.empty(batch_size * num_q_heads * _MAX_SLICES * _RECORD, dtype=torch.float32, device=device)
 
 
-def _row(t, dtype, name):
-    """q / k / v: 3-D of ``dtype``, heads 128 elements apart, tokens a multiple of 8 elements apart (a view is fine)."""
-    if getattr(t, "dtype", None) is not dtype:
-        raise RuntimeError(f"kvstep: {name} must be a {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
-    if t.dim() != 3:
-        raise RuntimeError(f"kvstep: {name} must be 3-D, got shape {tuple(t.shape)}")
-    if t.shape[2] != HEAD_DIM or t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != HEAD_DIM):
-        raise RuntimeError(f"kvstep: {name} must be [tokens, heads, {HEAD_DIM}] with contiguous heads (strides (s, {HEAD_DIM}, 1)), got shape "
-                           f"{tuple(t.shape)} strides {tuple(t.stride())}")
-    if t.shape[0] > 1 and (t.stride(0) % 8 or t.stride(0) < t.shape[1] * HEAD_DIM):
-        raise RuntimeError(f"kvstep: {name}'s token stride {t.stride(0)} must be a multiple of 8 elements and at least {t.shape[1] * HEAD_DIM}")
-
-
-def _token_stride(t):
-    return t.stride(0) if t.shape[0] > 1 else t.shape[1] * HEAD_DIM       # (the stride of a dimension of one entry says nothing)
-
-
 def decode_step_i4(o, q, k, v, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, layer_idx, state=None):
     """Quantise and store this token's k, v (float16 or bfloat16 [B, N, 128]) at position seq_len - 1 of an int4 cache, attend q
     ([B, Nq, 128]) over the sequence including it and write o ([B, Nq, 128], contiguous): one launch, bit for bit
@@ -57,15 +40,9 @@ def decode_step_i4(o, q, k, v, kv_data, kv_param, kv_indptr, kv_indices, last_pa
     views whose heads are contiguous and whose token strides are multiples of 8 elements (k's and v's equal).  ``state``: a
     ``DecodeStepState`` of this batch and head counts; None allocates one for the call (a zero-fill launch more)."""
     who = "decode_step_i4"
-    dtype = getattr(q, "dtype", None)
-    if dtype not in _DTYPES:
-        raise RuntimeError(f"kvstep.{who}: q must be a float16 or bfloat16 tensor, got {getattr(q, 'dtype', type(q))}")
+    dtype = _dtype_of(f"kvstep.{who}", q)
     _need(o, dtype, "o", 3)
-    _row(q, dtype, "q")
-    _row(k, dtype, "k")
-    _row(v, dtype, "v")
-    if _token_stride(k) != _token_stride(v):
-        raise RuntimeError(f"kvstep.{who}: k and v must have one token stride, got {k.stride(0)} / {v.stride(0)}")
+    _qkv_rows(f"kvstep.{who}", q, k, v, dtype)
     if state is not None and not isinstance(state, DecodeStepState):
         raise RuntimeError(f"kvstep.{who}: state must be a DecodeStepState or None, got {type(state)}")
     L, N, P, B, layer_idx = _cache(who, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, layer_idx, True)
@@ -74,8 +51,7 @@ def decode_step_i4(o, q, k, v, kv_data, kv_param, kv_indptr, kv_indices, last_pa
     if k.shape != v.shape or tuple(k.shape[:2]) != (B, N):
         raise RuntimeError(f"kvstep.{who}: k and v must be [{B}, {N}, {HEAD_DIM}], got {tuple(k.shape)} / {tuple(v.shape)}")
     Nq = q.shape[1]
-    if Nq < 1 or Nq % N:
-        raise RuntimeError(f"kvstep.{who}: {Nq} query heads are not a multiple of the cache's {N} kv heads")
+    _heads(f"kvstep.{who}", Nq, N)
     if state is not None and (state.batch_size, state.num_q_heads, state.num_kv_heads) != (B, Nq, N):
         raise RuntimeError(f"kvstep.{who}: the state was built for (batch, Nq, N) = {(state.batch_size, state.num_q_heads, state.num_kv_heads)}, "
                            f"the call has {(B, Nq, N)}")
