@@ -151,6 +151,15 @@ def _debug_set_tile_pair_loads(on: int) -> None:
     fn(int(on))
 
 
+def _debug_set_tile_quad_loads(on: int) -> None:
+    """DEBUG / tests: whether a launch that takes the paired-load sibling over the reference B layout takes the quad-load sibling instead,
+    which requests a row's four following K atoms back to back (arcq_debug_set_tile_quad_loads): 1 yes (the default), 0 no.  Process-wide;
+    read at every launch.  Inert while _debug_set_tile_pair_loads is 0."""
+    fn = _lib.lib().arcq_debug_set_tile_quad_loads
+    fn.restype, fn.argtypes = None, [_lib._i32]
+    fn(int(on))
+
+
 @functools.lru_cache(maxsize=None)
 def variant_for_kq(KQ: int) -> int:
     """Layout variant the reference's dispatch picks for this in_features (bindings.cpp:141-160)."""

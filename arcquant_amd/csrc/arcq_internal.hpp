@@ -175,6 +175,9 @@ inline bool tile_overlap_tail_forced(int64_t M, int64_t N) { return tile_overlap
 // gemm_tile_pl.hip: the value of arcq_debug_set_tile_pair_loads (1, the default: a launch that is eligible for the overlapped tail with
 // the plain epilogue takes the paired-load sibling; 0: it takes gemm_tile_ot_kernel)
 int tile_pair_loads_mode();
+// gemm_tile_ql.hip: the value of arcq_debug_set_tile_quad_loads (1, the default: a launch that takes the paired-load sibling over the
+// reference B layout takes the quad-load sibling instead; 0: it keeps gemm_tile_pl_kernel)
+int tile_quad_loads_mode();
 // gemm_regtile.hip: 16 < M <~ 1024, grids the tiled kernel cannot fill: operand fragments straight into registers, K split over waves
 int gemm_regtile_cfg(int64_t M, int64_t N, int64_t K, int epilogue);   // 0 = not this kernel, else its configuration
 int gemm_regtile(const GemmArgs& a, int cfg, hipStream_t stream);        // either B layout

@@ -1,7 +1,8 @@
 // The statements of the LDS-tiled GEMM kernel (design: gemm_tile_common.hpp), included inside the braces of a kernel definition.
 //
 // The kernel header in front of it supplies the template parameters BM, BN, WAVES_M, WAVES_N, kEpi, kBLayout, the parameter block
-// `TileParams p`, and as template parameters or constants kMfma32, kStagger, kPipe, kOverlapTail, kPairLoads and kEpiOps.
+// `TileParams p`, and as template parameters or constants kMfma32, kStagger, kPipe, kOverlapTail, kPairLoads and kEpiOps (and kQuadLoads
+// where ARCQ_TILE_BODY_QUAD_LOADS is defined: it is read behind that gate alone).
 // ONE body text under several headers: the body as a __device__ __forceinline__ function called by the kernels made hipcc generate
 // other code for every kernel, 0.3 - 0.9 % slower on the model's shapes (DESIGN.md 3.2); included as text, each kernel's code is what
 // it was.
@@ -29,6 +30,16 @@
 // from it.  The staged bytes, the pieces and their blocks, the barrier, the LDS image, the K and MFMA order, the final step and the
 // epilogue are the kOverlapTail kernel's: identical bits.  What only that kernel may DECLARE stands behind ARCQ_TILE_BODY_PAIR_LOADS,
 // which its header defines in front of the include and undefines behind it.
+// kQuadLoads (the paired-load kernel's text plus what stands behind ARCQ_TILE_BODY_QUAD_LOADS; reference B layout): a loop iteration is
+// FOUR K steps and an operand's code bytes are requested a row-quad at a time -- atoms kt + 2 .. kt + 5 of a row (each clamped), per unit
+// four 16-byte loads back to back through one descriptor and one lane offset: a whole 128-B line where the row starts one, two lines
+// otherwise.  A's quad is requested at the top of step 0 of the iteration and B's ahead of block 2 of step 2, each followed two blocks
+// later by the scale load of its FIRST atom; steps 1 and 3 request the other three scale pairs of the quad before them and no code
+// bytes (16 loads per four steps, as before; with all four scale loads in the quad's own step hipcc spilled: three registers more at
+// the step's end).  An iteration is entered with A's atom kt + 1 in sa and B's atoms kt + 1 .. kt + 3 in sb / yb (the prologue requests
+// B's atoms 2 and 3 behind atoms 0 and 1): at most five sets of one operand and three of the other are live, 256 VGPRs, no scratch.
+// The 1 - 3 steps left between the loop and the final step hold B's atoms already and request A's next atom one at a time, never an
+// atom that no step stages.  Everything else is the paired-load kernel's: identical bits.
   constexpr int kThreads = WAVES_M * WAVES_N * 64;
   constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N;     // wave tile
   constexpr int kT = kMfma32 ? 32 : 16;                   // MFMA tile edge
@@ -204,6 +215,40 @@
   using kPairSf = std::integral_constant<int, 4>;
   using kPairAll = std::integral_constant<int, 7>;
 #endif
+#ifdef ARCQ_TILE_BODY_QUAD_LOADS
+  // kQuadLoads: four atoms of a row requested together.  load_quad_q: per unit the 16 code bytes of atoms atom0 .. atom0 + 3 (each clamped
+  // to the range's last atom, so every address lies inside the descriptor), four consecutive loads fenced like load_pair's two;
+  // load_quad_sf: the scale bytes of atoms first .. last of that quad, one 2-byte load per atom and unit.  (Declared under this gate
+  // alone, like the pair's.)
+  static_assert(kBLayout == kBRef, "quads follow the reference layout's rows (repacked launches keep gemm_tile_pl_kernel)");
+  Staged qa[4][A_UNITS], qb[4][B_UNITS];   // the quad last requested: A's atoms kt + 2 .. kt + 5 (step 0), B's kt + 4 .. kt + 7 (step 2)
+  Staged yb[2][B_UNITS];                   // B's atoms kt + 2 and kt + 3 across the back-edge (sb holds kt + 1)
+  bool quad_single = false;                // kStepOneA: whether the step requests A's atom kt + 2 at all (workgroup-uniform)
+  auto quad_steps = [&](int atom0, StageStep (&s)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = stage_step(__builtin_amdgcn_readfirstlane(min(atom0 + i, a_end - 1)));
+  };
+  auto load_quad_q = [&](int atom0, const StageSrc& src, const auto& lane_q, auto& dst) {
+    StageStep s[4];
+    quad_steps(atom0, s);
+    __builtin_amdgcn_sched_barrier(0);            // (the scalar offsets are formed ahead of the first load, not inside the run)
+#pragma unroll
+    for (int u = 0; u < (int)(sizeof(dst[0]) / sizeof(dst[0][0])); ++u)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        dst[i][u].q = stage_load_q(src, lane_q[u], s[i]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  };
+  auto load_quad_sf = [&](int atom0, const StageSrc& src, const auto& lane_sf, auto& dst, int first, int last) {
+    StageStep s[4];
+    quad_steps(atom0, s);
+#pragma unroll
+    for (int u = 0; u < (int)(sizeof(dst[0]) / sizeof(dst[0][0])); ++u)
+#pragma unroll
+      for (int i = first; i <= last; ++i) dst[i][u].sf = stage_load_sf(src, lane_sf[u], s[i]);
+  };
+#endif
   auto store_step = [&](unsigned char* la, unsigned char* lb) {
 #pragma unroll
     for (int u = 0; u < A_UNITS; ++u)
@@ -286,6 +331,16 @@
   using kStepPair = std::integral_constant<int, 1>;
   using kStepOdd = std::integral_constant<int, 2>;
   using kStepNone = std::integral_constant<int, 3>;
+#ifdef ARCQ_TILE_BODY_QUAD_LOADS
+  // kQuadLoads: every step stages what sa / sb hold on entry (the caller names the sets).  kStepQuadA -- A's atoms kt + 2 .. kt + 5 into
+  // qa, codes and the first scale pair; kStepQuadB -- the same for B into qb; kStepSfA / kStepSfB (the steps behind those) -- the other
+  // three scale pairs of that quad; kStepOneA (behind the loop) -- A's atom kt + 2 alone into qa[0], if quad_single
+  using kStepQuadA = std::integral_constant<int, 4>;
+  using kStepQuadB = std::integral_constant<int, 5>;
+  using kStepOneA = std::integral_constant<int, 6>;
+  using kStepSfA = std::integral_constant<int, 7>;
+  using kStepSfB = std::integral_constant<int, 8>;
+#endif
   auto k_step_pipe = [&](int kt, unsigned char* ca, unsigned char* cb, unsigned char* na, unsigned char* nb, auto step_kind) {
     static_assert(kMfma32 || TM % 2 == 0, "pairs of A fragments");
     constexpr int kKind = decltype(step_kind)::value;
@@ -304,6 +359,18 @@
       for (int u = 0; u < B_UNITS; ++u) tb[u] = sb2[u];
     }
     if constexpr (kKind == kStepPair::value) load_pair(min(kt + 2, a_end - 1), min(kt + 3, a_end - 1), sa2, sb2, sa, sb, kPairA{});   // ... and the next: A's code pairs here
+#endif
+#ifdef ARCQ_TILE_BODY_QUAD_LOADS
+    if constexpr (kKind == kStepQuadA::value) load_quad_q(kt + 2, a_src, a_q, qa);          // A's quad here, its first scale load ahead of block 2
+    if constexpr (kKind == kStepSfA::value) load_quad_sf(kt + 1, a_src, a_sf, qa, 1, 3);
+    if constexpr (kKind == kStepSfB::value) load_quad_sf(kt + 1, b_src, b_sf, qb, 1, 3);
+    if constexpr (kKind == kStepOneA::value) {
+      if (quad_single) {                          // (kt + 2 < a_end: a step stages it)
+        const StageStep one = stage_step(__builtin_amdgcn_readfirstlane(kt + 2));
+#pragma unroll
+        for (int u = 0; u < A_UNITS; ++u) qa[0][u] = stage_load(a_src, a_q[u], a_sf[u], one);
+      }
+    }
 #endif
     __builtin_amdgcn_sched_barrier(0);
     constexpr int kPieces = (A_UNITS + B_UNITS) * 4, kBlocks = kMfma32 ? 4 : TM;   // 32x32x16: one block per 16-wide K slice
@@ -372,6 +439,19 @@
         if constexpr (kKind == kStepPair::value) {          // ... B's code pairs ahead of block 2, the scale loads of both ahead of block 4
           if (q == 2) load_pair(min(kt + 2, a_end - 1), min(kt + 3, a_end - 1), sa2, sb2, sa, sb, kPairB{});
           if (q == 4) load_pair(min(kt + 2, a_end - 1), min(kt + 3, a_end - 1), sa2, sb2, sa, sb, kPairSf{});
+          if (q == 2 || q == 4) __builtin_amdgcn_sched_barrier(0);
+        }
+#endif
+#ifdef ARCQ_TILE_BODY_QUAD_LOADS
+        if constexpr (kKind == kStepQuadA::value) {         // ... the first scale load of A's quad ahead of block 2
+          if (q == 2) {
+            load_quad_sf(kt + 2, a_src, a_sf, qa, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        if constexpr (kKind == kStepQuadB::value) {         // B's quad ahead of block 2, its first scale load ahead of block 4
+          if (q == 2) load_quad_q(kt + 2, b_src, b_q, qb);
+          if (q == 4) load_quad_sf(kt + 2, b_src, b_sf, qb, 0, 0);
           if (q == 2 || q == 4) __builtin_amdgcn_sched_barrier(0);
         }
 #endif
@@ -491,6 +571,17 @@
 #ifdef ARCQ_TILE_BODY_PAIR_LOADS                // (the same two steps, ordered as the even step orders its own)
   Staged sa0[A_UNITS], sb0[B_UNITS];
   load_pair(a_begin, min(a_begin + 1, a_end - 1), sa0, sb0, sa, sb, kPairAll{});
+#ifdef ARCQ_TILE_BODY_QUAD_LOADS                // ... and behind them B's atoms 2 and 3, which the loop's first two steps do not request
+  {
+    const StageStep b_s2 = stage_step(__builtin_amdgcn_readfirstlane(min(a_begin + 2, a_end - 1)));
+    const StageStep b_s3 = stage_step(__builtin_amdgcn_readfirstlane(min(a_begin + 3, a_end - 1)));
+#pragma unroll
+    for (int u = 0; u < B_UNITS; ++u) {
+      yb[0][u] = stage_load(b_src, b_q[u], b_sf[u], b_s2);
+      yb[1][u] = stage_load(b_src, b_q[u], b_sf[u], b_s3);
+    }
+  }
+#endif
 #else
   load_step(a_begin);
   Staged sa0[A_UNITS], sb0[B_UNITS];
@@ -546,13 +637,58 @@
     using Even = std::conditional_t<kPairLoads, kStepPair, kStepOne>;
     using Odd = std::conditional_t<kPairLoads, kStepOdd, kStepOne>;
     using Last = std::conditional_t<kPairLoads, kStepNone, kStepOne>;
-    for (; kt + 2 < a_end; kt += 2) {
-      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, Even{});
-      k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0, Odd{});
-    }
-    if (kt + 1 < a_end) {
-      k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, Last{});
-      tail_buf = A_TILE + B_TILE;
+#ifdef ARCQ_TILE_BODY_QUAD_LOADS
+    if constexpr (kQuadLoads) {
+      auto stage_from = [&](const Staged (&a)[A_UNITS], const Staged (&b)[B_UNITS]) {     // names the sets the next step stages
+#pragma unroll
+        for (int u = 0; u < A_UNITS; ++u) sa[u] = a[u];
+#pragma unroll
+        for (int u = 0; u < B_UNITS; ++u) sb[u] = b[u];
+      };
+      // four steps per iteration while all four stage an atom of the range: entered with A's atom kt + 1 in sa and B's kt + 1 .. kt + 3 in
+      // sb, yb[0], yb[1], left the same way
+      for (; kt + 4 < a_end; kt += 4) {
+        k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, kStepQuadA{});
+        stage_from(qa[0], yb[0]);
+        k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0, kStepSfA{});
+        stage_from(qa[1], yb[1]);
+        k_step_pipe(kt + 2, lds_a0, lds_b0, lds_a1, lds_b1, kStepQuadB{});
+        stage_from(qa[2], qb[0]);
+        k_step_pipe(kt + 3, lds_a1, lds_b1, lds_a0, lds_b0, kStepSfB{});
+        stage_from(qa[3], qb[1]);
+#pragma unroll
+        for (int u = 0; u < B_UNITS; ++u) {
+          yb[0][u] = qb[2][u];
+          yb[1][u] = qb[3][u];
+        }
+      }
+      // the 0 - 3 steps left ahead of the final step: B's atoms are held, A's next one is requested alone by the step before its own
+      const int left = a_end - 1 - kt;
+      if (left >= 1) {
+        quad_single = left >= 2;
+        k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, kStepOneA{});
+        if (left >= 2) {
+          stage_from(qa[0], yb[0]);
+          quad_single = left >= 3;
+          k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0, kStepOneA{});
+          if (left >= 3) {
+            stage_from(qa[0], yb[1]);
+            k_step_pipe(kt + 2, lds_a0, lds_b0, lds_a1, lds_b1, kStepNone{});
+          }
+        }
+        if (left & 1) tail_buf = A_TILE + B_TILE;
+      }
+    } else
+#endif
+    {
+      for (; kt + 2 < a_end; kt += 2) {
+        k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, Even{});
+        k_step_pipe(kt + 1, lds_a1, lds_b1, lds_a0, lds_b0, Odd{});
+      }
+      if (kt + 1 < a_end) {
+        k_step_pipe(kt, lds_a0, lds_b0, lds_a1, lds_b1, Last{});
+        tail_buf = A_TILE + B_TILE;
+      }
     }
   } else if constexpr (kPipe) {
     for (; kt + 1 < a_end; kt += 2) {

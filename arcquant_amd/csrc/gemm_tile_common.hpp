@@ -24,6 +24,7 @@
 //   gemm_tile_rw.hip      the repacked-weight instantiations (a unit of its own: the two long compiles run in parallel)
 //   gemm_tile_ot.hip      gemm_tile_ot_kernel, the overlapped-tail kernel of the 256 x 256 8-wave tile, and its launchers
 //   gemm_tile_pl.hip      gemm_tile_pl_kernel, its paired-load sibling, and its launchers
+//   gemm_tile_ql.hip      gemm_tile_ql_kernel, the quad-load sibling of that one (reference B layout), and its launchers
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,6 +64,8 @@ constexpr int kTileStamps = 5;          // kernel entry, K loop starts, K loop e
 int launch_tile_overlap_tail(const TileParams& p, int epi, int b_layout, dim3 grid, hipStream_t stream);
 // gemm_tile_pl.hip: launches gemm_tile_pl_kernel<256, 256, 2, 4, kEpiPlain, b_layout> (a launch eligible for the overlapped tail, plain epilogue)
 int launch_tile_pair_loads(const TileParams& p, int b_layout, dim3 grid, hipStream_t stream);
+// gemm_tile_ql.hip: launches gemm_tile_ql_kernel<256, 256, 2, 4, kEpiPlain, kBRef> (a launch the paired-load kernel would take, reference B layout)
+int launch_tile_quad_loads(const TileParams& p, dim3 grid, hipStream_t stream);
 
 // ---- the host dispatch, defined once in gemm_tile.hip (library-internal: not among the exported names) ----------------------------
 #pragma GCC visibility push(hidden)

@@ -61,7 +61,9 @@ static int launch_tile(const GemmArgs& a, hipStream_t stream, bool allow_split =
     overlap_tail = pipe && (kEpi == kEpiSiluMul ? tile_overlap_tail_mode() == 2 : tile_overlap_tail_mode() != 0) && a.M % BM == 0 && a.N % BN == 0 && p.splits <= 1 && a.out_dtype == ARCQ_OUT_BF16 &&
                    (int64_t)BM * a.N < (1ll << 31) && ((reinterpret_cast<uintptr_t>(a.bias) | reinterpret_cast<uintptr_t>(a.residual)) & 7) == 0;
   // ... and of those the plain-epilogue launches take its paired-load sibling (gemm_tile_pl.hip) unless the debug setter says 0
-  if (overlap_tail && kEpi == kEpiPlain && tile_pair_loads_mode() != 0) rc = launch_tile_pair_loads(p, kBLayout, grid, stream);
+  // ... and of those the launches over the reference B layout its quad-load sibling (gemm_tile_ql.hip) unless ITS debug setter says 0
+  if (overlap_tail && kEpi == kEpiPlain && kBLayout == kBRef && tile_pair_loads_mode() != 0 && tile_quad_loads_mode() != 0) rc = launch_tile_quad_loads(p, grid, stream);
+  else if (overlap_tail && kEpi == kEpiPlain && tile_pair_loads_mode() != 0) rc = launch_tile_pair_loads(p, kBLayout, grid, stream);
   else if (overlap_tail) rc = launch_tile_overlap_tail(p, kEpi, kBLayout, grid, stream);
   else if (!pipe && !stagger) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, false, kBLayout>>(grid, block, lds, stream, who, p);
   else if (pipe) rc = launch_kernel<gemm_tile_kernel<BM, BN, WAVES_M, WAVES_N, kMfma32, kEpi, false, true, kBLayout>>(grid, block, lds, stream, who, p);

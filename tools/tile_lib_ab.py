@@ -3,7 +3,7 @@
 each build in its own subprocess, rounds interleaved; per shape and build the values of every round, their median and their
 run-to-run band (max - min).  usage: tile_lib_ab.py [--rounds N] name=path[:ENV=VAL] ...     (the comparator first)
 ENV ARCQ_AB_OVERLAP_TAIL=0|1|2 calls arcq_debug_set_tile_overlap_tail with that value first (a library that has the setter),
-ARCQ_AB_PAIR_LOADS=0|1 arcq_debug_set_tile_pair_loads."""
+ARCQ_AB_PAIR_LOADS=0|1 arcq_debug_set_tile_pair_loads, ARCQ_AB_QUAD_LOADS=0|1 arcq_debug_set_tile_quad_loads."""
 import json
 import os
 import statistics
@@ -26,6 +26,8 @@ if os.environ.get('ARCQ_AB_OVERLAP_TAIL'):
     agemm._debug_set_tile_overlap_tail(int(os.environ['ARCQ_AB_OVERLAP_TAIL']))
 if os.environ.get('ARCQ_AB_PAIR_LOADS'):
     agemm._debug_set_tile_pair_loads(int(os.environ['ARCQ_AB_PAIR_LOADS']))
+if os.environ.get('ARCQ_AB_QUAD_LOADS'):
+    agemm._debug_set_tile_quad_loads(int(os.environ['ARCQ_AB_QUAD_LOADS']))
 dev = torch.device('cuda:0')
 out = []
 for (M, N, KQ, epi, *ke) in {shapes!r}:
@@ -73,6 +75,7 @@ if __name__ == "__main__":
     for rnd in range(rounds):
         for n, s in specs.items():
             acc[n].append(run(s))
+            print(f"round {rnd + 1} of {rounds}: {n} done", file=sys.stderr, flush=True)      # (rows come at the end: a sign of life)
     for i, shp in enumerate(SHAPES):
         row = {"shape": list(shp[:3]), "KE": shp[4] if len(shp) > 4 else 64, "epilogue": shp[3] or "plain"}
         for n in specs:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Workload of a rocprofv3 --pmc pass over the tile GEMM's headline launch (bench.py's problem: M = N = 4096, KQ = 4096, KE = 64): N
 back-to-back launches through agemm.matmul (reference layout) or, with `rw`, agemm.matmul_rw (repacked weight).  ARCQ_HIP_LIB selects
-the library.  usage: rocprofv3 --pmc <counters> --kernel-trace ... -- python3 tools/tile_pmc_run.py [ref|rw] [launches]
+the library, ARCQ_AB_PAIR_LOADS / ARCQ_AB_QUAD_LOADS = 0|1 call arcq_debug_set_tile_pair_loads / arcq_debug_set_tile_quad_loads first.  usage: rocprofv3 --pmc <counters> --kernel-trace ... -- python3 tools/tile_pmc_run.py [ref|rw] [launches]
 (tools/pmc_summarize.py <dir> gemm_tile <launches> then gives the per-launch means)."""
 import os
 import sys
@@ -14,6 +14,10 @@ from bench import make_problem  # noqa: E402
 
 route = sys.argv[1] if len(sys.argv) > 1 else "ref"
 launches = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+if os.environ.get("ARCQ_AB_PAIR_LOADS"):
+    agemm._debug_set_tile_pair_loads(int(os.environ["ARCQ_AB_PAIR_LOADS"]))
+if os.environ.get("ARCQ_AB_QUAD_LOADS"):
+    agemm._debug_set_tile_quad_loads(int(os.environ["ARCQ_AB_QUAD_LOADS"]))
 dev = torch.device("cuda:0")
 M, N, KQ, KE = 4096, 4096, 4096, 64
 p = make_problem(M, N, KQ, KE, dev)
