@@ -133,6 +133,12 @@ int gemm_repacked(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipS
 int gemm_repacked_mid_supported(int64_t M, int64_t N, int64_t K);                                          // gemm_rowmid.hip: 16 < M <= 64
 int gemm_repacked_mid(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipStream_t stream);
 int gemm_repacked_stream(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipStream_t stream);   // gemm_stream.hip (A-B)
+// kEpiSiluMul on the M <= 16 repacked kernels (D stays gate|up, absmax_slots gets max |silu(g) * u| per row block): 0, or the error set
+inline int repacked_silu_args_check(const GemmArgs& a) {
+  if (a.epilogue == kEpiSiluMul && (!a.absmax_slots || (a.N % 4) || a.bias || a.residual || a.out_dtype != ARCQ_OUT_BF16))
+    return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4_repacked_silu_absmax: needs absmax_slots, N %% 4 == 0, bf16 output, no bias / residual");
+  return 0;
+}
 struct FusedArgs {
   int kind;                   // ARCQ_SRC_RMSNORM | ARCQ_SRC_DYNAMIC
   int silu_act;               // ARCQ_SRC_RMSNORM only: D = bf16 silu(gate) * up [M, N/2] of interleaved gate|up rows + out_slots

@@ -87,6 +87,14 @@ __device__ __forceinline__ int64_t sf_atom_offset(int r, int atom, int atoms_k) 
 // alpha*acc (+bias) -> bf16 / fp32 store helpers
 __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) { return f32_to_bf16_bits(a) | (f32_to_bf16_bits(b) << 16); }
 
+// max |silu(g) * u| (bf16 magnitude bits) of a lane's four outputs alpha * sum[0..3] = (g, u, g, u) of interleaved gate|up rows, formed
+// from the very bf16 values a plain bf16 epilogue stores, with the quantiser's own silu_mul_bf16 (arcq_device.hpp)
+__device__ __forceinline__ uint32_t silu_absmax(float alpha, const float (&sum)[4]) {
+  const uint32_t b0 = f32_to_bf16_bits(alpha * sum[0]), b1 = f32_to_bf16_bits(alpha * sum[1]);
+  const uint32_t b2 = f32_to_bf16_bits(alpha * sum[2]), b3 = f32_to_bf16_bits(alpha * sum[3]);
+  return max(silu_mul_bf16(b0, b1) & 0x7fffu, silu_mul_bf16(b2, b3) & 0x7fffu);
+}
+
 // Epilogue helpers shared by the GEMM kernels; P is any parameter block with D, N, bias, residual, out_dtype.
 // Idx = uint32_t inside the decode kernel (M <= 16: element offsets fit 32 bits, so the address is an SGPR base
 // plus one VGPR offset instead of a 64-bit VGPR pair per lane -- the kernel is register bound), size_t elsewhere.

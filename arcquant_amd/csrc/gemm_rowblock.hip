@@ -21,13 +21,15 @@
 // v_mfma_f32_16x16x32_f16 with the activation fragments read from the LDS image, and -- when a row block is split over
 // S waves -- adds the S partial tiles through LDS at the very end.  ~50 instructions per 16 bytes of weights.
 // Shapes: M <= 16 and an activation image that fits LDS (M * K_padded * 2 B <= 160 KB); others use the other kernels.
+// The tile pair and its loads, the tile contraction and the image unit writer are rowblock_core.hpp's, shared with gemm_rowmid.hip
+// and gemm_stream.hip; the work split, the ring loop, the slice reduction and the epilogue prefetch are written out per kernel
+// (rowblock_core.hpp says why).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "arcq_internal.hpp"
-#include "gemm_common.hpp"
-#include "rowblock_split.hpp"
+#include "rowblock_core.hpp"
 
 namespace arcq {
 
@@ -48,12 +50,6 @@ struct RowblockParams {
   int slices;             // waves that share one row block (1, 2, 4 or 8)
   int a_stride;           // bytes per token row of the LDS image
   unsigned int* silu_slots;   // kSiluAbsmax: one word per row block, max |silu(gate) * up| of its outputs (bf16 bits)
-};
-
-typedef uint32_t rb_u32x4 __attribute__((ext_vector_type(4)));
-struct RowblockRegs {     // one tile pair of this lane: 2 x 16 bytes of codes, 4 scale bytes
-  rb_u32x4 b0, b1;
-  uint32_t s;
 };
 
 constexpr int kRbWaves = 8, kRbThreads = kRbWaves * 64;
@@ -108,40 +104,26 @@ __global__ __launch_bounds__(kRbThreads, 4) void gemm_rowblock_kernel(RowblockPa
   const uint8_t* sp = p.RSF + ((size_t)rbc * p.pairs + pr_load) * 256 + lane * 4;
   const int last = npairs > 0 ? npairs - 1 : 0;
   int issued = 0;
-  auto issue = [&](RowblockRegs& r) __attribute__((always_inline)) {       // unpredicated; the cursor stops at the last pair
+  auto issue = [&](WeightPair& r) __attribute__((always_inline)) {         // unpredicated; the cursor stops at the last pair
     const int i = min(issued, last);
-    // a weight byte is read once per launch by one CU: non-temporal loads (gemm_common.hpp)
-    r.b0 = ARCQ_WLOAD(reinterpret_cast<const rb_u32x4*>(wp + (size_t)i * 2048));
-    r.b1 = ARCQ_WLOAD(reinterpret_cast<const rb_u32x4*>(wp + (size_t)i * 2048 + 1024));
-    r.s = ARCQ_WLOAD(reinterpret_cast<const uint32_t*>(sp + (size_t)i * 256));
+    weight_pair_load(r, wp, sp, i);
     ++issued;
   };
-  RowblockRegs r0, r1, r2;
+  WeightPair r0, r1, r2;
   issue(r0);
   issue(r1);
   issue(r2);
 
   // ---- activation image: unit = 32 elements (16 packed bytes, two scale bytes) -> 64 bytes of fp16
-  auto put_unit = [&](int u, uint4 qv, uint32_t sf) __attribute__((always_inline)) {
-    const int m = u / upr, c = u - m * upr;
-    uint4 f0 = make_uint4(0, 0, 0, 0), f1 = f0, f2 = f0, f3 = f0;
-    if (c < real) {
-      sf >>= (c & 1) * 16;
-      const f16x2 s0 = sf_pair_at(sf, 0), s1 = sf_pair_at(sf, 8);
-      f0 = dequant8(qv.x, s0).u; f1 = dequant8(qv.y, s0).u; f2 = dequant8(qv.z, s1).u; f3 = dequant8(qv.w, s1).u;
-    }
-    uint4* dst = reinterpret_cast<uint4*>(a_img + (size_t)m * p.a_stride + c * 64);
-    dst[0] = f0; dst[1] = f1; dst[2] = f2; dst[3] = f3;
-  };
 #pragma unroll
   for (int j = 0; j < kUnits; ++j) {
     const int u = tid + j * kRbThreads;
-    if (u < units) put_unit(u, qv_pre[j], sf_pre[j]);
+    if (u < units) image_put_unit(a_img, p.a_stride, u, upr, real, qv_pre[j], sf_pre[j]);
   }
   for (int u = tid + kUnits * kRbThreads; u < units; u += kRbThreads) {       // beyond the prefetch (M * K > 128 K elements)
     const int m = u / upr, c = min(u - m * upr, real - 1);
-    put_unit(u, *reinterpret_cast<const uint4*>(p.A + (size_t)m * (p.K >> 1) + c * 16),
-             *reinterpret_cast<const uint32_t*>(p.SFA + sf_atom_offset(m, c >> 1, atoms_k)));
+    image_put_unit(a_img, p.a_stride, u, upr, real, *reinterpret_cast<const uint4*>(p.A + (size_t)m * (p.K >> 1) + c * 16),
+                   *reinterpret_cast<const uint32_t*>(p.SFA + sf_atom_offset(m, c >> 1, atoms_k)));
   }
   __syncthreads();
 
@@ -149,31 +131,16 @@ __global__ __launch_bounds__(kRbThreads, 4) void gemm_rowblock_kernel(RowblockPa
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   const unsigned char* a_lane = a_img + (size_t)min(rl, p.M - 1) * p.a_stride + (size_t)pr_begin * 512 + q * 64;   // tokens >= M: any row
   int done = 0;
-  auto tile = [&](rb_u32x4 b, uint32_t s16, const unsigned char* ap) __attribute__((always_inline)) {
-    Frag8 a0, a1, a2, a3;
-    a0.u = *reinterpret_cast<const uint4*>(ap);
-    a1.u = *reinterpret_cast<const uint4*>(ap + 16);
-    a2.u = *reinterpret_cast<const uint4*>(ap + 32);
-    a3.u = *reinterpret_cast<const uint4*>(ap + 48);
-    const f16x2 s0 = sf_pair_at(s16, 0), s1 = sf_pair_at(s16, 8);
-    const Frag8 b0 = dequant8(b.x, s0), b1 = dequant8(b.y, s0), b2 = dequant8(b.z, s1), b3 = dequant8(b.w, s1);
-    // weights are the MFMA A operand (rows = weight rows), activations the B operand (columns = tokens)
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0.v, a0.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b1.v, a1.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b2.v, a2.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b3.v, a3.v, acc, 0, 0, 0);
-  };
-  auto step = [&](RowblockRegs& r) __attribute__((always_inline)) {
+  auto step = [&](WeightPair& r) __attribute__((always_inline)) {
     const unsigned char* ap = a_lane + (size_t)done * 512;
-    tile(r.b0, r.s, ap);
-    tile(r.b1, r.s >> 16, ap + 256);
+    acc = tile_image(r.b0, r.s, ap, acc);
+    acc = tile_image(r.b1, r.s >> 16, ap + 256, acc);
     issue(r);                                               // refill: three pairs ahead
     __builtin_amdgcn_sched_barrier(0);                      // hipcc otherwise sinks all refills to the end of the unrolled body
     ++done;
   };
   // bias / residual of this wave's output tile (the slice-0 wave finishes the row block): fetched now, behind the ring's first
   // loads, instead of as a global round trip after the last barrier (N % 4 == 0: 8-byte loads; by-name registers)
-  typedef uint32_t rb_u32x2 __attribute__((ext_vector_type(2)));
   rb_u32x2 ep_bias = {0, 0}, ep_res = {0, 0};
   const bool ep_pre = !kSiluAbsmax && (p.N & 3) == 0 && (p.bias || p.residual);
   if (ep_pre && slice == 0 && active && rl < p.M && rb * 16 + 4 * q < p.N) {
@@ -209,11 +176,7 @@ __global__ __launch_bounds__(kRbThreads, 4) void gemm_rowblock_kernel(RowblockPa
   }
   if constexpr (kSiluAbsmax) {                              // N % 4 == 0, bf16 out, no bias / residual (checked by the launcher)
     uint32_t m = 0;
-    if (active && rl < p.M && n0 < p.N) {
-      const uint32_t b0 = f32_to_bf16_bits(alpha * sum[0]), b1 = f32_to_bf16_bits(alpha * sum[1]);
-      const uint32_t b2 = f32_to_bf16_bits(alpha * sum[2]), b3 = f32_to_bf16_bits(alpha * sum[3]);
-      m = max(silu_mul_bf16(b0, b1) & 0x7fffu, silu_mul_bf16(b2, b3) & 0x7fffu);
-    }
+    if (active && rl < p.M && n0 < p.N) m = silu_absmax(alpha, sum);
 #pragma unroll
     for (int sh = 32; sh > 0; sh >>= 1) m = max(m, (uint32_t)__shfl_down((int)m, sh, 64));
     if (lane == 0 && active) p.silu_slots[rb] = m;
@@ -262,7 +225,7 @@ __global__ __launch_bounds__(kRbThreads, 2) void gemm_rowblock_direct_kernel(Row
   const uint8_t* srow = p.SFA + sf_atom_offset(tok, 0, atoms_k) + (q & 1) * 2;
   const int last = npairs > 0 ? npairs - 1 : 0;
   int issued = 0;
-  auto issue = [&](RowblockRegs& r, RowblockActRegs& x) __attribute__((always_inline)) {   // unpredicated; the cursor stops at the last pair
+  auto issue = [&](WeightPair& r, RowblockActRegs& x) __attribute__((always_inline)) {   // unpredicated; the cursor stops at the last pair
     const int i = min(issued, last);
     const int t0 = 2 * (pr_load + i), t1 = t0 + 1;                      // the pair's two 128-element tiles
     // a tile past K (padding): bytes of the last real tile (any finite codes), its weight scales are zero.  The second half of a
@@ -282,20 +245,16 @@ __global__ __launch_bounds__(kRbThreads, 2) void gemm_rowblock_direct_kernel(Row
     x.a1 = *reinterpret_cast<const rb_u32x4*>(arow + a_off(t1));
     x.s0 = *reinterpret_cast<const uint16_t*>(srow + s_off(t0));
     x.s1 = *reinterpret_cast<const uint16_t*>(srow + s_off(t1));
-    // a weight byte is read once per launch by one CU: non-temporal loads (gemm_common.hpp)
-    r.b0 = ARCQ_WLOAD(reinterpret_cast<const rb_u32x4*>(wp + (size_t)i * 2048));
-    r.b1 = ARCQ_WLOAD(reinterpret_cast<const rb_u32x4*>(wp + (size_t)i * 2048 + 1024));
-    r.s = ARCQ_WLOAD(reinterpret_cast<const uint32_t*>(sp + (size_t)i * 256));
+    weight_pair_load(r, wp, sp, i);
     ++issued;
   };
-  RowblockRegs r0, r1, r2;
+  WeightPair r0, r1, r2;
   RowblockActRegs x0, x1, x2;
   issue(r0, x0);
   issue(r1, x1);
   issue(r2, x2);
 
   // bias / residual of this wave's output tile (the slice-0 wave finishes the row block), behind the ring's first loads
-  typedef uint32_t rb_u32x2 __attribute__((ext_vector_type(2)));
   rb_u32x2 ep_bias = {0, 0}, ep_res = {0, 0};
   const bool ep_pre = !kSiluAbsmax && (p.N & 3) == 0 && (p.bias || p.residual);
   if (ep_pre && slice == 0 && active && rl < p.M && rb * 16 + 4 * q < p.N) {
@@ -306,20 +265,9 @@ __global__ __launch_bounds__(kRbThreads, 2) void gemm_rowblock_direct_kernel(Row
 
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   int done = 0;
-  auto tile = [&](rb_u32x4 b, uint32_t s16, rb_u32x4 a, uint32_t as16) __attribute__((always_inline)) {
-    const f16x2 t0 = sf_pair_at(as16, 0), t1 = sf_pair_at(as16, 8);
-    const Frag8 a0 = dequant8(a.x, t0), a1 = dequant8(a.y, t0), a2 = dequant8(a.z, t1), a3 = dequant8(a.w, t1);
-    const f16x2 s0 = sf_pair_at(s16, 0), s1 = sf_pair_at(s16, 8);
-    const Frag8 b0 = dequant8(b.x, s0), b1 = dequant8(b.y, s0), b2 = dequant8(b.z, s1), b3 = dequant8(b.w, s1);
-    // weights are the MFMA A operand (rows = weight rows), activations the B operand (columns = tokens)
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0.v, a0.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b1.v, a1.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b2.v, a2.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b3.v, a3.v, acc, 0, 0, 0);
-  };
-  auto step = [&](RowblockRegs& r, RowblockActRegs& x) __attribute__((always_inline)) {
-    tile(r.b0, r.s, x.a0, x.s0);
-    tile(r.b1, r.s >> 16, x.a1, x.s1);
+  auto step = [&](WeightPair& r, RowblockActRegs& x) __attribute__((always_inline)) {
+    acc = tile_packed(r.b0, r.s, x.a0, x.s0, acc);
+    acc = tile_packed(r.b1, r.s >> 16, x.a1, x.s1, acc);
     issue(r, x);                                            // refill: three pairs ahead
     __builtin_amdgcn_sched_barrier(0);
     ++done;
@@ -351,11 +299,7 @@ __global__ __launch_bounds__(kRbThreads, 2) void gemm_rowblock_direct_kernel(Row
   }
   if constexpr (kSiluAbsmax) {                              // N % 4 == 0, bf16 out, no bias / residual (checked by the launcher)
     uint32_t m = 0;
-    if (active && rl < p.M && n0 < p.N) {
-      const uint32_t b0 = f32_to_bf16_bits(alpha * sum[0]), b1 = f32_to_bf16_bits(alpha * sum[1]);
-      const uint32_t b2 = f32_to_bf16_bits(alpha * sum[2]), b3 = f32_to_bf16_bits(alpha * sum[3]);
-      m = max(silu_mul_bf16(b0, b1) & 0x7fffu, silu_mul_bf16(b2, b3) & 0x7fffu);
-    }
+    if (active && rl < p.M && n0 < p.N) m = silu_absmax(alpha, sum);
 #pragma unroll
     for (int sh = 32; sh > 0; sh >>= 1) m = max(m, (uint32_t)__shfl_down((int)m, sh, 64));
     if (lane == 0 && active) p.silu_slots[rb] = m;
@@ -363,12 +307,11 @@ __global__ __launch_bounds__(kRbThreads, 2) void gemm_rowblock_direct_kernel(Row
 }
 
 // Repacked sizes: rows padded to 16, K to 256.
-static int64_t rowblock_pairs(int64_t K) { return (K + 255) / 256; }
-int64_t gemm_repacked_w_bytes(int64_t N, int64_t K) { return ((N + 15) / 16) * rowblock_pairs(K) * 2048; }
-int64_t gemm_repacked_sf_bytes(int64_t N, int64_t K) { return ((N + 15) / 16) * rowblock_pairs(K) * 256; }
+int64_t gemm_repacked_w_bytes(int64_t N, int64_t K) { return ((N + 15) / 16) * repacked_pairs(K) * 2048; }
+int64_t gemm_repacked_sf_bytes(int64_t N, int64_t K) { return ((N + 15) / 16) * repacked_pairs(K) * 256; }
 
 static int rowblock_lds_bytes(int M, int64_t K, int slices, int* a_stride) {
-  const int stride = (int)(rowblock_pairs(K) * 512 + 16);          // + 16: token rows start in different banks
+  const int stride = (int)(repacked_pairs(K) * 512 + 16);          // + 16: token rows start in different banks
   *a_stride = stride;
   const int red = slices > 1 ? kRbWaves * 64 * 4 * (int)sizeof(float) : 0;      // aliased onto the image
   return M * stride > red ? M * stride : red;
@@ -415,19 +358,17 @@ int gemm_repacked(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipS
   if (a.M > 16) return gemm_repacked_mid(a, RW, RSF, stream);
   if (use_stream) return gemm_repacked_stream(a, RW, RSF, stream);
   const bool silu = a.epilogue == kEpiSiluMul;              // here: D stays gate|up, absmax_slots gets max |silu(g) * u| per row block
-  if (silu && (!a.absmax_slots || (a.N % 4) || a.bias || a.residual || a.out_dtype != ARCQ_OUT_BF16))
-    return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4_repacked_silu_absmax: needs absmax_slots, N %% 4 == 0, bf16 output, no bias / residual");
+  if (const int err = repacked_silu_args_check(a)) return err;
   if (!gemm_repacked_supported(a.M, a.N, a.K))
     return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4_repacked: M=%d K=%d outside the repacked path (M <= 16, activation image <= 160 KB)", a.M, a.K);
   RowblockParams p;
   copy_gemm_fields(p, a);
   p.RW = RW; p.RSF = RSF;
   p.silu_slots = a.absmax_slots;
-  p.pairs = (int)rowblock_pairs(a.K);
+  p.pairs = (int)repacked_pairs(a.K);
   p.row_blocks = (a.N + 15) / 16;
   static const int forced = env_int("ARCQ_ROWBLOCK_SLICES", 0);   // tuning only
-  int s = rowblock_choose_slices(p.row_blocks, p.pairs);
-  if (forced == 1 || forced == 2 || forced == 4 || forced == 8) s = forced;
+  const int s = repacked_slices(p.row_blocks, p.pairs, forced);
   p.slices = s;
   const int lds = rowblock_lds_bytes(a.M, a.K, s, &p.a_stride);
   // the no-image kernel: ARCQ_ROWBLOCK_DIRECT=0/1 forces (A-B), default by shape (rowblock_use_direct)

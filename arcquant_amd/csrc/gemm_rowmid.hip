@@ -9,14 +9,14 @@
 // 2 q, 2 q + 1 of the tile -- and are dequantised per MFMA next to the weights (exact: gemm_common.hpp).  A weight unit
 // (16 rows x 256 K, 2 KB) is fetched once and contracted against ceil(M / 16) token tiles; the extra work per unit is
 // ceil(M / 16) x (2 LDS reads + 2 x 20 conversion instructions + 8 MFMA), which two 8-wave workgroups per CU still hide behind the
-// weight stream at M = 32.  Work split, register ring and slice reduction are those of gemm_rowblock.hip.
+// weight stream at M = 32.  Work split, register ring and slice reduction are those of gemm_rowblock.hip (written out here as there);
+// the tile pair, its loads, the dequantisation of a tile and its four MFMA are rowblock_core.hpp's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "arcq_internal.hpp"
-#include "gemm_common.hpp"
-#include "rowblock_split.hpp"
+#include "rowblock_core.hpp"
 
 namespace arcq {
 
@@ -38,12 +38,6 @@ struct RowmidParams {
   int a_stride;           // bytes per token row of the packed codes in LDS
   int s_stride;           // bytes per token row of the scale bytes in LDS
   int sf_off;             // LDS byte offset of the scale rows
-};
-
-typedef uint32_t rm_u32x4 __attribute__((ext_vector_type(4)));
-struct RowmidRegs {       // one tile pair of this lane: 2 x 16 bytes of codes, 4 scale bytes
-  rm_u32x4 b0, b1;
-  uint32_t s;
 };
 
 constexpr int kRmWaves = 8, kRmThreads = kRmWaves * 64;
@@ -78,11 +72,9 @@ __global__ __launch_bounds__(kRmThreads, kTok <= 2 ? ARCQ_ROWMID_WPS2 : 2) void 
   const uint8_t* sp = p.RSF + ((size_t)rbc * p.pairs + pr_load) * 256 + lane * 4;
   const int last = npairs > 0 ? npairs - 1 : 0;
   int issued = 0;
-  auto issue = [&](RowmidRegs& r) __attribute__((always_inline)) {       // unpredicated; the cursor stops at the last pair
+  auto issue = [&](WeightPair& r) __attribute__((always_inline)) {       // unpredicated; the cursor stops at the last pair
     const int i = min(issued, last);
-    r.b0 = ARCQ_WLOAD(reinterpret_cast<const rm_u32x4*>(wp + (size_t)i * 2048));
-    r.b1 = ARCQ_WLOAD(reinterpret_cast<const rm_u32x4*>(wp + (size_t)i * 2048 + 1024));
-    r.s = ARCQ_WLOAD(reinterpret_cast<const uint32_t*>(sp + (size_t)i * 256));
+    weight_pair_load(r, wp, sp, i);
     ++issued;
   };
 
@@ -107,7 +99,7 @@ __global__ __launch_bounds__(kRmThreads, kTok <= 2 ? ARCQ_ROWMID_WPS2 : 2) void 
       *reinterpret_cast<uint32_t*>(s_lds + (size_t)m * p.s_stride + (size_t)a * 4) = v;
     }
   }
-  RowmidRegs r0, r1, r2;
+  WeightPair r0, r1, r2;
   issue(r0);
   issue(r1);
   issue(r2);
@@ -126,23 +118,16 @@ __global__ __launch_bounds__(kRmThreads, kTok <= 2 ? ARCQ_ROWMID_WPS2 : 2) void 
     s_tok[t] = s_lds + (size_t)m * p.s_stride + (size_t)pr_begin * 16 + q * 2;
   }
   int done = 0;
-  auto tile = [&](rm_u32x4 b, uint32_t s16, int off_a, int off_s) __attribute__((always_inline)) {
-    const f16x2 s0 = sf_pair_at(s16, 0), s1 = sf_pair_at(s16, 8);
-    const Frag8 b0 = dequant8(b.x, s0), b1 = dequant8(b.y, s0), b2 = dequant8(b.z, s1), b3 = dequant8(b.w, s1);
+  auto tile = [&](rb_u32x4 b, uint32_t s16, int off_a, int off_s) __attribute__((always_inline)) {
+    const TileFrags w = tile_dequant(b, s16);
 #pragma unroll
     for (int t = 0; t < kTok; ++t) {
-      const uint4 ac = *reinterpret_cast<const uint4*>(a_tok[t] + off_a);
+      const rb_u32x4 ac = *reinterpret_cast<const rb_u32x4*>(a_tok[t] + off_a);
       const uint32_t as16 = *reinterpret_cast<const uint16_t*>(s_tok[t] + off_s);
-      const f16x2 t0 = sf_pair_at(as16, 0), t1 = sf_pair_at(as16, 8);
-      const Frag8 a0 = dequant8(ac.x, t0), a1 = dequant8(ac.y, t0), a2 = dequant8(ac.z, t1), a3 = dequant8(ac.w, t1);
-      // weights are the MFMA A operand (rows = weight rows), activations the B operand (columns = tokens)
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0.v, a0.v, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b1.v, a1.v, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b2.v, a2.v, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b3.v, a3.v, acc[t], 0, 0, 0);
+      acc[t] = tile_mfma(w, tile_dequant(ac, as16), acc[t]);
     }
   };
-  auto step = [&](RowmidRegs& r) __attribute__((always_inline)) {
+  auto step = [&](WeightPair& r) __attribute__((always_inline)) {
     tile(r.b0, r.s, done * 128, done * 16);
     tile(r.b1, r.s >> 16, done * 128 + 64, done * 16 + 8);
     issue(r);                                               // refill: three pairs ahead
@@ -215,11 +200,9 @@ __global__ __launch_bounds__(kRmThreads, kTok <= 2 ? 4 : 2) void gemm_rowtok_ker
   const uint8_t* sp = p.RSF + ((size_t)rbc * p.pairs + pr_load) * 256 + lane * 4;
   const int last = npairs > 0 ? npairs - 1 : 0;
   int issued = 0;
-  auto issue = [&](RowmidRegs& r) __attribute__((always_inline)) {
+  auto issue = [&](WeightPair& r) __attribute__((always_inline)) {
     const int i = min(issued, last);
-    r.b0 = ARCQ_WLOAD(reinterpret_cast<const rm_u32x4*>(wp + (size_t)i * 2048));
-    r.b1 = ARCQ_WLOAD(reinterpret_cast<const rm_u32x4*>(wp + (size_t)i * 2048 + 1024));
-    r.s = ARCQ_WLOAD(reinterpret_cast<const uint32_t*>(sp + (size_t)i * 256));
+    weight_pair_load(r, wp, sp, i);
     ++issued;
   };
   // activation rows of this lane (tokens >= M: the last row, never stored) and the clamps for tiles / atoms past K (they meet zero
@@ -241,7 +224,7 @@ __global__ __launch_bounds__(kRmThreads, kTok <= 2 ? 4 : 2) void gemm_rowtok_ker
   };
   auto s_off = [&](int t) __attribute__((always_inline)) -> size_t { return (size_t)min(2 * t + (q >> 1), atoms_k - 1) * 512; };
 
-  RowmidRegs r0, r1, r2;
+  WeightPair r0, r1, r2;
   issue(r0);
   issue(r1);
   issue(r2);
@@ -250,43 +233,27 @@ __global__ __launch_bounds__(kRmThreads, kTok <= 2 ? 4 : 2) void gemm_rowtok_ker
 #pragma unroll
   for (int t = 0; t < kTok; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   int done = 0;
-  auto step = [&](RowmidRegs& r) __attribute__((always_inline)) {
+  auto step = [&](WeightPair& r) __attribute__((always_inline)) {
     const int t0 = 2 * (pr_begin + done), t1 = t0 + 1;
     const size_t oa0 = a_off(t0), oa1 = a_off(t1), os0 = s_off(t0), os1 = s_off(t1);
-    rm_u32x4 xa0[kTok], xa1[kTok];
+    rb_u32x4 xa0[kTok], xa1[kTok];
     uint32_t xs0[kTok], xs1[kTok];
 #pragma unroll
     for (int t = 0; t < kTok; ++t) {                         // every activation load of the pair first ...
-      xa0[t] = *reinterpret_cast<const rm_u32x4*>(arow[t] + oa0);
-      xa1[t] = *reinterpret_cast<const rm_u32x4*>(arow[t] + oa1);
+      xa0[t] = *reinterpret_cast<const rb_u32x4*>(arow[t] + oa0);
+      xa1[t] = *reinterpret_cast<const rb_u32x4*>(arow[t] + oa1);
       xs0[t] = *reinterpret_cast<const uint16_t*>(srow[t] + os0);
       xs1[t] = *reinterpret_cast<const uint16_t*>(srow[t] + os1);
     }
     {                                                        // ... then the pair's two tiles against every token tile
-      const f16x2 s0 = sf_pair_at(r.s, 0), s1 = sf_pair_at(r.s, 8);
-      const Frag8 b0 = dequant8(r.b0.x, s0), b1 = dequant8(r.b0.y, s0), b2 = dequant8(r.b0.z, s1), b3 = dequant8(r.b0.w, s1);
+      const TileFrags w = tile_dequant(r.b0, r.s);
 #pragma unroll
-      for (int t = 0; t < kTok; ++t) {
-        const f16x2 u0 = sf_pair_at(xs0[t], 0), u1 = sf_pair_at(xs0[t], 8);
-        const Frag8 a0 = dequant8(xa0[t].x, u0), a1 = dequant8(xa0[t].y, u0), a2 = dequant8(xa0[t].z, u1), a3 = dequant8(xa0[t].w, u1);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0.v, a0.v, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b1.v, a1.v, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b2.v, a2.v, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b3.v, a3.v, acc[t], 0, 0, 0);
-      }
+      for (int t = 0; t < kTok; ++t) acc[t] = tile_mfma(w, tile_dequant(xa0[t], xs0[t]), acc[t]);
     }
     {
-      const f16x2 s0 = sf_pair_at(r.s >> 16, 0), s1 = sf_pair_at(r.s >> 16, 8);
-      const Frag8 b0 = dequant8(r.b1.x, s0), b1 = dequant8(r.b1.y, s0), b2 = dequant8(r.b1.z, s1), b3 = dequant8(r.b1.w, s1);
+      const TileFrags w = tile_dequant(r.b1, r.s >> 16);
 #pragma unroll
-      for (int t = 0; t < kTok; ++t) {
-        const f16x2 u0 = sf_pair_at(xs1[t], 0), u1 = sf_pair_at(xs1[t], 8);
-        const Frag8 a0 = dequant8(xa1[t].x, u0), a1 = dequant8(xa1[t].y, u0), a2 = dequant8(xa1[t].z, u1), a3 = dequant8(xa1[t].w, u1);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0.v, a0.v, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b1.v, a1.v, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b2.v, a2.v, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b3.v, a3.v, acc[t], 0, 0, 0);
-      }
+      for (int t = 0; t < kTok; ++t) acc[t] = tile_mfma(w, tile_dequant(xa1[t], xs1[t]), acc[t]);
     }
     issue(r);                                               // refill: three pairs ahead
     __builtin_amdgcn_sched_barrier(0);
@@ -328,10 +295,8 @@ __global__ __launch_bounds__(kRmThreads, kTok <= 2 ? 4 : 2) void gemm_rowtok_ker
   }
 }
 
-static int64_t rowmid_pairs(int64_t K) { return (K + 255) / 256; }
-
 static int rowmid_lds_bytes(int M, int64_t K, int slices, int tok, RowmidParams* p) {
-  const int pairs = (int)rowmid_pairs(K);
+  const int pairs = (int)repacked_pairs(K);
   const int a_stride = pairs * 128 + 16;                    // + 16: token rows start in different banks
   const int s_stride = pairs * 16 + 4;
   const int sf_off = (M * a_stride + 15) & ~15;
@@ -387,11 +352,10 @@ int gemm_repacked_mid(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, 
   RowmidParams p;
   copy_gemm_fields(p, a);
   p.RW = RW; p.RSF = RSF;
-  p.pairs = (int)rowmid_pairs(a.K);
+  p.pairs = (int)repacked_pairs(a.K);
   p.row_blocks = (a.N + 15) / 16;
   static const int forced = env_int("ARCQ_ROWMID_SLICES", 0);   // tuning only
-  int s = rowblock_choose_slices(p.row_blocks, p.pairs);
-  if (forced == 1 || forced == 2 || forced == 4 || forced == 8) s = forced;
+  int s = repacked_slices(p.row_blocks, p.pairs, forced);
   if (s > p.pairs) s = 1;
   p.slices = s;
   const int tok = (a.M + 15) / 16;

@@ -28,13 +28,15 @@
 //                    block: the down projection's kSrcDyn prologue then needs no abs-max pass and no SiLU
 //
 // Roofline: HBM.  Bytes per launch = N*K*9/16 (+ padding of K to 256) + activations + output.
+// The unit (tile pair) and its loads, the tile contraction and the kSrcPacked image writer are rowblock_core.hpp's, shared with
+// gemm_rowblock.hip and gemm_rowmid.hip.
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include "arcq_internal.hpp"
-#include "gemm_common.hpp"
+#include "rowblock_core.hpp"
 #include "quantize_device.hpp"
 #include "stream_split.hpp"
 
@@ -109,30 +111,11 @@ struct StreamParams {
 #endif
 };
 
-typedef uint32_t st_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t st_u32x2 __attribute__((ext_vector_type(2)));
-struct StreamRegs {           // one unit of this lane: 2 x 16 bytes of codes, 4 scale bytes
-  st_u32x4 b0, b1;
-  uint32_t s;
-};
-
 constexpr int kStThreads = kStreamWaves * 64;
 constexpr int kStSlotBytes = kStreamWaves * 2 * 64 * 16;     // partial tiles: [wave][segment][lane] float4
 constexpr int kStMiscBytes = 1024;                           // wave maxima, rstd per token, the dynamic scale
 
-// ---- prologue, kSrcPacked: unit = 32 codes (16 bytes + two scale bytes) -> 64 bytes of fp16 --------------------------------
-__device__ __forceinline__ void image_put_unit(unsigned char* a_img, const StreamParams& p, int u, int upr, int real, uint4 qv, uint32_t sf) {
-  const int m = u / upr, c = u - m * upr;
-  uint4 f0 = make_uint4(0, 0, 0, 0), f1 = f0, f2 = f0, f3 = f0;
-  if (c < real) {
-    sf >>= (c & 1) * 16;
-    const f16x2 s0 = sf_pair_at(sf, 0), s1 = sf_pair_at(sf, 8);
-    f0 = dequant8(qv.x, s0).u; f1 = dequant8(qv.y, s0).u; f2 = dequant8(qv.z, s1).u; f3 = dequant8(qv.w, s1).u;
-  }
-  uint4* dst = reinterpret_cast<uint4*>(a_img + (size_t)m * p.a_stride + c * 64);
-  dst[0] = f0; dst[1] = f1; dst[2] = f2; dst[3] = f3;
-}
-
+// ---- prologue: kSrcPacked fills the image unit by unit (image_put_unit, rowblock_core.hpp); the fused sources group by group:
 // one quantised group -> its 16 exact fp16 values at group position `pos` of token row m
 __device__ __forceinline__ void image_put_group(unsigned char* a_img, const StreamParams& p, int m, int pos, const GroupQ& g) {
   const f16x2 s2 = sf_pair(g.s8);
@@ -152,7 +135,7 @@ constexpr int kTask = 6;
 
 // ---- prologue loads hipcc must not wait for conservatively: issued by asm, retired by asm_wait_loads<N>() + asm_tie() -----------
 __device__ __forceinline__ uint4 asm_load_b128(const void* ptr) {
-  st_u32x4 v;
+  rb_u32x4 v;
   asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(ptr) : "memory");
   return make_uint4(v.x, v.y, v.z, v.w);
 }
@@ -312,15 +295,10 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
   // ---- the first task of the weight stream
   const uint8_t* const wp = p.RW + ((size_t)rb0 * P + u0) * 2048 + lane * 16;
   const uint8_t* const sp = p.RSF + ((size_t)rb0 * P + u0) * 256 + lane * 4;
-  auto load_unit = [&](StreamRegs& r, int i) __attribute__((always_inline)) {       // unit i of this wave's range
-    // a weight byte is read once per launch by one CU: non-temporal loads (gemm_common.hpp)
-    r.b0 = ARCQ_WLOAD(reinterpret_cast<const st_u32x4*>(wp + (size_t)i * 2048));
-    r.b1 = ARCQ_WLOAD(reinterpret_cast<const st_u32x4*>(wp + (size_t)i * 2048 + 1024));
-    r.s = ARCQ_WLOAD(reinterpret_cast<const uint32_t*>(sp + (size_t)i * 256));
-  };
+  auto load_unit = [&](WeightPair& r, int i) __attribute__((always_inline)) { weight_pair_load(r, wp, sp, i); };   // unit i of this wave's range
   // bias / residual of the (<= 2) row blocks this wave owns, fetched behind its LAST task's loads: they arrive with the last
   // weights instead of costing a global round trip after the final barrier (plain epilogue, N % 4 == 0: 8-byte loads)
-  st_u32x2 ep_bias0 = {0, 0}, ep_bias1 = {0, 0}, ep_res0 = {0, 0}, ep_res1 = {0, 0};   // by name: a runtime-indexed array lands in scratch
+  rb_u32x2 ep_bias0 = {0, 0}, ep_bias1 = {0, 0}, ep_res0 = {0, 0}, ep_res1 = {0, 0};   // by name: a runtime-indexed array lands in scratch
   const bool ep_pre = (kOut == kOutPlain || kOut == kOutSiluAct) && (p.N & 3) == 0 && (p.bias || p.residual);
   auto prefetch_epilogue = [&]() __attribute__((always_inline)) {
     if (!ep_pre) return;
@@ -330,15 +308,15 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
       if (seg_n <= 0 || (seg == 0 && pa0 != 0)) continue;    // as in the epilogue: not this wave's row block
       const int n0 = (rb0 + rbl0 + seg) * 16 + 4 * q;
       if (rl < p.M && n0 < p.N) {
-        if (p.bias) (seg == 0 ? ep_bias0 : ep_bias1) = *reinterpret_cast<const st_u32x2*>(p.bias + n0);
-        if (p.residual) (seg == 0 ? ep_res0 : ep_res1) = *reinterpret_cast<const st_u32x2*>(p.residual + (size_t)rl * p.N + n0);
+        if (p.bias) (seg == 0 ? ep_bias0 : ep_bias1) = *reinterpret_cast<const rb_u32x2*>(p.bias + n0);
+        if (p.residual) (seg == 0 ? ep_res0 : ep_res1) = *reinterpret_cast<const rb_u32x2*>(p.residual + (size_t)rl * p.N + n0);
       }
     }
   };
   const int ntasks = (n + kTask - 1) / kTask;
   int task_left = ntasks, done = 0;
   int c = ntasks > 0 ? (n + ntasks - 1) / ntasks : 0;       // units of the current task (wave-uniform)
-  StreamRegs r0 = {}, r1 = {}, r2 = {}, r3 = {}, r4 = {}, r5 = {};
+  WeightPair r0 = {}, r1 = {}, r2 = {}, r3 = {}, r4 = {}, r5 = {};
   auto load_task_part = [&](int lo, int hi) __attribute__((always_inline)) {      // units [lo, hi) of the current task
     if (c > 0 && lo <= 0 && 0 < hi) load_unit(r0, done);
     if (c > 1 && lo <= 1 && 1 < hi) load_unit(r1, done + 1);
@@ -373,11 +351,11 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
 #pragma unroll
     for (int j = 0; j < kPre; ++j) {
       const int u = tid + j * kStThreads;
-      if (u < units) image_put_unit(a_img, p, u, upr, real, pre_q[j], pre_s[j]);
+      if (u < units) image_put_unit(a_img, p.a_stride, u, upr, real, pre_q[j], pre_s[j]);
     }
     for (int u = tid + kPre * kStThreads; u < units; u += kStThreads) {       // beyond the prefetch (M * K > 64 K elements)
       const int m = u / upr, cc = min(u - m * upr, real - 1);
-      image_put_unit(a_img, p, u, upr, real, *reinterpret_cast<const uint4*>(p.A + (size_t)m * (p.K >> 1) + cc * 16),
+      image_put_unit(a_img, p.a_stride, u, upr, real, *reinterpret_cast<const uint4*>(p.A + (size_t)m * (p.K >> 1) + cc * 16),
                      *reinterpret_cast<const uint32_t*>(p.SFA + sf_atom_offset(m, cc >> 1, atoms_k)));
     }
   } else {
@@ -462,17 +440,17 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
     // `p.stage` and the divider's fast path are uniform over the launch: the task loop is instantiated per combination (as
     // branches inside the 16-element gather they cost a scalar branch and a FULL wait per element -- sixteen serialised LDS
     // round trips per group)
-    const st_u32x4 pi0 = {pre_i0.x, pre_i0.y, pre_i0.z, pre_i0.w}, pi1 = {pre_i1.x, pre_i1.y, pre_i1.z, pre_i1.w};
+    const rb_u32x4 pi0 = {pre_i0.x, pre_i0.y, pre_i0.z, pre_i0.w}, pi1 = {pre_i1.x, pre_i1.y, pre_i1.z, pre_i1.w};
     auto run_groups = [&](auto stage_tag, auto fast_tag) __attribute__((always_inline)) {
     constexpr bool kStage = decltype(stage_tag)::value, kFast = decltype(fast_tag)::value;
     for (int t = tid; t < ntask_q; t += kStThreads) {
       int m = first_m, g = first_g;
       bool twin = first_twin;                                // the residual twin of (m, g): uniform over a wave except at one boundary
-      st_u32x4 i0 = pi0, i1 = pi1;                           // (native vectors: a HIP uint4 captured by the lambda lands in scratch)
+      rb_u32x4 i0 = pi0, i1 = pi1;                           // (native vectors: a HIP uint4 captured by the lambda lands in scratch)
       if (t != tid) {                                        // later tasks of this thread (M * KQ > 16 K elements)
         twin = qtask(t, m, g);
-        i0 = *reinterpret_cast<const st_u32x4*>(p.idx + (size_t)g * 16);
-        i1 = *reinterpret_cast<const st_u32x4*>(p.idx + (size_t)g * 16 + 8);
+        i0 = *reinterpret_cast<const rb_u32x4*>(p.idx + (size_t)g * 16);
+        i1 = *reinterpret_cast<const rb_u32x4*>(p.idx + (size_t)g * 16 + 8);
       }
       const uint32_t iw[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
       const uint16_t* xrow_lds = reinterpret_cast<const uint16_t*>(xstage + (size_t)m * p.xrow_bytes);
@@ -544,21 +522,9 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
   f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
   const unsigned char* const a_tok = a_img + (size_t)min(rl, p.M - 1) * p.a_stride + q * 64;   // tokens >= M: any row (never stored)
   int pr = pa0;
-  auto tile = [&](st_u32x4 b, uint32_t s16, const unsigned char* ap) __attribute__((always_inline)) {
-    Frag8 a0, a1, a2, a3;
-    a0.u = *reinterpret_cast<const uint4*>(ap);
-    a1.u = *reinterpret_cast<const uint4*>(ap + 16);
-    a2.u = *reinterpret_cast<const uint4*>(ap + 32);
-    a3.u = *reinterpret_cast<const uint4*>(ap + 48);
-    const f16x2 s0 = sf_pair_at(s16, 0), s1 = sf_pair_at(s16, 8);
-    const Frag8 b0 = dequant8(b.x, s0), b1 = dequant8(b.y, s0), b2 = dequant8(b.z, s1), b3 = dequant8(b.w, s1);
-    // weights are the MFMA A operand (rows = weight rows), activations the B operand (columns = tokens)
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b0.v, a0.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b1.v, a1.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b2.v, a2.v, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b3.v, a3.v, acc, 0, 0, 0);
-  };
-  auto step = [&](const StreamRegs& r) __attribute__((always_inline)) {
+  // (a lambda of its own around the shared tile: called straight from `step`, hipcc numbers this kernel's registers differently)
+  auto tile = [&](rb_u32x4 b, uint32_t s16, const unsigned char* ap) __attribute__((always_inline)) { acc = tile_image(b, s16, ap, acc); };
+  auto step = [&](const WeightPair& r) __attribute__((always_inline)) {
     const unsigned char* ap = a_tok + (size_t)pr * 512;
     tile(r.b0, r.s, ap);
     tile(r.b1, r.s >> 16, ap + 256);
@@ -622,7 +588,7 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
       uint32_t mx = 0;
       if (live) {
         uint32_t y[4];                                      // bf16 (gate, up, gate, up) as the separate GEMM (+ bias) would leave them
-        const st_u32x2 eb = seg == 0 ? ep_bias0 : ep_bias1;   // this tile's four bias values, prefetched (N % 4 == 0 here)
+        const rb_u32x2 eb = seg == 0 ? ep_bias0 : ep_bias1;   // this tile's four bias values, prefetched (N % 4 == 0 here)
         const uint32_t bw[2] = {eb.x, eb.y};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -646,18 +612,14 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
     } else {
       if (live) {
         if (ep_pre) {
-          const st_u32x2 eb = seg == 0 ? ep_bias0 : ep_bias1, er = seg == 0 ? ep_res0 : ep_res1;
+          const rb_u32x2 eb = seg == 0 ? ep_bias0 : ep_bias1, er = seg == 0 ? ep_res0 : ep_res1;
           finish4_pre<uint32_t>(p, alpha, rl, n0, sv, make_uint2(eb.x, eb.y), make_uint2(er.x, er.y));
         }
         else finish4<uint32_t>(p, alpha, rl, n0, sv);
       }
       if constexpr (kOut == kOutSiluAbsmax) {               // N % 4 == 0, bf16 out, no bias / residual (checked by the launcher)
         uint32_t mx = 0;
-        if (live) {
-          const uint32_t b0 = f32_to_bf16_bits(alpha * sv[0]), b1 = f32_to_bf16_bits(alpha * sv[1]);
-          const uint32_t b2 = f32_to_bf16_bits(alpha * sv[2]), b3 = f32_to_bf16_bits(alpha * sv[3]);
-          mx = max(silu_mul_bf16(b0, b1) & 0x7fffu, silu_mul_bf16(b2, b3) & 0x7fffu);
-        }
+        if (live) mx = silu_absmax(alpha, sv);
         mx = wave_max_u32(mx);
         if (lane == 0) p.out_slots[rb] = mx;
       }
@@ -668,8 +630,6 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-static int64_t stream_pairs(int64_t K) { return (K + 255) / 256; }
-
 struct StreamGeom {
   int pairs, row_blocks, grid, a_stride, img_bytes, stage, xrow_bytes, slot_off, stage_off, misc_off, lds;
 };
@@ -678,7 +638,7 @@ struct StreamGeom {
 static int stream_geometry(int src, int64_t M, int64_t N, int64_t K, int64_t KQ, StreamGeom* g) {
   if (M < 1 || M > 16 || N < 1 || K < 64 || (K % 64)) return 0;
   const int64_t cap = 160 * 1024;
-  g->pairs = (int)stream_pairs(K);
+  g->pairs = (int)repacked_pairs(K);
   g->row_blocks = (int)((N + 15) / 16);
   g->grid = stream_grid(g->row_blocks);
   g->a_stride = g->pairs * 512 + 16;                        // + 16: token rows start in different banks
@@ -741,8 +701,7 @@ static void fill_common(StreamParams& p, const StreamGeom& g, const GemmArgs& a,
 // workgroups per CU with a three-deep ring, measured faster on every plain shape and stays the default there)
 int gemm_repacked_stream(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipStream_t stream) {
   const bool silu = a.epilogue == kEpiSiluMul;              // here: D stays gate|up, absmax_slots gets max |silu(g) * u| per row block
-  if (silu && (!a.absmax_slots || (a.N % 4) || a.bias || a.residual || a.out_dtype != ARCQ_OUT_BF16))
-    return fail(ARCQ_ERR_SHAPE, "arcq_gemm_nvfp4_repacked_silu_absmax: needs absmax_slots, N %% 4 == 0, bf16 output, no bias / residual");
+  if (const int err = repacked_silu_args_check(a)) return err;
   StreamGeom g;
   if (!stream_geometry(kSrcPacked, a.M, a.N, a.K, 0, &g))
     return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4_repacked: M=%d K=%d outside the repacked path (M <= 16, activation image <= 160 KB)", a.M, a.K);

@@ -22,6 +22,15 @@ inline int rowblock_choose_slices(int64_t row_blocks, int pairs) {
   return s;
 }
 
+// tile pairs per row block of the repacked weight: K padded to 256
+inline int64_t repacked_pairs(int64_t K) { return (K + 255) / 256; }
+
+// the slices of a launch: what a tuning knob forces (1, 2, 4 or 8; any other value forces nothing), else the choice above
+inline int repacked_slices(int64_t row_blocks, int pairs, int forced) {
+  if (forced == 1 || forced == 2 || forced == 4 || forced == 8) return forced;
+  return rowblock_choose_slices(row_blocks, pairs);
+}
+
 // balanced: the first (pairs % slices) slices own one pair more
 ARCQ_HD inline void rowblock_slice_range(int pairs, int slices, int slice, int* begin, int* count) {
   const int base = pairs / slices, extra = pairs - base * slices;
