@@ -63,6 +63,49 @@ struct GemmRule {
 int gemm_checks(const GemmRule& r, const void* A, const void* B, const void* SFA, const void* SFB, const void* D, const void* absmax_slots, int64_t M,
                 int64_t N, int64_t K, const void* bias, const void* residual, int out_dtype);
 
+// c_api.hip: the argument checks of a quantiser entry point (host only), parameterised by what differs between entry points.
+// `family` selects the pinned texts, the output alignments and where the KQ range is reported:
+//   kQuantNv       NVFP4 rows: variant checked; KQ > 32767 and a KQ outside [kq_min, kq_max] are ARCQ_ERR_UNSUPPORTED, after the variant;
+//                  X / reorder_index 16-byte, then QX 8-byte and SFX 4-byte, in two messages
+//   kQuantNvContig arcq_quantize_x_dyn_slots with reorder_index == NULL: no index; the KQ range is part of the shape fault
+//   kQuantMx       MXFP4 rows: no variant; the range is part of the shape fault; X, reorder_index, QX 16-byte, SFX unaligned
+//   kQuantMxFused  MXFP4 fused sources: as kQuantMx, the range spelled out in the text, `extra` among the 16-byte inputs
+enum : int { kQuantNv = 0, kQuantNvContig = 1, kQuantMx = 2, kQuantMxFused = 3 };
+enum : int { kQuantStatic = 0, kQuantState = 1, kQuantSlots = 2 };
+struct QuantRule {
+  const char* who;
+  int family = kQuantNv;
+  int64_t kq_min = 64, kq_max = 32767;  // (kQuantNv: the RMSNorm range when narrower)
+  bool extra = false;                   // takes a further 16-byte input, the norm weight
+  int dyn = kQuantStatic;               // kQuantState: scale_out and state required; kQuantSlots: scale_out, absmax_slots and 0 < nslots <= INT32_MAX
+  bool layout = false;                  // takes a gate|up layout
+  const char* x_alone = nullptr;        // the three dynamic entries that once validated through a rows = 0 call of the static one, pinned:
+                                        // the shape fault says rows=0, M < 0 is empty, and X (under this name) is reported alone ahead of
+                                        // the row limit
+};
+struct QuantArgs {
+  const void *X, *extra, *idx, *Q, *SF;
+  int64_t rows, KQ, KE;
+  int variant = ARCQ_VARIANT_G16, layout = ARCQ_GU_HALVES;
+  const void *scale_out = nullptr, *dyn = nullptr;   // dyn: state or absmax_slots
+  int64_t nslots = 0;
+};
+// In the order every entry point reports them: layout, scale_out / state / slots, (kQuantNv) misaligned norm weight, shape, variant,
+// KQ limits, empty input (returns 1: nothing to do), NULL, x_alone, row limit, alignment.  Returns ARCQ_OK to go on or the recorded
+// failure; no HIP call.
+int quant_checks(const QuantRule& r, const QuantArgs& a);
+
+// The grid of every row quantiser: grid.x = one workgroup per row (grid-strided beyond kMaxQuantBlocks = 256 CUs x 8 resident workgroups);
+// few rows (decode): each row is also split over up to 16 workgroups (grid.y) of >= 32 units -- 16-element groups or 32-element blocks --
+// so that the chip is not idle
+constexpr int kMaxQuantBlocks = 2048;
+inline dim3 quant_grid(int64_t rows, int64_t units) {
+  const int g = (int)(rows < kMaxQuantBlocks ? rows : kMaxQuantBlocks);
+  int s = 1;
+  while (g * s < 256 && s < 16 && units / (s * 2) >= 32) s *= 2;
+  return dim3(g, s);
+}
+
 // quantize.hip
 int quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, int variant,
                hipStream_t stream);

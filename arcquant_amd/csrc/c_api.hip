@@ -8,6 +8,7 @@
 
 #include "arcq_device.hpp"
 #include "arcq_internal.hpp"
+#include "quantize_device.hpp"
 
 namespace arcq {
 
@@ -68,6 +69,45 @@ int gemm_checks(const GemmRule& r, const void* A, const void* B, const void* SFA
   return check_epi_align(r.who, bias, residual, r.epi_align);
 }
 
+int quant_checks(const QuantRule& r, const QuantArgs& a) {
+  const bool nv = r.family == kQuantNv, mx = r.family == kQuantMx || r.family == kQuantMxFused;
+  if (r.layout && a.layout != ARCQ_GU_HALVES && a.layout != ARCQ_GU_PAIRS) return fail(ARCQ_ERR_SHAPE, "%s: unknown layout %d", r.who, a.layout);
+  // pinned quirks: the dynamic entries report scale_out / state / slots ahead of the shape, and arcq_rmsnorm_quantize_x a misaligned norm weight
+  if (r.dyn == kQuantState && (!a.scale_out || !a.dyn)) return fail(ARCQ_ERR_NULL, "%s: NULL scale_out / state", r.who);
+  if (r.dyn == kQuantSlots && (!a.scale_out || !a.dyn || a.nslots <= 0 || a.nslots > INT32_MAX))
+    return fail(ARCQ_ERR_NULL, "%s: NULL scale_out / absmax_slots, or no slots", r.who);
+  if (nv && r.extra && a.rows > 0 && (bits(a.extra) & 15)) return fail(ARCQ_ERR_SHAPE, "%s: the norm weight must be 16-byte aligned", r.who);
+  // KQ and KE in whole scale-factor atoms (64 elements = 4 groups): every size the reference dispatches (bindings.cpp:141-160), every
+  // select_num it produces (multiples of 64) and every 64-aligned TP shard.  The kernels rely on it: the four lanes of a quad store the
+  // four scale bytes of one aligned dword of the swizzled layout.
+  const int64_t rows = r.x_alone && a.rows < 0 ? 0 : a.rows, rows_said = r.x_alone ? 0 : rows;
+  if (rows < 0 || a.KQ <= 0 || (a.KQ % 64) || (a.KE % 64) || a.KE < 0 || a.KE > a.KQ || (!nv && (a.KQ < r.kq_min || a.KQ > r.kq_max))) {
+    char range[48] = "";
+    if (r.family == kQuantMxFused) snprintf(range, sizeof(range), ", %lld<=KQ<=%lld", (long long)r.kq_min, (long long)r.kq_max);
+    else if (!nv) snprintf(range, sizeof(range), "<=%lld", (long long)r.kq_max);
+    return fail(ARCQ_ERR_SHAPE, "%s: need KQ%%64==0, KE%%64==0, 0<=KE<=KQ%s (%s=%lld KQ=%lld KE=%lld)", r.who, range,
+                r.family == kQuantNvContig ? "M" : "rows", (long long)rows_said, (long long)a.KQ, (long long)a.KE);
+  }
+  if (!mx && a.variant != ARCQ_VARIANT_G16 && a.variant != ARCQ_VARIANT_G32) return fail(ARCQ_ERR_SHAPE, "%s: unknown variant %d", r.who, a.variant);
+  if (nv && a.KQ > 32767)   // int16 reorder_index (bindings.cpp:137)
+    return fail(ARCQ_ERR_UNSUPPORTED, "%s: KQ=%lld does not fit an int16 reorder_index", r.who, (long long)a.KQ);
+  if (nv && (a.KQ < r.kq_min || a.KQ > r.kq_max))   // the reduction tree of rmsnorm.cu:130-146 is defined for 128..512 threads
+    return fail(ARCQ_ERR_UNSUPPORTED, "%s: KQ=%lld outside the reference's RMSNorm range [%lld, %lld]", r.who, (long long)a.KQ, (long long)r.kq_min,
+                (long long)r.kq_max);
+  if (rows == 0) return 1;                                     // nothing to do
+  if (!a.X || (r.family != kQuantNvContig && !a.idx) || !a.Q || !a.SF || (r.extra && !a.extra)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", r.who);
+  if (r.x_alone && (bits(a.X) & 15)) return fail(ARCQ_ERR_SHAPE, "%s: %s must be 16-byte aligned", r.who, r.x_alone);
+  if (rows > INT32_MAX) return fail(ARCQ_ERR_UNSUPPORTED, "%s: too many rows", r.who);
+  // 16-byte row / index loads; NVFP4: 8-byte code stores, 4-byte scale stores; MXFP4: 16-byte code stores (Kp/2 is a multiple of 64), scale bytes
+  const bool in_bad = (bits(a.X) | bits(a.idx) | bits(a.extra)) & 15, out_bad = mx ? (bits(a.Q) & 15) != 0 : (bits(a.Q) & 7) || (bits(a.SF) & 3);
+  static const char* const kAlignText[] = {"%s: X and reorder_index must be 16-byte aligned", "%s: X must be 16-byte, QX 8-byte and SFX 4-byte aligned",
+                                           "%s: X, reorder_index and the packed output must be 16-byte aligned",
+                                           "%s: the inputs, reorder_index and the packed output must be 16-byte aligned"};
+  if (in_bad || (!nv && out_bad)) return fail(ARCQ_ERR_SHAPE, kAlignText[r.family], r.who);
+  if (out_bad) return fail(ARCQ_ERR_SHAPE, "%s: the packed output must be 8-byte and the scale buffer 4-byte aligned", r.who);
+  return ARCQ_OK;
+}
+
 static GemmArgs gemm_args(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t K, float alpha_host,
                           const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* workspace, int64_t workspace_bytes) {
   GemmArgs a;
@@ -99,15 +139,12 @@ int64_t arcq_sf_used_bytes(int64_t rows, int64_t K) { return ((rows + 127) / 128
 int64_t arcq_sf_offset(int64_t row, int64_t pos, int64_t K) { return sf_offset(row, pos, K); }
 
 int64_t arcq_primary_pos(int64_t g, int64_t KQ, int64_t KE, int variant) {
-  const int64_t P = (KQ - KE) / 16;
-  if (variant == ARCQ_VARIANT_G16) return g + (g > P ? g - P : 0);
-  const int64_t g1 = g & ~(int64_t)1;
-  return g1 + (g1 > P ? g1 - P : 0) + (g & 1);
+  const int64_t P = (KQ - KE) / 16;                          // the kernels' rule (quantize_device.hpp)
+  return variant == ARCQ_VARIANT_G16 ? aug_group_pos<ARCQ_VARIANT_G16>(g, P) : aug_group_pos<ARCQ_VARIANT_G32>(g, P);
 }
 int64_t arcq_residual_pos(int64_t g, int64_t KQ, int64_t KE, int variant) {
-  const int64_t P = (KQ - KE) / 16;
-  if (g < P) return -1;
-  return arcq_primary_pos(g, KQ, KE, variant) + (variant == ARCQ_VARIANT_G16 ? 1 : 2);
+  if (g < (KQ - KE) / 16) return -1;
+  return arcq_primary_pos(g, KQ, KE, variant) + (variant == ARCQ_VARIANT_G16 ? aug_twin_step<ARCQ_VARIANT_G16> : aug_twin_step<ARCQ_VARIANT_G32>);
 }
 
 int arcq_quantize_x(const void* X, const int16_t* reorder_index, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE,

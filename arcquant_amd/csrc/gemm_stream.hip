@@ -480,18 +480,12 @@ __global__ __launch_bounds__(kStThreads) void gemm_stream_kernel(StreamParams p)
         v[2 * j] = a;
         v[2 * j + 1] = b;
       }
-      int pos;                                                 // augmented-K position (reorder.cu:139 / :451-452)
-      if (kVariant == ARCQ_VARIANT_G16) {
-        pos = g + (g > Ptail ? g - Ptail : 0);
-      } else {
-        const int g1 = g & ~1;
-        pos = g1 + (g1 > Ptail ? g1 - Ptail : 0) + (g & 1);
-      }
+      const int pos = aug_group_pos<kVariant>(g, Ptail);       // augmented-K position (quantize_device.hpp)
       if (!twin) {                                             // the primary's codes do not depend on kResid (quantize_group)
         image_put_group(a_img, p, m, pos, quantize_group<false, kVariant>(v));
       } else {                                                 // residual channels: reorder.cu:166-198, 499-550
         quantize_group<true, kVariant>(v);                     // v <- bf16(v - q * S)
-        image_put_group(a_img, p, m, pos + (kVariant == ARCQ_VARIANT_G16 ? 1 : 2), quantize_group<false, kVariant>(v));
+        image_put_group(a_img, p, m, pos + aug_twin_step<kVariant>, quantize_group<false, kVariant>(v));
       }
     }
     };

@@ -145,15 +145,7 @@ __global__ __launch_bounds__(kQuantThreads) void quantize_rows_kernel(
     // one group: 16 gathered values -> codes + scale byte(s) at the group's augmented-K position
     auto finish = [&](int g, float (&v)[16]) __attribute__((always_inline)) {
       const bool tail = g >= P;
-      // augmented-K position of this group (reorder.cu:139 / :451-452)
-      int p;
-      if (kVariant == ARCQ_VARIANT_G16) {
-        p = g + (g > P ? g - P : 0);
-      } else {
-        const int g1 = g & ~1;
-        p = g1 + (g1 > P ? g1 - P : 0) + (g & 1);
-      }
-      const int pr = p + (kVariant == ARCQ_VARIANT_G16 ? 1 : 2);
+      const int p = aug_group_pos<kVariant>(g, P), pr = p + aug_twin_step<kVariant>;
 
       if (kMode == kModeW) {
         GroupQ q = quantize_group<false, kVariant>(v);
@@ -286,14 +278,7 @@ __global__ __launch_bounds__(kQuantThreads) void quantize_contig_dyn_kernel(cons
       v[2 * j + 1] = round_to_bf16(dyn_div.template div<kFast>(bf16_bits_to_f32(w[j] >> 16)));
     }
     const bool tail = g >= P;
-    int p;
-    if (kVariant == ARCQ_VARIANT_G16) {
-      p = g + (g > P ? g - P : 0);
-    } else {
-      const int g1 = g & ~1;
-      p = g1 + (g1 > P ? g1 - P : 0) + (g & 1);
-    }
-    const int pr = p + (kVariant == ARCQ_VARIANT_G16 ? 1 : 2);
+    const int p = aug_group_pos<kVariant>(g, P), pr = p + aug_twin_step<kVariant>;
     uint8_t* qrow = Q + (size_t)row * (K >> 1);
     if (!tail) {
       GroupQ q = quantize_group<false, kVariant>(v);
@@ -375,70 +360,48 @@ __global__ void absmax_finish_kernel(unsigned int* slot, float* scale_out) {
 // ----------------------------------------------------------------------------------------------------
 // launchers
 // ----------------------------------------------------------------------------------------------------
-constexpr int kMaxQuantBlocks = 2048;   // 256 CUs x 8 resident workgroups, rows are grid-strided beyond
-
-// grid.x = one workgroup per row (grid-strided beyond kMaxQuantBlocks); few rows (decode): each row is also split
-// over up to 16 workgroups of >= 32 groups so that the chip is not idle
-static void quant_grid(int64_t rows, int64_t KQ, int* grid, int* gsplit) {
-  const int g = (int)(rows < kMaxQuantBlocks ? rows : kMaxQuantBlocks);
-  int s = 1;
-  while (g * s < 256 && s < 16 && (KQ / 16) / (s * 2) >= 32) s *= 2;
-  *grid = g;
-  *gsplit = s;
+// the kernel instantiation of a run-time variant: launch(std::integral_constant<int, variant>)
+template <typename F>
+static int by_variant(int variant, F&& launch) {
+  if (variant == ARCQ_VARIANT_G16) return launch(std::integral_constant<int, ARCQ_VARIANT_G16>{});
+  return launch(std::integral_constant<int, ARCQ_VARIANT_G32>{});
 }
 
+// (arguments already checked: quant_checks)
 template <int kMode, int kDyn = kDynNone, int kSilu = kSiluNone>
 static int launch_quantize(const void* X, const void* Wn, float eps, const int16_t* idx, uint8_t* Q, uint8_t* SF,
                            int64_t rows, int64_t KQ, int64_t KE, int variant, hipStream_t stream, const char* who,
                            const unsigned int* dyn = nullptr, int nslots = 0, float* scale_out = nullptr, const void* Xup = nullptr,
                            int64_t ldx = 0) {
-  // KQ and KE in whole scale-factor atoms (64 elements = 4 groups): every size the reference dispatches (bindings.cpp:141-160),
-  // every select_num it produces (multiples of 64) and every 64-aligned TP shard.  The kernel relies on it: the four
-  // lanes of a quad store the four scale bytes of one aligned dword of the swizzled layout.
-  if (rows < 0 || KQ <= 0 || (KQ % 64) || (KE % 64) || KE < 0 || KE > KQ)
-    return fail(ARCQ_ERR_SHAPE, "%s: need KQ%%64==0, KE%%64==0, 0<=KE<=KQ (rows=%lld KQ=%lld KE=%lld)", who,
-                (long long)rows, (long long)KQ, (long long)KE);
-  if (variant != ARCQ_VARIANT_G16 && variant != ARCQ_VARIANT_G32)
-    return fail(ARCQ_ERR_SHAPE, "%s: unknown variant %d", who, variant);
-  if (KQ > 32767)   // int16 reorder_index (bindings.cpp:137)
-    return fail(ARCQ_ERR_UNSUPPORTED, "%s: KQ=%lld does not fit an int16 reorder_index", who, (long long)KQ);
-  if (kMode == kModeRms && (KQ < 2048 || KQ > 8192))   // reduction tree of rmsnorm.cu:130-146 is defined for 128..512 threads
-    return fail(ARCQ_ERR_UNSUPPORTED, "%s: KQ=%lld outside the reference's RMSNorm range [2048, 8192]", who, (long long)KQ);
-  if (rows == 0) return ARCQ_OK;
-  if (!X || !idx || !Q || !SF || (kMode == kModeRms && !Wn)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (rows > INT32_MAX) return fail(ARCQ_ERR_UNSUPPORTED, "%s: too many rows", who);
-  // 16-byte row / index loads, 8-byte code stores, 4-byte scale stores
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(Xup)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: X and reorder_index must be 16-byte aligned", who);
-  if ((reinterpret_cast<uintptr_t>(Q) & 7) || (reinterpret_cast<uintptr_t>(SF) & 3))
-    return fail(ARCQ_ERR_SHAPE, "%s: the packed output must be 8-byte and the scale buffer 4-byte aligned", who);
-
-  size_t lds = lds_row_bytes((size_t)KQ) + (kMode == kModeRms ? 512 * sizeof(float) + lds_row_bytes((size_t)KQ) : 0);
-  int grid, gsplit;
-  quant_grid(rows, KQ, &grid, &gsplit);
-  const dim3 g2(grid, gsplit), block(kQuantThreads);
+  const size_t lds = lds_row_bytes((size_t)KQ) + (kMode == kModeRms ? 512 * sizeof(float) + lds_row_bytes((size_t)KQ) : 0);
+  const dim3 grid = quant_grid(rows, KQ / 16), block(kQuantThreads);
   const uint16_t *x = (const uint16_t*)X, *xup = (const uint16_t*)Xup, *wn = (const uint16_t*)Wn;
   const int64_t ld = ldx ? ldx : KQ;
-  if (variant == ARCQ_VARIANT_G16)
-    return launch_kernel<quantize_rows_kernel<ARCQ_VARIANT_G16, kMode, kDyn, kSilu>>(g2, block, (int)lds, stream, who, x, xup, ld, wn, eps, idx, Q, SF, (int)rows, (int)KQ,
-                                                                                      (int)KE, dyn, nslots, scale_out);
-  return launch_kernel<quantize_rows_kernel<ARCQ_VARIANT_G32, kMode, kDyn, kSilu>>(g2, block, (int)lds, stream, who, x, xup, ld, wn, eps, idx, Q, SF, (int)rows, (int)KQ,
-                                                                                    (int)KE, dyn, nslots, scale_out);
+  return by_variant(variant, [&](auto v) {
+    return launch_kernel<quantize_rows_kernel<decltype(v)::value, kMode, kDyn, kSilu>>(grid, block, (int)lds, stream, who, x, xup, ld, wn, eps, idx, Q, SF, (int)rows,
+                                                                                       (int)KQ, (int)KE, dyn, nslots, scale_out);
+  });
 }
 
+template <int kMode>
+static int quantize_static(const char* who, const void* X, const void* Wn, float eps, const int16_t* idx, uint8_t* Q, uint8_t* SF, int64_t rows, int64_t KQ,
+                           int64_t KE, int variant, hipStream_t stream) {
+  QuantRule r{who};
+  if (kMode == kModeRms) { r.extra = true; r.kq_min = 2048; r.kq_max = 8192; }
+  if (const int rc = quant_checks(r, QuantArgs{X, Wn, idx, Q, SF, rows, KQ, KE, variant})) return rc < 0 ? rc : ARCQ_OK;
+  return launch_quantize<kMode>(X, Wn, eps, idx, Q, SF, rows, KQ, KE, variant, stream, who);
+}
 int quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, int variant,
                hipStream_t stream) {
-  return launch_quantize<kModeX>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, "arcq_quantize_x");
+  return quantize_static<kModeX>("arcq_quantize_x", X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream);
 }
 int quantize_w(const void* W, const int16_t* idx, uint8_t* QW, uint8_t* SFW, int64_t N, int64_t KQ, int64_t KE, int variant,
                hipStream_t stream) {
-  return launch_quantize<kModeW>(W, nullptr, 0.f, idx, QW, SFW, N, KQ, KE, variant, stream, "arcq_quantize_w");
+  return quantize_static<kModeW>("arcq_quantize_w", W, nullptr, 0.f, idx, QW, SFW, N, KQ, KE, variant, stream);
 }
 int rmsnorm_quantize_x(const void* X, const void* Wn, float eps, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M,
                        int64_t KQ, int64_t KE, int variant, hipStream_t stream) {
-  if (M > 0 && (reinterpret_cast<uintptr_t>(Wn) & 15) != 0)
-    return fail(ARCQ_ERR_SHAPE, "arcq_rmsnorm_quantize_x: the norm weight must be 16-byte aligned");
-  return launch_quantize<kModeRms>(X, Wn, eps, idx, QX, SFX, M, KQ, KE, variant, stream, "arcq_rmsnorm_quantize_x");
+  return quantize_static<kModeRms>("arcq_rmsnorm_quantize_x", X, Wn, eps, idx, QX, SFX, M, KQ, KE, variant, stream);
 }
 
 // workgroups of the abs-max pass: ~16 chunks (256 B) per thread, at most one slot per CU
@@ -454,49 +417,39 @@ static int absmax_grid(int64_t chunks) {
 constexpr int64_t kDynLocalMaxBytes = 48 * 1024;
 constexpr int64_t kDynLocalMaxTotalBytes = 16 * 1024 * 1024;
 
+// The three dynamic entries below run every check before their first launch: a failure after the abs-max launch would leave a stale
+// maximum in `state`.
 int quantize_x_dyn(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, float* scale_out, void* state, int64_t M,
                    int64_t KQ, int64_t KE, int variant, hipStream_t stream) {
-  if (!scale_out || !state) return fail(ARCQ_ERR_NULL, "arcq_quantize_x_dyn: NULL scale_out / state");
-  // validate the shape first (rows = 0 runs every check and launches nothing): a failure after the abs-max
-  // launch would leave a stale maximum in `state`
-  const int rc = launch_quantize<kModeX>(X, nullptr, 0.f, idx, QX, SFX, 0, KQ, KE, variant, stream, "arcq_quantize_x_dyn");
-  if (rc != ARCQ_OK || M <= 0) return rc;
-  if (!X || !idx || !QX || !SFX) return fail(ARCQ_ERR_NULL, "arcq_quantize_x_dyn: NULL pointer");
-  if ((reinterpret_cast<uintptr_t>(X) & 15) != 0) return fail(ARCQ_ERR_SHAPE, "arcq_quantize_x_dyn: X must be 16-byte aligned");
+  const char* who = "arcq_quantize_x_dyn";
+  QuantRule r{who};
+  r.dyn = kQuantState; r.x_alone = "X";
+  if (const int rc = quant_checks(r, QuantArgs{X, nullptr, idx, QX, SFX, M, KQ, KE, variant, 0, scale_out, state})) return rc < 0 ? rc : ARCQ_OK;
   unsigned int* st = reinterpret_cast<unsigned int*>(state);     // ARCQ_DYN_STATE_BYTES of scratch, fully rewritten here
   const int64_t n = M * KQ, n8 = n / 8;
-  int qg, qs;
-  quant_grid(M, KQ, &qg, &qs);
-  if (n * 2 <= kDynLocalMaxBytes && n * 2 * qg * qs <= kDynLocalMaxTotalBytes)     // decode-sized: one launch, `state` untouched
-    return launch_quantize<kModeX, kDynLocal>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, "arcq_quantize_x_dyn", nullptr, 0, scale_out);
+  const dim3 qg = quant_grid(M, KQ / 16);
+  if (n * 2 <= kDynLocalMaxBytes && n * 2 * (int64_t)(qg.x * qg.y) <= kDynLocalMaxTotalBytes)     // decode-sized: one launch, `state` untouched
+    return launch_quantize<kModeX, kDynLocal>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, who, nullptr, 0, scale_out);
   const int grid = absmax_grid(n8);
-  if (int e = launch_kernel<absmax_bits_kernel<false>>(dim3(grid), dim3(kAbsmaxThreads), 0, stream, "arcq_quantize_x_dyn", (const uint16_t*)X, n8, n, st)) return e;
-  return launch_quantize<kModeX, kDynState>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, "arcq_quantize_x_dyn", st, grid, scale_out);
+  if (int e = launch_kernel<absmax_bits_kernel<false>>(dim3(grid), dim3(kAbsmaxThreads), 0, stream, who, (const uint16_t*)X, n8, n, st)) return e;
+  return launch_quantize<kModeX, kDynState>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, who, st, grid, scale_out);
 }
 
 // The abs-max words were produced elsewhere (the silu-mul GEMM epilogue): one quantiser launch.
 int quantize_x_dyn_slots(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, float* scale_out, const uint32_t* slots,
                          int64_t nslots, int64_t M, int64_t KQ, int64_t KE, int variant, hipStream_t stream) {
   const char* who = "arcq_quantize_x_dyn_slots";
-  if (!scale_out || !slots || nslots <= 0 || nslots > INT32_MAX) return fail(ARCQ_ERR_NULL, "%s: NULL scale_out / absmax_slots, or no slots", who);
-  if (!idx) {                                               // identity: X is already in reordered channel order
-    if (M < 0 || KQ <= 0 || (KQ % 64) || (KE % 64) || KE < 0 || KE > KQ || KQ > 32767)
-      return fail(ARCQ_ERR_SHAPE, "%s: need KQ%%64==0, KE%%64==0, 0<=KE<=KQ<=32767 (M=%lld KQ=%lld KE=%lld)", who, (long long)M, (long long)KQ, (long long)KE);
-    if (variant != ARCQ_VARIANT_G16 && variant != ARCQ_VARIANT_G32) return fail(ARCQ_ERR_SHAPE, "%s: unknown variant %d", who, variant);
-    if (M == 0) return ARCQ_OK;
-    if (!X || !QX || !SFX) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(QX) & 7) || (reinterpret_cast<uintptr_t>(SFX) & 3))
-      return fail(ARCQ_ERR_SHAPE, "%s: X must be 16-byte, QX 8-byte and SFX 4-byte aligned", who);
-    const int64_t total = M * (KQ / 16);
-    const int grid = (int)((total + kQuantThreads - 1) / kQuantThreads < kMaxQuantBlocks ? (total + kQuantThreads - 1) / kQuantThreads : kMaxQuantBlocks);
-    const uint16_t* x = (const uint16_t*)X;
-    if (variant == ARCQ_VARIANT_G16)
-      return launch_kernel<quantize_contig_dyn_kernel<ARCQ_VARIANT_G16>>(dim3(grid), dim3(kQuantThreads), 0, stream, who, x, QX, SFX, (int)M, (int)KQ, (int)KE, slots,
-                                                                         (int)nslots, scale_out);
-    return launch_kernel<quantize_contig_dyn_kernel<ARCQ_VARIANT_G32>>(dim3(grid), dim3(kQuantThreads), 0, stream, who, x, QX, SFX, (int)M, (int)KQ, (int)KE, slots,
-                                                                       (int)nslots, scale_out);
-  }
-  return launch_quantize<kModeX, kDynState>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, who, slots, (int)nslots, scale_out);
+  QuantRule r{who};
+  r.dyn = kQuantSlots; r.family = idx ? kQuantNv : kQuantNvContig;
+  if (const int rc = quant_checks(r, QuantArgs{X, nullptr, idx, QX, SFX, M, KQ, KE, variant, 0, scale_out, slots, nslots})) return rc < 0 ? rc : ARCQ_OK;
+  if (idx) return launch_quantize<kModeX, kDynState>(X, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, who, slots, (int)nslots, scale_out);
+  // identity: X is already in reordered channel order
+  const int64_t want = (M * (KQ / 16) + kQuantThreads - 1) / kQuantThreads;
+  const dim3 grid((unsigned)(want < kMaxQuantBlocks ? want : kMaxQuantBlocks)), block(kQuantThreads);
+  return by_variant(variant, [&](auto v) {
+    return launch_kernel<quantize_contig_dyn_kernel<decltype(v)::value>>(grid, block, 0, stream, who, (const uint16_t*)X, QX, SFX, (int)M, (int)KQ, (int)KE, slots,
+                                                                        (int)nslots, scale_out);
+  });
 }
 
 // GU = [M, 2*KQ] bf16 (gate | up, the fused gate_up projection's output): quantise silu(gate) * up with its
@@ -505,12 +458,9 @@ int quantize_x_dyn_slots(const void* X, const int16_t* idx, uint8_t* QX, uint8_t
 int silu_mul_quantize_x_dyn(const void* GU, const int16_t* idx, uint8_t* QX, uint8_t* SFX, float* scale_out, void* state, int64_t M,
                             int64_t KQ, int64_t KE, int variant, int layout, hipStream_t stream) {
   const char* who = "arcq_silu_mul_quantize_x_dyn";
-  if (layout != ARCQ_GU_HALVES && layout != ARCQ_GU_PAIRS) return fail(ARCQ_ERR_SHAPE, "%s: unknown layout %d", who, layout);
-  if (!scale_out || !state) return fail(ARCQ_ERR_NULL, "%s: NULL scale_out / state", who);
-  const int rc = launch_quantize<kModeX>(GU, nullptr, 0.f, idx, QX, SFX, 0, KQ, KE, variant, stream, who);
-  if (rc != ARCQ_OK || M <= 0) return rc;
-  if (!GU || !idx || !QX || !SFX) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if ((reinterpret_cast<uintptr_t>(GU) & 15) != 0) return fail(ARCQ_ERR_SHAPE, "%s: GU must be 16-byte aligned", who);
+  QuantRule r{who};
+  r.dyn = kQuantState; r.layout = true; r.x_alone = "GU";
+  if (const int rc = quant_checks(r, QuantArgs{GU, nullptr, idx, QX, SFX, M, KQ, KE, variant, layout, scale_out, state})) return rc < 0 ? rc : ARCQ_OK;
   unsigned int* st = reinterpret_cast<unsigned int*>(state);
   const uint16_t* G = reinterpret_cast<const uint16_t*>(GU);
   const uint16_t* U = G + KQ;
@@ -531,12 +481,9 @@ int silu_mul_quantize_x_dyn(const void* GU, const int16_t* idx, uint8_t* QX, uin
 int silu_mul_quantize_x_dyn_slots(const void* GU, const int16_t* idx, uint8_t* QX, uint8_t* SFX, float* scale_out, const uint32_t* slots,
                                   int64_t nslots, int64_t M, int64_t KQ, int64_t KE, int variant, int layout, hipStream_t stream) {
   const char* who = "arcq_silu_mul_quantize_x_dyn_slots";
-  if (layout != ARCQ_GU_HALVES && layout != ARCQ_GU_PAIRS) return fail(ARCQ_ERR_SHAPE, "%s: unknown layout %d", who, layout);
-  if (!scale_out || !slots || nslots <= 0 || nslots > INT32_MAX) return fail(ARCQ_ERR_NULL, "%s: NULL scale_out / absmax_slots, or no slots", who);
-  const int rc = launch_quantize<kModeX>(GU, nullptr, 0.f, idx, QX, SFX, 0, KQ, KE, variant, stream, who);
-  if (rc != ARCQ_OK || M <= 0) return rc;
-  if (!GU || !idx || !QX || !SFX) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if ((reinterpret_cast<uintptr_t>(GU) & 15) != 0) return fail(ARCQ_ERR_SHAPE, "%s: GU must be 16-byte aligned", who);
+  QuantRule r{who};
+  r.dyn = kQuantSlots; r.layout = true; r.x_alone = "GU";
+  if (const int rc = quant_checks(r, QuantArgs{GU, nullptr, idx, QX, SFX, M, KQ, KE, variant, layout, scale_out, slots, nslots})) return rc < 0 ? rc : ARCQ_OK;
   const uint16_t* G = reinterpret_cast<const uint16_t*>(GU);
   if (layout == ARCQ_GU_PAIRS)
     return launch_quantize<kModeX, kDynState, kSiluPairs>(G, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, variant, stream, who, slots, (int)nslots, scale_out, G, 2 * KQ);

@@ -1,6 +1,13 @@
 // Per-group NVFP4 quantisation of the quantiser kernels (quantize.hip), kept apart from the row/launch logic: ONE
 // statement of the arithmetic for every kernel that has to produce the same bytes (a GEMM prologue that quantised its
-// own activations with it was bit-identical but slower).
+// own activations with it was bit-identical but slower).  Also the augmented-K position rule, for the kernels
+// (quantize.hip, the prologue of gemm_stream.hip) and for arcq_primary_pos / arcq_residual_pos.
+//
+// Remaining duplication, on purpose: the emission of an activation group (primary codes, the quad's scale dword, the
+// residual twin) is written out in both kernels of quantize.hip, the dynamic-scale step (abs-max words -> amax / 2688 -> scale_out ->
+// bf16-rounded divisor) in both and in the stream prologue, the index-word gather through lds_pad_pair in quantize.hip (twice),
+// quantize_mx.hip (twice) and the stream prologue.  Behind a function boundary hipcc numbers the registers of these issue-bound kernels
+// differently (profiles/quant_shared_isa_identity.txt lists what was kept identical); such a change needs an A-B on the GPU first.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -66,6 +73,17 @@ __device__ __forceinline__ GroupQ quantize_group(float (&v)[16]) {
   g.packed = make_uint2(lo, hi);
   return g;
 }
+
+// Augmented-K position of reordered group g (reorder.cu:139 / :451-452); P = first group of the outlier tail.  The twin of a tail group
+// (the residual of x, the duplicate of w) sits aug_twin_step further.
+template <int kVariant, typename T>
+__host__ __device__ __forceinline__ T aug_group_pos(T g, T P) {
+  if (kVariant == ARCQ_VARIANT_G16) return g + (g > P ? g - P : 0);
+  const T g1 = g & ~(T)1;
+  return g1 + (g1 > P ? g1 - P : 0) + (g & 1);
+}
+template <int kVariant>
+constexpr int aug_twin_step = kVariant == ARCQ_VARIANT_G16 ? 1 : 2;
 
 // max |x| over eight bf16 values (as bit patterns: |bf16| ordering == ordering of the low 15 bits)
 __device__ __forceinline__ uint32_t absmax_bits_chunk(const uint4 d, uint32_t m) {

@@ -78,14 +78,7 @@ __global__ __launch_bounds__(kMxThreads) void mx_quantize_rows_kernel(const uint
         mx_store_x_block(qrow, srow, b, br, tail, v);
       }
     }
-    // padding blocks [K/32, Kp/32): code 0, scale 2^0 (at most two blocks; written by the workgroup of the row's first range)
-    if (blockIdx.y == 0) {
-      const int pb = (K >> 5) + tid;
-      if (pb < Bp) {
-        *reinterpret_cast<uint4*>(qrow + (size_t)pb * 16) = make_uint4(0, 0, 0, 0);
-        srow[pb] = 127;
-      }
-    }
+    if (blockIdx.y == 0) mx_store_padding(qrow, srow, K, Bp, tid);     // (by the workgroup of the row's first range)
     __syncthreads();   // row_lds is rewritten by the next row
   }
 }
@@ -163,37 +156,20 @@ __global__ __launch_bounds__(kMxThreads) void mx_fused_rows_kernel(const uint16_
       }
       mx_store_x_block(qrow, srow, b, B + (b - P), b >= P, v);
     }
-    if (blockIdx.y == 0) {                                // padding blocks [K/32, Kp/32): code 0, scale 2^0
-      const int pb = (K >> 5) + tid;
-      if (pb < Bp) {
-        *reinterpret_cast<uint4*>(qrow + (size_t)pb * 16) = make_uint4(0, 0, 0, 0);
-        srow[pb] = 127;
-      }
-    }
+    if (blockIdx.y == 0) mx_store_padding(qrow, srow, K, Bp, tid);     // (by the workgroup of the row's first range)
     if (!kDirect) __syncthreads();   // row_lds (and the reduction scratch) are rewritten by the next row
   }
 }
 
-constexpr int kMxMaxBlocks = 2048;
-
+// (the grid of every launch here is quant_grid over the row's 32-element blocks)
 template <bool kModeW>
 static int mx_launch(const void* X, const int16_t* idx, uint8_t* Q, uint8_t* SF, int64_t rows, int64_t KQ, int64_t KE, hipStream_t stream,
                      const char* who) {
-  if (rows < 0 || KQ <= 0 || (KQ % 64) || (KE % 64) || KE < 0 || KE > KQ || KQ > 32767)
-    return fail(ARCQ_ERR_SHAPE, "%s: need KQ%%64==0, KE%%64==0, 0<=KE<=KQ<=32767 (rows=%lld KQ=%lld KE=%lld)", who, (long long)rows,
-                (long long)KQ, (long long)KE);
-  if (rows == 0) return ARCQ_OK;
-  if (!X || !idx || !Q || !SF) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (rows > INT32_MAX) return fail(ARCQ_ERR_UNSUPPORTED, "%s: too many rows", who);
-  // 16-byte row / index loads and code stores (Kp/2 is a multiple of 64); scale bytes need no alignment
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(Q)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: X, reorder_index and the packed output must be 16-byte aligned", who);
-  const size_t lds = lds_row_bytes((size_t)KQ);
-  const int grid = (int)(rows < kMxMaxBlocks ? rows : kMxMaxBlocks);
-  int split = 1;       // decode: split the row's blocks over up to 16 workgroups of >= 32 blocks each
-  while (grid * split < 256 && split < 16 && (KQ / 32) / (split * 2) >= 32) split *= 2;
-  return launch_kernel<mx_quantize_rows_kernel<kModeW>>(dim3(grid, split), dim3(kMxThreads), (int)lds, stream, who, (const uint16_t*)X, idx, Q, SF, (int)rows, (int)KQ,
-                                                        (int)KE);
+  QuantRule r{who};
+  r.family = kQuantMx;
+  if (const int rc = quant_checks(r, QuantArgs{X, nullptr, idx, Q, SF, rows, KQ, KE})) return rc < 0 ? rc : ARCQ_OK;
+  return launch_kernel<mx_quantize_rows_kernel<kModeW>>(quant_grid(rows, KQ / 32), dim3(kMxThreads), (int)lds_row_bytes((size_t)KQ), stream, who, (const uint16_t*)X,
+                                                        idx, Q, SF, (int)rows, (int)KQ, (int)KE);
 }
 
 int mx_quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, hipStream_t stream) {
@@ -203,63 +179,37 @@ int mx_quantize_w(const void* W, const int16_t* idx, uint8_t* QW, uint8_t* SFW, 
   return mx_launch<true>(W, idx, QW, SFW, N, KQ, KE, stream, "arcq_mx_quantize_w");
 }
 
-// shape, NULL and alignment rules shared by the fused entry points (those of mx_launch, `extra` = a further 16-byte aligned input)
-static int mx_fused_checks(const void* X, const void* extra, bool has_extra, const int16_t* idx, const uint8_t* Q, const uint8_t* SF, int64_t rows,
-                           int64_t KQ, int64_t KE, int64_t kq_min, int64_t kq_max, const char* who) {
-  if (rows < 0 || KQ <= 0 || (KQ % 64) || (KE % 64) || KE < 0 || KE > KQ || KQ < kq_min || KQ > kq_max)
-    return fail(ARCQ_ERR_SHAPE, "%s: need KQ%%64==0, KE%%64==0, 0<=KE<=KQ, %lld<=KQ<=%lld (rows=%lld KQ=%lld KE=%lld)", who, (long long)kq_min,
-                (long long)kq_max, (long long)rows, (long long)KQ, (long long)KE);
-  if (rows == 0) return 1;                                  // nothing to do
-  if (!X || !idx || !Q || !SF || (has_extra && !extra)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (rows > INT32_MAX) return fail(ARCQ_ERR_UNSUPPORTED, "%s: too many rows", who);
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(extra) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(Q)) & 15)
-    return fail(ARCQ_ERR_SHAPE, "%s: the inputs, reorder_index and the packed output must be 16-byte aligned", who);
-  return ARCQ_OK;
-}
-
-// the grid of mx_launch: one workgroup per row, decode-sized inputs split over up to 16 workgroups of >= 32 blocks each
-static void mx_grid(int64_t rows, int64_t KQ, int* grid, int* split) {
-  *grid = (int)(rows < kMxMaxBlocks ? rows : kMxMaxBlocks);
-  int s = 1;
-  while (*grid * s < 256 && s < 16 && (KQ / 32) / (s * 2) >= 32) s *= 2;
-  *split = s;
-}
-
 template <int kSrc, bool kDirect>
 static int mx_fused_launch(const void* X, const void* Xup, int64_t ldx, const void* Wn, float eps, const int16_t* idx, uint8_t* Q, uint8_t* SF,
-                           int64_t rows, int64_t KQ, int64_t KE, int grid, int split, hipStream_t stream, const char* who) {
+                           int64_t rows, int64_t KQ, int64_t KE, hipStream_t stream, const char* who) {
   const size_t lds = kDirect ? 0 : lds_row_bytes((size_t)KQ) + (kSrc == kMxSrcRms ? 512 * sizeof(float) + lds_row_bytes((size_t)KQ) : 0);
-  return launch_kernel<mx_fused_rows_kernel<kSrc, kDirect>>(dim3(grid, split), dim3(kMxThreads), (int)lds, stream, who, (const uint16_t*)X, (const uint16_t*)Xup, ldx,
-                                                            (const uint16_t*)Wn, eps, idx, Q, SF, (int)rows, (int)KQ, (int)KE);
+  return launch_kernel<mx_fused_rows_kernel<kSrc, kDirect>>(quant_grid(rows, KQ / 32), dim3(kMxThreads), (int)lds, stream, who, (const uint16_t*)X,
+                                                            (const uint16_t*)Xup, ldx, (const uint16_t*)Wn, eps, idx, Q, SF, (int)rows, (int)KQ, (int)KE);
 }
 
 int mx_rmsnorm_quantize_x(const void* X, const void* Wn, float eps, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ,
                           int64_t KE, hipStream_t stream) {
-  const char* who = "arcq_mx_rmsnorm_quantize_x";
+  QuantRule r{"arcq_mx_rmsnorm_quantize_x"};
   // 2048 <= KQ <= 8192: the reduction tree of rms_rstd_tree is defined for 128 .. 512 virtual threads (arcq_rmsnorm_quantize_x's range)
-  const int rc = mx_fused_checks(X, Wn, true, idx, QX, SFX, M, KQ, KE, 2048, 8192, who);
-  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
-  int grid, split;
-  mx_grid(M, KQ, &grid, &split);
-  return mx_fused_launch<kMxSrcRms, false>(X, nullptr, KQ, Wn, eps, idx, QX, SFX, M, KQ, KE, grid, split, stream, who);
+  r.family = kQuantMxFused; r.extra = true; r.kq_min = 2048; r.kq_max = 8192;
+  if (const int rc = quant_checks(r, QuantArgs{X, Wn, idx, QX, SFX, M, KQ, KE})) return rc < 0 ? rc : ARCQ_OK;
+  return mx_fused_launch<kMxSrcRms, false>(X, nullptr, KQ, Wn, eps, idx, QX, SFX, M, KQ, KE, stream, r.who);
 }
 
 int mx_silu_mul_quantize_x(const void* GU, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, int layout,
                            hipStream_t stream) {
   const char* who = "arcq_mx_silu_mul_quantize_x";
-  if (layout != ARCQ_GU_HALVES && layout != ARCQ_GU_PAIRS) return fail(ARCQ_ERR_SHAPE, "%s: unknown layout %d", who, layout);
-  const int rc = mx_fused_checks(GU, nullptr, false, idx, QX, SFX, M, KQ, KE, 64, 32767, who);
-  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
-  int grid, split;
-  mx_grid(M, KQ, &grid, &split);
+  QuantRule r{who};
+  r.family = kQuantMxFused; r.layout = true;
+  if (const int rc = quant_checks(r, QuantArgs{GU, nullptr, idx, QX, SFX, M, KQ, KE, ARCQ_VARIANT_G16, layout})) return rc < 0 ? rc : ARCQ_OK;
   const uint16_t* G = reinterpret_cast<const uint16_t*>(GU);
   const bool pairs = layout == ARCQ_GU_PAIRS;
   const uint16_t* U = pairs ? G : G + KQ;
-  if (split > 1)
-    return pairs ? mx_fused_launch<kMxSrcSiluPairs, true>(G, U, 2 * KQ, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, grid, split, stream, who)
-                 : mx_fused_launch<kMxSrcSiluHalves, true>(G, U, 2 * KQ, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, grid, split, stream, who);
-  return pairs ? mx_fused_launch<kMxSrcSiluPairs, false>(G, U, 2 * KQ, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, grid, split, stream, who)
-               : mx_fused_launch<kMxSrcSiluHalves, false>(G, U, 2 * KQ, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, grid, split, stream, who);
+  if (quant_grid(M, KQ / 32).y > 1)                           // rows split over workgroups: the direct gather
+    return pairs ? mx_fused_launch<kMxSrcSiluPairs, true>(G, U, 2 * KQ, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, stream, who)
+                 : mx_fused_launch<kMxSrcSiluHalves, true>(G, U, 2 * KQ, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, stream, who);
+  return pairs ? mx_fused_launch<kMxSrcSiluPairs, false>(G, U, 2 * KQ, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, stream, who)
+               : mx_fused_launch<kMxSrcSiluHalves, false>(G, U, 2 * KQ, nullptr, 0.f, idx, QX, SFX, M, KQ, KE, stream, who);
 }
 
 }  // namespace arcq

@@ -75,4 +75,13 @@ __device__ __forceinline__ void mx_store_x_block(uint8_t* qrow, uint8_t* srow, i
   }
 }
 
+// The padding blocks [K/32, Bp) of a row (K = KQ + KE, Bp = round_up(K, 128) / 32: at most two): code 0, scale 2^0; thread t writes block K/32 + t.
+__device__ __forceinline__ void mx_store_padding(uint8_t* qrow, uint8_t* srow, int K, int Bp, int t) {
+  const int pb = (K >> 5) + t;
+  if (pb < Bp) {
+    *reinterpret_cast<uint4*>(qrow + (size_t)pb * 16) = make_uint4(0, 0, 0, 0);
+    srow[pb] = 127;
+  }
+}
+
 }  // namespace arcq

@@ -5,6 +5,9 @@ the built library and compares for equality, so a change of the validation code 
 Every pointer is a stand-in address that is never dereferenced: each case ends in a rejection (-1 shape, -2 unsupported, -4 NULL) or in
 the empty-shape return (0 with M == 0 or N == 0).  The script refuses to write a table with any other outcome, so no case can reach a
 launch.  Run it on the commit whose behaviour is to be pinned:  python tests/golden/make_cabi_rejections.py
+
+A second table, tests/golden/cabi_quant_rejections.json, holds the same for the twelve quantiser entry points (QUANT_SPECS below; rows == 0
+is their empty shape), replayed by its own test of tests/test_cabi.py.
 """
 import json
 import os
@@ -117,9 +120,115 @@ def _cases(s):
     return cases
 
 
+# ---- the quantisers: tests/golden/cabi_quant_rejections.json ---------------------------------------------------------------------------
+# Per entry point: ``order`` = its arguments in C order (the row count is called M everywhere), ``align`` = every pointer it needs with
+# the alignment it demands BEFORE its first HIP call (0: none), ``data`` = the pointers that may be NULL when M == 0, ``base`` = a shape
+# it would run.  ``neg_rows`` / ``big_rows``: M < 0 and M > INT32_MAX are rejections of this entry before its first HIP call.
+#   arcq_quantize_x_dyn and the two arcq_silu_mul_quantize_x_dyn* accept M < 0 as empty (0 with rows != 0: not a case for this table).
+#   arcq_quantize_x_dyn (beyond the decode-sized single launch) and arcq_silu_mul_quantize_x_dyn launch their abs-max pass before the row
+#   limit and the reorder_index / QX / SFX alignment are looked at, and the identity form of arcq_quantize_x_dyn_slots has no row limit:
+#   those faults reach a HIP call there, so the table cannot hold them (arcq_quantize_x_dyn's base shape is decode-sized).
+_NV = ["X", "reorder_index", "QX", "SFX", "M", "KQ", "KE", "variant", "stream"]
+_NV_ALIGN = dict(X=16, reorder_index=16, QX=8, SFX=4)
+_MX_ALIGN = dict(X=16, reorder_index=16, QX=16, SFX=0)
+_DATA = ["X", "reorder_index", "QX", "SFX"]
+QUANT_SPECS = [
+    dict(name="arcq_quantize_x", order=_NV, align=_NV_ALIGN, data=_DATA, base=dict(variant=1), neg_rows=True, big_rows=True),
+    dict(name="arcq_quantize_w", order=_NV, align=_NV_ALIGN, data=_DATA, base=dict(variant=1), neg_rows=True, big_rows=True),
+    dict(name="arcq_rmsnorm_quantize_x", order=["X", "W", "eps", "reorder_index", "QX", "SFX", "M", "KQ", "KE", "variant", "stream"],
+         align=dict(_NV_ALIGN, W=16), data=_DATA + ["W"], base=dict(KQ=4096, variant=0), neg_rows=True, big_rows=True, rms="W"),
+    dict(name="arcq_quantize_x_dyn", order=["X", "reorder_index", "QX", "SFX", "scale_out", "state", "M", "KQ", "KE", "variant", "stream"],
+         align=dict(_NV_ALIGN, scale_out=0, state=0), data=_DATA, base=dict(variant=1), dyn=["scale_out", "state"]),
+    dict(name="arcq_quantize_x_dyn_slots", order=["X", "reorder_index", "QX", "SFX", "scale_out", "absmax_slots", "nslots", "M", "KQ", "KE", "variant", "stream"],
+         align=dict(_NV_ALIGN, scale_out=0, absmax_slots=0), data=_DATA, base=dict(variant=1), neg_rows=True, big_rows=True,
+         dyn=["scale_out", "absmax_slots"], keep="reorder_index"),      # (without it the call is the next group's)
+    # reorder_index == NULL: X is already in reordered channel order (its own kernel, its own checks)
+    dict(name="arcq_quantize_x_dyn_slots", group="arcq_quantize_x_dyn_slots, reorder_index == NULL",
+         order=["X", "reorder_index", "QX", "SFX", "scale_out", "absmax_slots", "nslots", "M", "KQ", "KE", "variant", "stream"],
+         align=dict(X=16, QX=8, SFX=4, scale_out=0, absmax_slots=0), data=["X", "QX", "SFX"], base=dict(variant=1), neg_rows=True,
+         dyn=["scale_out", "absmax_slots"]),
+    dict(name="arcq_silu_mul_quantize_x_dyn", order=["X", "reorder_index", "QX", "SFX", "scale_out", "state", "M", "KQ", "KE", "variant", "layout", "stream"],
+         align=dict(X=16, reorder_index=0, QX=0, SFX=0, scale_out=0, state=0), data=_DATA, base=dict(variant=1), dyn=["scale_out", "state"]),
+    dict(name="arcq_silu_mul_quantize_x_dyn_slots", order=["X", "reorder_index", "QX", "SFX", "scale_out", "absmax_slots", "nslots", "M", "KQ", "KE", "variant",
+                                                            "layout", "stream"],
+         align=dict(_NV_ALIGN, scale_out=0, absmax_slots=0), data=_DATA, base=dict(variant=1), big_rows=True, dyn=["scale_out", "absmax_slots"]),
+    dict(name="arcq_mx_quantize_x", order=_NV[:7] + ["stream"], align=_MX_ALIGN, data=_DATA, neg_rows=True, big_rows=True),
+    dict(name="arcq_mx_quantize_w", order=_NV[:7] + ["stream"], align=_MX_ALIGN, data=_DATA, neg_rows=True, big_rows=True),
+    dict(name="arcq_mx_rmsnorm_quantize_x", order=["X", "W", "eps", "reorder_index", "QX", "SFX", "M", "KQ", "KE", "stream"],
+         align=dict(_MX_ALIGN, W=16), data=_DATA + ["W"], base=dict(KQ=4096), neg_rows=True, big_rows=True, rms="W"),
+    dict(name="arcq_mx_silu_mul_quantize_x", order=_NV[:7] + ["layout", "stream"], align=_MX_ALIGN, data=_DATA, neg_rows=True, big_rows=True),
+]
+
+
+def _quant_cases(s):
+    """One case per fault, pointer and pairing that the entry has: the table stays readable, a second value per fault would pin nothing more."""
+    order, align, data = s["order"], s["align"], s["data"]
+    base = {a: None for a in order}
+    base.update({p: P for p in align}, eps=1e-6, M=4, KQ=3584, KE=64, variant=0, layout=0, nslots=8)
+    base.update(s.get("base", {}))
+    KQ, big = base["KQ"], dict(M=1 << 31)
+    mis = {p: P + a // 2 for p, a in align.items() if a}         # one misaligned address per pointer with an alignment rule
+    shape = [dict(KQ=KQ + 16), dict(KE=100), dict(KE=-64), dict(KE=KQ + 64), dict(KQ=0), dict(KQ=32768)]
+    shape += [dict(KQ=1024), dict(KQ=8256)] if s.get("rms") else []
+    shape += [dict(M=-1)] if s.get("neg_rows") else []
+    enums = [{e: 7} for e in ("variant", "layout") if e in order]
+    slots = [dict(nslots=0), dict(nslots=1 << 31)] if "nslots" in order else []
+    faults = shape + enums + slots + ([big] if s.get("big_rows") else [])
+    nulls, x, q = {p: None for p in data}, data[0], "QX"
+    out = faults + [{p: None} for p in align] + [{p: v} for p, v in mis.items()]
+    out += [dict(M=0), dict(M=0, **nulls), dict(M=0, **{p: None for p in align}), dict(shape[0], M=0), dict(shape[5], M=0), dict(M=0, **{x: mis[x]})]
+    out += [dict(e, M=0) for e in enums + slots[:1]]
+    # pairs of faults from different classes: which one is reported is part of the contract
+    out += [dict(shape[0], **{x: None}), dict(shape[0], **{x: mis[x]}), dict(shape[5], **{x: None}), {x: None, q: mis.get(q, P)}, {"SFX": None, x: mis[x]}]
+    out += [dict(shape[0], **e) for e in enums + slots[:1]] + [dict(shape[5], **e) for e in enums] + [dict(e, **{x: None}) for e in enums + slots[:1]]
+    out += [{x: mis[x], q: mis[q]}] if q in mis else []
+    out += [dict(big, **{x: None}), dict(big, **{x: mis[x]}), dict(big, **shape[0])] if s.get("big_rows") else []
+    for d in s.get("dyn", ()):
+        out += [dict(shape[0], **{d: None}), {d: None, "M": 0}, {d: None, x: None}]
+    if s.get("rms"):
+        w = s["rms"]
+        out += [dict(shape[0], **{w: mis[w]}), dict(shape[6], **{w: mis[w]}), {w: mis[w], "M": 0}, {w: mis[w], x: None}, {w: None, x: mis[x]}, dict(big, **{w: mis[w]})]
+        out += [dict(e, **{w: mis[w]}) for e in enums]
+    seen, cases = set(), []
+    for over in out:
+        full = dict(base, **over)
+        args = [full[a] for a in order]
+        if json.dumps(args) not in seen and full.get(s.get("keep"), P) is not None:
+            seen.add(json.dumps(args))
+            cases.append(args)
+    return dict(fn=s["name"], group=s.get("group", s["name"]), rows_arg=order.index("M"), cases=cases)
+
+
+def _absmax_cases():
+    """arcq_absmax_scale(X, n, scale_out, stream) has no empty return (n == 0 still issues a memset): rejections only."""
+    out = [(x, n, so) for n in (-1, -(1 << 40)) for x in (P, None, P + 2) for so in (P, None)]
+    out += [(x, n, None) for n in (0, 8) for x in (P, None, P + 8)]
+    out += [(None, 1, P), (None, 1 << 40, P)] + [(P + off, n, P) for off in (1, 2, 4, 8) for n in (0, 4096)]
+    return dict(fn="arcq_absmax_scale", group="arcq_absmax_scale", rows_arg=1, cases=[[x, n, so, None] for x, n, so in out])
+
+
+def quant_main(L):
+    """The table: one object per entry point (``group``: the reorder_index == NULL form of arcq_quantize_x_dyn_slots apart), its cases as
+    [args, status, error text], ``rows_arg`` = which argument is the row count."""
+    groups = [_quant_cases(s) for s in QUANT_SPECS] + [_absmax_cases()]
+    for g in groups:
+        for i, args in enumerate(g["cases"]):
+            st = int(getattr(L, g["fn"])(*args))
+            ok = st in (-1, -2, -4) or (st == 0 and args[g["rows_arg"]] == 0 and g["fn"] != "arcq_absmax_scale")
+            if not ok:
+                raise SystemExit(f"{g['fn']}{tuple(args)} -> {st}: not a rejection, such a case must not be in the table")
+            g["cases"][i] = [args, st, L.arcq_last_error().decode() if st else ""]
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cabi_quant_rejections.json")
+    with open(path, "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps(dict(g, cases=[])).replace("[]}", "[\n") + ",\n".join(json.dumps(c) for c in g["cases"]) + "\n]}"
+                                    for g in groups) + "\n]\n")
+    print(f"{sum(len(g['cases']) for g in groups)} cases, at least {min(len(g['cases']) for g in groups)} per entry point -> {path}")
+
+
 def main():
     from arcquant_amd import _lib
     L = _lib.lib()
+    quant_main(L)
     table = []
     for s in SPECS:
         for c in _cases(s):

@@ -136,3 +136,43 @@ def test_rejections_are_those_of_the_recorded_table():
         assert st == c["status"], (c, st, L.arcq_last_error())
         if st:
             assert L.arcq_last_error().decode() == c["error"], c
+
+
+def test_quantiser_rejections_are_those_of_the_recorded_table():
+    """tests/golden/cabi_quant_rejections.json (second table of tests/golden/make_cabi_rejections.py) pins the same for the twelve quantiser
+    entry points, one object per entry with its cases as [args, status, error text]: status and arcq_last_error() text must be equal, case
+    by case.  No case can launch: each expects a rejection, or ARCQ_OK with rows == 0 (never for arcq_absmax_scale, whose n == 0 still
+    issues a memset)."""
+    import json
+    L = _lib.lib()
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "cabi_quant_rejections.json")))
+    assert len({g["fn"] for g in table}) == 12
+    assert len({g["group"] for g in table}) == 13                     # arcq_quantize_x_dyn_slots with reorder_index == NULL is its own group
+    for g in table:
+        assert len(g["cases"]) >= 20, g["group"]
+        for args, status, _ in g["cases"]:
+            assert status in (-1, -2, -4) or (status == 0 and args[g["rows_arg"]] == 0 and g["fn"] != "arcq_absmax_scale"), (g["group"], args)
+    for g in table:
+        for args, status, error in g["cases"]:
+            st = getattr(L, g["fn"])(*args)
+            assert st == status, (g["group"], args, status, st, L.arcq_last_error())
+            if st:
+                assert L.arcq_last_error().decode() == error, (g["group"], args)
+
+
+def test_dynamic_quantisers_check_everything_before_their_first_launch():
+    """Faults the recorded table cannot hold, because the library that wrote it reported them only after a launch (the abs-max pass of
+    arcq_quantize_x_dyn beyond decode size and of arcq_silu_mul_quantize_x_dyn) or not at all (the row limit of arcq_quantize_x_dyn_slots
+    with reorder_index == NULL, whose kernel counts rows in 32 bits): same status and text as the static quantiser, and no HIP call."""
+    L = _lib.lib()
+    P = 4096
+    err = lambda: L.arcq_last_error().decode()
+    silu, dyn, slots = L.arcq_silu_mul_quantize_x_dyn, L.arcq_quantize_x_dyn, L.arcq_quantize_x_dyn_slots
+    assert silu(P, P + 8, P, P, P, P, 4, 3584, 64, 1, 0, None) == -1 and err() == "arcq_silu_mul_quantize_x_dyn: X and reorder_index must be 16-byte aligned"
+    assert silu(P, P, P + 4, P, P, P, 4, 3584, 64, 1, 0, None) == -1 and "8-byte" in err()
+    assert silu(P, P, P, P + 2, P, P, 4, 3584, 64, 1, 0, None) == -1 and "4-byte" in err()
+    assert silu(P, P, P, P, P, P, 1 << 31, 3584, 64, 1, 0, None) == -2 and err() == "arcq_silu_mul_quantize_x_dyn: too many rows"
+    assert dyn(P, P + 8, P, P, P, P, 4096, 4096, 64, 0, None) == -1 and err() == "arcq_quantize_x_dyn: X and reorder_index must be 16-byte aligned"
+    assert dyn(P, P, P, P + 2, P, P, 4096, 4096, 64, 0, None) == -1 and "4-byte" in err()
+    assert dyn(P, P, P, P, P, P, 1 << 31, 4096, 64, 0, None) == -2 and err() == "arcq_quantize_x_dyn: too many rows"
+    assert slots(P, None, P, P, P, P, 8, 1 << 31, 3584, 64, 1, None) == -2 and err() == "arcq_quantize_x_dyn_slots: too many rows"
