@@ -64,6 +64,11 @@ SYMBOLS = {
     "arcq_mx_silu_mul_quantize_x": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
     "arcq_gemm_mxfp4_silu_mul": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p]),
     "arcq_gemm_mxfp4_silu_mul_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _i64, _p]),
+    "arcq_mx_repacked_w_bytes": (_i64, [_i64, _i64]),
+    "arcq_mx_repacked_sf_bytes": (_i64, [_i64, _i64]),
+    "arcq_gemm_mxfp4_repacked_supported": (_i32, [_i64, _i64, _i64]),
+    "arcq_gemm_mxfp4_repacked": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p]),
+    "arcq_gemm_mxfp4_repacked_silu_mul": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p]),
 }
 
 # include/arcq_harness.h: e2e-harness-only entry points (NOT the drop-in boundary)

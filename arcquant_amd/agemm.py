@@ -747,6 +747,20 @@ def dynamic_matmul_repacked(X: torch.Tensor, reorder_index: torch.Tensor, KE: in
     return out, scale.reshape(())
 
 
+# ---- MXFP4 repacked weight (include/arcq.h "MXFP4 repacked weight"): the layout functions and the decode GEMM over it live in
+# arcquant_amd/mx.py with the other MXFP4 operators that only the ctypes mirror has; they are reachable under this module's name too.
+# (Resolved on first use: mx imports this module's validators.)
+_FROM_MX = ("MX_REPACKED_MAX_M", "mx_repack_w", "mx_unrepack_w", "mx_repacked_supported", "mx_matmul_repacked")
+
+
+def __getattr__(name):
+    if name in _FROM_MX:
+        from . import mx
+        value = globals()[name] = getattr(mx, name)
+        return value
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 # --- KV-cache functions of the reference module (bindings.cpp:576-581): OUT OF SCOPE.
 # Present so that `from model.kv_cache import *` still imports against this module.
 def _kv_stub(name):

@@ -136,6 +136,14 @@ int gemm_mx_silu_mul(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, con
                      float alpha_host, const float* alpha_dev, const void* bias, hipStream_t stream);
 int gemm_mx_silu_mul_quantize(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, uint8_t* QACT, uint8_t* SFACT, int64_t M,
                               int64_t N, int64_t Kp, float alpha_host, const float* alpha_dev, const void* bias, int64_t KE, hipStream_t stream);
+// gemm_mx_rw.hip: M <= 64 over the MXFP4 repacked weight (arcq.h "MXFP4 repacked weight"); the sums are gemm_mx's, bit for bit
+int64_t gemm_mx_repacked_w_bytes(int64_t N, int64_t Kp);
+int64_t gemm_mx_repacked_sf_bytes(int64_t N, int64_t Kp);
+int gemm_mx_repacked_supported(int64_t M, int64_t N, int64_t Kp);
+int gemm_mx_repacked(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* D, int64_t M, int64_t N, int64_t Kp,
+                     float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, hipStream_t stream);
+int gemm_mx_repacked_silu_mul(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* ACT, int64_t M, int64_t N,
+                              int64_t Kp, float alpha_host, const float* alpha_dev, const void* bias, hipStream_t stream);
 
 // gemm_skinny.hip / gemm_tile.hip
 struct GemmArgs {

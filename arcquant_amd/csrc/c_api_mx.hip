@@ -66,4 +66,35 @@ int arcq_gemm_mxfp4_silu_mul_quantize(const uint8_t* A, const uint8_t* B, const 
   return gemm_mx_silu_mul_quantize(A, B, SFA, SFB, QACT, SFACT, M, N, K, alpha_host, alpha_dev, bias, KE, (hipStream_t)stream);
 }
 
+int64_t arcq_mx_repacked_w_bytes(int64_t N, int64_t K) { return gemm_mx_repacked_w_bytes(N, K); }
+int64_t arcq_mx_repacked_sf_bytes(int64_t N, int64_t K) { return gemm_mx_repacked_sf_bytes(N, K); }
+int arcq_gemm_mxfp4_repacked_supported(int64_t M, int64_t N, int64_t K) { return gemm_mx_repacked_supported(M, N, K); }
+
+// M beyond the decode kernel is reported once the divisibility rules hold, ahead of out_dtype; everything else is gemm_checks' order
+static int mx_repacked_max_m(const GemmRule& r, int64_t M, int64_t N, int64_t K) {
+  if (M > r.max_m && N >= 0 && K > 0 && (K % r.k_mult) == 0 && (N % r.n_mult) == 0)
+    return fail(ARCQ_ERR_SHAPE, "%s: need M <= %lld over the repacked weight (M=%lld)", r.who, (long long)r.max_m, (long long)M);
+  return ARCQ_OK;
+}
+
+int arcq_gemm_mxfp4_repacked(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* D, int64_t M, int64_t N, int64_t K,
+                             float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* stream) {
+  GemmRule r{"arcq_gemm_mxfp4_repacked"};
+  r.k_mult = 128; r.n_mult = 16; r.max_m = 64; r.epi_align = 2; r.b = "MRW"; r.sfb = "MRSF";
+  if (int rc = mx_repacked_max_m(r, M, N, K)) return rc;
+  const int rc = gemm_checks(r, A, MRW, SFA, MRSF, D, nullptr, M, N, K, bias, residual, out_dtype);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_repacked(A, MRW, SFA, MRSF, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, (hipStream_t)stream);
+}
+
+int arcq_gemm_mxfp4_repacked_silu_mul(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* ACT, int64_t M, int64_t N,
+                                      int64_t K, float alpha_host, const float* alpha_dev, const void* bias, void* stream) {
+  GemmRule r{"arcq_gemm_mxfp4_repacked_silu_mul"};
+  r.k_mult = 128; r.n_mult = 16; r.max_m = 64; r.epi_align = 2; r.b = "MRW"; r.sfb = "MRSF"; r.d = "ACT";
+  if (int rc = mx_repacked_max_m(r, M, N, K)) return rc;
+  const int rc = gemm_checks(r, A, MRW, SFA, MRSF, ACT, nullptr, M, N, K, bias, nullptr, ARCQ_OUT_BF16);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_repacked_silu_mul(A, MRW, SFA, MRSF, ACT, M, N, K, alpha_host, alpha_dev, bias, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -70,7 +70,7 @@ class QLinear:
         self.bias = (torch.randn(out_f, generator=gen, device=device, dtype=torch.float32) * 0.02).to(torch.bfloat16) if bias else None
         self.idx = torch.arange(in_f, dtype=torch.int16, device=device)
         self.in_f, self.out_f, self.KE = in_f, out_f, select_num
-        self.RW = self.RSF = None
+        self.RW = self.RSF = self.MRW = self.MRSF = None
         self.quant_type = quant_type
         if quant_type == "MXFP4":            # codes [out_f, Kp/2] + E8M0 bytes [out_f, Kp/32]; no per-tensor scale: alpha = 1
             self.W, self.SFW = agemm.mx_reorder_quantize_w(w, self.idx, select_num)
@@ -88,10 +88,16 @@ class QLinear:
         if release_reference:
             self.W = self.SFW = None
 
+    def mx_repack(self):
+        """Second copy of an MXFP4 weight in MFMA operand order for calls of at most agemm.MX_REPACKED_MAX_M tokens (agemm.mx_repack_w)."""
+        self.MRW, self.MRSF = agemm.mx_repack_w(self.W, self.SFW)
+
     def matmul(self, A, SFA, scale, ops=agemm, **kw):
         """GEMM against this weight (+ its bias, in the epilogue): the repacked kernel for decode-sized token counts where available.
         ``ops``: the module whose ``matmul_repacked`` / ``matmul_rw`` is called (the ctypes mirror or the extension module)."""
         kw.setdefault("bias", self.bias)
+        if self.MRW is not None and A.shape[0] <= agemm.MX_REPACKED_MAX_M:
+            return agemm.mx_matmul_repacked(A, self.MRW, SFA, self.MRSF, scale, self.out_f, **kw)
         if self.quant_type == "MXFP4":
             return agemm.mx_matmul(A, self.W, SFA, self.SFW, scale, **kw)
         if self.W is None:           # repacked only: one copy for every M (the repacked kernels where matmul_repacked would run)
@@ -101,7 +107,7 @@ class QLinear:
         return agemm.matmul(A, self.W, SFA, self.SFW, scale, **kw)
 
     def bytes(self):
-        if self.quant_type == "MXFP4":   # Kp/2 code bytes + Kp/32 scale bytes per row
+        if self.quant_type == "MXFP4":   # Kp/2 code bytes + Kp/32 scale bytes per row (a decode step reads one copy, whichever it is)
             return self.W.numel() + self.SFW.numel()
         if self.W is None:           # repacked only: the padded RW / RSF it holds
             return self.RW.numel() + self.RSF.numel()
@@ -124,13 +130,17 @@ class DecoderModel:
 
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
                  repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False, kv_cache: str = "bf16",
-                 kv_fused_step: bool = False, kv_paged_prefill: bool = False, rope: bool = False, rope_theta: float = 1e6, rope_tables=None):
+                 kv_fused_step: bool = False, kv_paged_prefill: bool = False, mx_repacked_decode: bool = False, rope: bool = False,
+                 rope_theta: float = 1e6, rope_tables=None):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
         the repack and every GEMM the repacked kernels do not serve runs through agemm.matmul_rw / matmul_rw_silu_mul.
         mx_quantised_epilogue (quant_type="MXFP4", fused=True only): the gate|up GEMM writes the down projection's quantised input itself
         (mx.matmul_silu_mul_quantize) instead of mx.matmul_silu_mul + mx_reorder_quantize_x, prefill and decode alike; same logits.
+        mx_repacked_decode (quant_type="MXFP4", fused=True only, not with mx_quantised_epilogue): every linear additionally keeps its weight
+        as agemm.mx_repack_w lays it out; calls of at most agemm.MX_REPACKED_MAX_M tokens run q|k|v, o, gate|up and down through
+        agemm.mx_matmul_repacked / mx.matmul_silu_mul_repacked.  Same logits, bit for bit.
         kv_cache="int4" (attention="cache", head dimension 128): the reference's int4 paged cache (arcquant_amd.kvcache)
         instead of the dense bf16 one -- a prefill writes its k / v through init_kv_quantize_i4, a decode step appends with
         append_kv_quantize_i4 and attends with batch_decode_i4.  "bf16" (default) is the dense cache.
@@ -168,8 +178,12 @@ class DecoderModel:
         if mx_quantised_epilogue and (quant_type != "MXFP4" or not fused):
             raise ValueError("DecoderModel: mx_quantised_epilogue needs quant_type='MXFP4' and fused=True (NVFP4's per-tensor scale needs the "
                              "whole activation first; the unfused model is the reference's call structure)")
+        if mx_repacked_decode and (quant_type != "MXFP4" or not fused or mx_quantised_epilogue):
+            raise ValueError("DecoderModel: mx_repacked_decode needs quant_type='MXFP4' and fused=True, and has no form of the quantising "
+                             "epilogue (mx_quantised_epilogue)")
         self.quant_type = quant_type
         self.mx_quantised_epilogue = mx_quantised_epilogue
+        self.mx_repacked_decode = mx_repacked_decode
         self.cfg, self.device, self.batch, self.max_len, self.fused = cfg, device, batch, max_len, fused
         self.repacked_only = repacked_only
         self.attention = attention
@@ -212,6 +226,10 @@ class DecoderModel:
             for L in self.layers:
                 for name in ("qkv", "o", "gateup", "down"):
                     L[name].repack(release_reference=repacked_only)
+        if mx_repacked_decode:
+            for L in self.layers:
+                for name in ("qkv", "o", "gateup", "down"):
+                    L[name].mx_repack()
         self.idx_h = torch.arange(h, dtype=torch.int16, device=device)
         self.idx_i = torch.arange(it, dtype=torch.int16, device=device)
         self.inv_idx_i = torch.argsort(self.idx_i.long()).to(torch.int16)     # act_scatter_index of the gate|up epilogue
@@ -362,7 +380,8 @@ class DecoderModel:
             mx.rmsnorm_quantize_x -> q|k|v mx_matmul (+bias) -> attention -> mx_reorder_quantize_x -> o mx_matmul (+bias, +residual)
             mx.rmsnorm_quantize_x -> mx.matmul_silu_mul (+bias) -> mx_reorder_quantize_x -> down mx_matmul (+bias, +residual)
         (a decode step may take mx_matmul + mx.silu_mul_quantize_x instead of the middle two: mx_decode_route; with
-        mx_quantised_epilogue the middle two are mx.matmul_silu_mul_quantize at every T -- idx_i is the identity); fused=False, the
+        mx_quantised_epilogue the middle two are mx.matmul_silu_mul_quantize at every T -- idx_i is the identity; with mx_repacked_decode a
+        call of at most agemm.MX_REPACKED_MAX_M tokens takes every GEMM over the repacked weight); fused=False, the
         reference's call structure (model/qQwenLayer.py): separate q, k, v and gate, up GEMMs, bias / SiLU*up / residual as torch ops.
         Every activation quantiser is one launch either way -- MXFP4 has no per-tensor scale to find first."""
         cfg = self.cfg
@@ -388,6 +407,9 @@ class DecoderModel:
                     qa, sfa = mx.matmul_silu_mul_quantize(A, Gt.W, SFA, Gt.SFW, 1.0, ke, bias=Gt.bias)
                 elif T <= 64 and self.mx_decode_route == "quantiser":
                     qa, sfa = mx.silu_mul_quantize_x(Gt.matmul(A, SFA, 1.0), self.idx_i, ke, layout=agemm.GU_PAIRS)
+                elif Gt.MRW is not None and T <= agemm.MX_REPACKED_MAX_M:
+                    act = mx.matmul_silu_mul_repacked(A, Gt.MRW, SFA, Gt.MRSF, 1.0, Gt.out_f, bias=Gt.bias)
+                    qa, sfa = agemm.mx_reorder_quantize_x(act, self.idx_i, ke)
                 else:
                     act = mx.matmul_silu_mul(A, Gt.W, SFA, Gt.SFW, 1.0, bias=Gt.bias)
                     qa, sfa = agemm.mx_reorder_quantize_x(act, self.idx_i, ke)
@@ -532,7 +554,7 @@ class DecoderModel:
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
                  attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False, kv_cache="bf16",
-                 kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6):
+                 kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6, mx_repacked_decode=False):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
     weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
@@ -543,7 +565,7 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         mem0 = torch.cuda.memory_allocated(device)
         model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
                              quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
-                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta)
+                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mx_repacked_decode)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -602,6 +624,8 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         res["quant_type"] = quant_type
     if mx_quantised_epilogue:
         res["mx_quantised_epilogue"] = True
+    if mx_repacked_decode:
+        res["mx_repacked_decode"] = True
     if kv_cache != "bf16":
         res["kv_cache"] = kv_cache
     if kv_fused_step:
@@ -615,7 +639,7 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
                    fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False,
-                   kv_cache="bf16", kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6):
+                   kv_cache="bf16", kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6, mx_repacked_decode=False):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -646,7 +670,7 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
     with torch.no_grad():
         model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
                              quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
-                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta)
+                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mx_repacked_decode)
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -689,6 +713,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         res["quant_type"] = quant_type
     if mx_quantised_epilogue:
         res["mx_quantised_epilogue"] = True
+    if mx_repacked_decode:
+        res["mx_repacked_decode"] = True
     if kv_cache != "bf16":
         res["kv_cache"] = kv_cache
     if kv_fused_step:
@@ -861,15 +887,18 @@ if __name__ == "__main__":
     qe = "--mx-quantised-epilogue" in sys.argv   # MXFP4, the fused model only: the gate|up GEMM quantises the down projection's input
     if qe and qt != "MXFP4":
         sys.exit("--mx-quantised-epilogue needs --quant-type MXFP4")
+    mrd = "--mx-repacked-decode" in sys.argv     # MXFP4, the fused model only: decode GEMMs over the repacked weight (agemm.mx_repack_w)
+    if mrd and (qt != "MXFP4" or qe):
+        sys.exit("--mx-repacked-decode needs --quant-type MXFP4 and excludes --mx-quantised-epilogue")
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
             print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
-                                            kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta)), flush=True)
+                                            kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mrd)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
-            if ((ro or qe) and not fused) or (kvc == "int4" and att != "cache"):
+            if ((ro or qe or mrd) and not fused) or (kvc == "int4" and att != "cache"):
                 continue
             print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
-                                          kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta)), flush=True)
+                                          kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mrd)), flush=True)
             torch.cuda.empty_cache()

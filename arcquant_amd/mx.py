@@ -2,13 +2,17 @@
 quantisers and the gate|up GEMM with SiLU*up in its epilogue -- what ``agemm.rmsnorm_quantize_x``, ``silu_mul_quantize_x_dynamic`` and
 ``matmul_silu_mul`` are to NVFP4.  MXFP4 has no per-tensor scale, so each operator is ONE launch and returns no scale and no abs-max
 slots.  ``matmul_silu_mul_quantize`` ends the family: the gate|up GEMM that writes the down projection's quantised input itself, which
-NVFP4's per-tensor scale rules out (``gate_up_rows`` lays the weight out for it).
+NVFP4's per-tensor scale rules out (``gate_up_rows`` lays the weight out for it).  The decode path over a weight repacked into MFMA
+operand order is here too: ``mx_repack_w`` / ``mx_unrepack_w``, ``mx_matmul_repacked`` and ``matmul_silu_mul_repacked`` (1 <= M <= 64, bit
+for bit the results of ``mx_matmul`` / ``matmul_silu_mul``).
 
 The plain MXFP4 quantisers and GEMM stay in ``agemm`` (``mx_reorder_quantize_{x,w}``, ``mx_matmul``).  This module is a ctypes mirror
 only: the extension module ``agemm.so`` does not bind these operators.  Validation follows the mirror's order (``agemm._need`` ...):
 dtype / rank / contiguity, then the size relations, then the optional tensors, and LAST where everything lives.
 """
 from __future__ import annotations
+
+import functools
 
 import torch
 
@@ -92,6 +96,122 @@ def matmul_silu_mul(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: to
         st = _lib.lib().arcq_gemm_mxfp4_silu_mul(A.data_ptr(), B.data_ptr(), SFA.data_ptr(), SFB.data_ptr(), out.data_ptr(), M, N, K, alpha_host,
                                                  alpha_p, bias_p, _stream(A))
     _lib.check(st, "mx.matmul_silu_mul")
+    return out
+
+
+# ---- the MXFP4 repacked weight (include/arcq.h "MXFP4 repacked weight") and the decode GEMMs over it; also reachable as
+# agemm.mx_repack_w, agemm.mx_unrepack_w, agemm.mx_repacked_supported, agemm.mx_matmul_repacked and agemm.MX_REPACKED_MAX_M.
+# Layers and the harness take the repacked GEMMs for calls of at most MX_REPACKED_MAX_M tokens and ``mx_matmul`` above.  It is the
+# kernel's own limit (arcq_gemm_mxfp4_repacked_supported): measured against ``mx_matmul`` the repacked kernel is ahead at every M up to
+# 64 (profiles/mxfp4_repacked_decode.json), so nothing lowers it.
+MX_REPACKED_MAX_M = 64
+_MX_ROUND = 32          # K steps of one MRSF round: 8 waves x the 4 bytes of a dword
+_MX_SF_PAD = 127        # padding bytes of a partial MRSF round: E8M0 2^0 (never multiplied)
+
+
+@functools.lru_cache(maxsize=None)
+def _mx_repacked_bytes(N: int, K: int):
+    L = _lib.lib()
+    return int(L.arcq_mx_repacked_w_bytes(N, K)), int(L.arcq_mx_repacked_sf_bytes(N, K))
+
+
+def mx_repack_w(QW: torch.Tensor, SFW: torch.Tensor):
+    """One-time re-layout of an MXFP4 weight for the decode path (include/arcq.h, "MXFP4 repacked weight"): returns ``(MRW, MRSF)``.
+    Pure data movement with torch ops -- the codes and E8M0 bytes are those ``mx_reorder_quantize_w`` wrote:
+    MRW  = [row blocks of 16][steps of 128 K][lane = 16*q + r][16 bytes], as many bytes as QW;
+    MRSF = [row blocks][rounds of 32 steps][wave = t % 8][lane][u = (t / 8) % 4], the steps of a partial last round padded with 127.
+    ``mx_unrepack_w`` is its inverse; both also run on CPU tensors.  N % 16 == 0, K % 128 == 0 (K is the stored Kp)."""
+    _need(QW, torch.uint8, "QW", 2)            # (pure data movement: no device rule)
+    _need(SFW, torch.uint8, "SFW", 2)
+    N, K = QW.shape[0], QW.shape[1] * 2
+    if N == 0 or K == 0 or N % 16 or K % 128:
+        raise RuntimeError(f"Value error in mx_repack_w: N={N} must be a multiple of 16 and K={K} a multiple of 128")
+    if tuple(SFW.shape) != (N, K // 32):
+        raise RuntimeError(f"Value error in mx_repack_w: SFW must be [{N}, {K // 32}]")
+    RB, T = N // 16, K // 128
+    R = (T + _MX_ROUND - 1) // _MX_ROUND
+    # codes: [RB, r, T, q, 16 B] -> [RB, T, q, r, 16 B]
+    MRW = QW.view(RB, 16, T, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+    # scales: step t = 32 round + 8 u + wave; [RB, r, round, u, wave, q] -> [RB, round, wave, q, r, u]
+    sf = torch.full((RB, 16, R * _MX_ROUND, 4), _MX_SF_PAD, dtype=torch.uint8, device=QW.device)
+    sf[:, :, :T] = SFW.view(RB, 16, T, 4)
+    MRSF = sf.view(RB, 16, R, 4, 8, 4).permute(0, 2, 4, 5, 1, 3).contiguous().view(-1)
+    assert (MRW.numel(), MRSF.numel()) == _mx_repacked_bytes(N, K)
+    return MRW, MRSF
+
+
+def mx_unrepack_w(MRW: torch.Tensor, MRSF: torch.Tensor, N: int, K: int):
+    """The exact inverse of ``mx_repack_w`` (pure data movement with torch ops, on MRW's device): returns ``(QW u8 [N, K/2], SFW u8
+    [N, K/32])`` as ``mx_reorder_quantize_w`` wrote them; the padding bytes of MRSF are dropped."""
+    _need(MRW, torch.uint8, "MRW", 1)
+    _need(MRSF, torch.uint8, "MRSF", 1)
+    N, K = int(N), int(K)
+    if N <= 0 or K <= 0 or N % 16 or K % 128 or (MRW.numel(), MRSF.numel()) != _mx_repacked_bytes(N, K):
+        raise RuntimeError(f"Value error in mx_unrepack_w: MRW / MRSF do not belong to a [{N}, {K}] MXFP4 weight (N % 16 == 0, K % 128 == 0)")
+    RB, T = N // 16, K // 128
+    R = (T + _MX_ROUND - 1) // _MX_ROUND
+    QW = MRW.view(RB, T, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(N, K // 2)
+    sf = MRSF.view(RB, R, 8, 4, 16, 4).permute(0, 4, 1, 5, 2, 3).reshape(RB, 16, R * _MX_ROUND, 4)
+    return QW, sf[:, :, :T].reshape(N, K // 32)
+
+
+@functools.lru_cache(maxsize=None)
+def mx_repacked_supported(M: int, N: int, K: int) -> bool:
+    """Whether ``mx_matmul_repacked`` can run this shape: 1 <= M <= 64, N % 16 == 0, K % 128 == 0."""
+    return bool(_lib.lib().arcq_gemm_mxfp4_repacked_supported(int(M), int(N), int(K)))
+
+
+def _need_mx_repacked(A, MRW, SFA, MRSF, N, who):
+    # A / SFA are the activations of an [M, K] call, (MRW, MRSF) the repacked MXFP4 weight of N rows over this K -> (M, N, K)
+    _need(A, torch.uint8, "A", 2)
+    _need(MRW, torch.uint8, "MRW", 1)
+    _need(SFA, torch.uint8, "SFA", 2)
+    _need(MRSF, torch.uint8, "MRSF", 1)
+    M, K, N = A.shape[0], A.shape[1] * 2, int(N)
+    if K % 128:
+        raise RuntimeError(f"{who}: K={K} is not a padded MXFP4 K (a multiple of 128)")
+    if N <= 0 or N % 16:
+        raise RuntimeError(f"{who}: N={N} must be a positive multiple of 16")
+    if (MRW.numel(), MRSF.numel()) != _mx_repacked_bytes(N, K):
+        raise RuntimeError(f"{who}: MRW / MRSF do not belong to a [{N}, {K}] MXFP4 weight")
+    if tuple(SFA.shape) != (M, K // 32):
+        raise RuntimeError(f"{who}: SFA must be [rows, K/32]")
+    if not mx_repacked_supported(M, N, K):
+        raise RuntimeError(f"{who}: M={M} is outside the repacked path (1 <= M <= {MX_REPACKED_MAX_M}; see mx_repacked_supported)")
+    return M, N, K
+
+
+def mx_matmul_repacked(A: torch.Tensor, MRW: torch.Tensor, SFA: torch.Tensor, MRSF: torch.Tensor, scale, N: int, *, bias=None, residual=None,
+                       out_dtype=torch.bfloat16, out=None, scale_host: float = 1.0):
+    """``mx_matmul`` for decode shapes (1 <= M <= 64) over a weight prepared by ``mx_repack_w`` (same arguments otherwise, plus the row
+    count ``N`` of the weight): every weight load is one contiguous span and the weight is read once whatever M is.  Bit for bit the
+    result of ``mx_matmul`` on the un-repacked operands (the same sums in the same order)."""
+    M, N, K = _need_mx_repacked(A, MRW, SFA, MRSF, N, "mx.mx_matmul_repacked")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, A, "mx.mx_matmul_repacked")
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device("mx.mx_matmul_repacked", A, MRW, SFA, MRSF, alpha_dev, out, bias, residual)
+    with _on(A.device):
+        st = _lib.lib().arcq_gemm_mxfp4_repacked(A.data_ptr(), MRW.data_ptr(), SFA.data_ptr(), MRSF.data_ptr(), out.data_ptr(), M, N, K,
+                                                 alpha_host, alpha_p, bias_p, residual_p, oc, _stream(A))
+    _lib.check(st, "mx.mx_matmul_repacked")
+    return out
+
+
+def matmul_silu_mul_repacked(A: torch.Tensor, MRW: torch.Tensor, SFA: torch.Tensor, MRSF: torch.Tensor, scale, N: int, *, scale_host: float = 1.0,
+                             bias=None, out=None):
+    """``matmul_silu_mul`` for decode shapes (1 <= M <= 64) over the gate|up weight as ``agemm.mx_repack_w`` left it (rows interleaving
+    gate and up; ``N`` is its row count).  Returns ``act`` bf16 [M, N/2], bit for bit what ``matmul_silu_mul`` returns on the
+    un-repacked weight."""
+    M, N, K = _need_mx_repacked(A, MRW, SFA, MRSF, N, "mx.matmul_silu_mul_repacked")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, _ = _out(out, M, N // 2, torch.bfloat16, A, "mx.matmul_silu_mul_repacked")
+    bias_p = _opt(bias, torch.bfloat16, "bias", (N,))
+    _same_device("mx.matmul_silu_mul_repacked", A, MRW, SFA, MRSF, alpha_dev, out, bias)
+    with _on(A.device):
+        st = _lib.lib().arcq_gemm_mxfp4_repacked_silu_mul(A.data_ptr(), MRW.data_ptr(), SFA.data_ptr(), MRSF.data_ptr(), out.data_ptr(), M, N, K,
+                                                          alpha_host, alpha_p, bias_p, _stream(A))
+    _lib.check(st, "mx.matmul_silu_mul_repacked")
     return out
 
 

@@ -89,18 +89,22 @@ class QLinearLayer(nn.Module):
     """Weight quantised once at construction; forward = ARC-NVFP4 GEMM (+ bias) on pre-quantised activations."""
 
     def __init__(self, originalLayer: nn.Linear, select_num, reorder_index, out_reorder_index=None, quant_type="NVFP4",
-                 repack_for_decode: bool = False, repacked_only: bool = False):
+                 repack_for_decode: bool = False, repacked_only: bool = False, mx_repack_for_decode: bool = False):
         """``repack_for_decode`` (extension, default off = the reference's behaviour and memory): additionally keep the
         weight in MFMA-operand-order tiles (``agemm.repack_w``) and use ``agemm.matmul_repacked`` for calls of at most 16
         tokens.  ``repacked_only`` (extension): keep ONLY that copy -- ``W`` / ``scale_w`` are registered as None, every call
         runs through ``agemm.matmul_rw`` (the same results as ``repack_for_decode``, but the decode shapes ``matmul`` serves with
         an LDS-transposing kernel: there up to fp32 summation order); ``agemm.unrepack_w(RW, RSF, ...)`` rebuilds the
-        reference-layout pair."""
+        reference-layout pair.  ``mx_repack_for_decode`` (extension, quant_type='MXFP4' only): additionally keep the weight as
+        ``agemm.mx_repack_w`` lays it out (``MRW`` / ``MRSF``); calls of at most ``agemm.MX_REPACKED_MAX_M`` tokens run through
+        ``agemm.mx_matmul_repacked``, longer ones through ``agemm.mx_matmul`` -- the same bits either way."""
         super().__init__()
         if quant_type not in ("NVFP4", "MXFP4"):
             raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4 and MXFP4 are)")
         if quant_type == "MXFP4" and (repack_for_decode or repacked_only):
             raise ValueError("repack_for_decode / repacked_only apply to the NVFP4 weight layout only, not to quant_type='MXFP4'")
+        if mx_repack_for_decode and quant_type != "MXFP4":
+            raise ValueError("mx_repack_for_decode applies to quant_type='MXFP4' only (NVFP4 has repack_for_decode / repacked_only)")
         self.in_features = originalLayer.in_features
         self.out_features = originalLayer.out_features
         if originalLayer.bias is not None:
@@ -124,6 +128,9 @@ class QLinearLayer(nn.Module):
         self.register_buffer("scale", scale)
         self.register_buffer("RW", RW)
         self.register_buffer("RSF", RSF)
+        MRW, MRSF = agemm.mx_repack_w(W, scale_w) if mx_repack_for_decode else (None, None)
+        self.register_buffer("MRW", MRW)
+        self.register_buffer("MRSF", MRSF)
 
     @torch.no_grad()
     def forward(self, x):
@@ -131,7 +138,9 @@ class QLinearLayer(nn.Module):
         # `y = matmul(...); y = y + bias` (model/qLinearLayer.py:74-76): the bias add runs in the GEMM epilogue with the same
         # two roundings (the bf16 product, then the bf16 sum), so the result is bit-identical to the two torch steps
         bias = self.bias if self.bias is None or self.bias.dtype == torch.bfloat16 else None
-        if self.quant_type == "MXFP4":
+        if getattr(self, "MRW", None) is not None and qx.shape[0] <= agemm.MX_REPACKED_MAX_M:
+            y = agemm.mx_matmul_repacked(qx, self.MRW, scale_x, self.MRSF, scale * self.scale, self.out_features, bias=bias)
+        elif self.quant_type == "MXFP4":
             y = agemm.mx_matmul(qx, self.W, scale_x, self.scale_w, scale * self.scale, bias=bias)
         elif self.W is None:
             y = agemm.matmul_rw(qx, self.RW, scale_x, self.RSF, scale * self.scale, self.out_features, bias=bias)

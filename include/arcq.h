@@ -336,6 +336,36 @@ int arcq_gemm_mxfp4_silu_mul_quantize(const uint8_t *A, const uint8_t *B, const 
                                       uint8_t *SFACT, int64_t M, int64_t N, int64_t K, float alpha_host, const float *alpha_dev,
                                       const void *bias, int64_t KE, void *stream);
 
+/* ---- MXFP4 repacked weight: decode GEMMs (1 <= M <= 64) over a weight laid out in MFMA operand order --------------------------------
+ * A static MXFP4 weight (QW [N, K/2], SFW [N, K/32] of arcq_mx_quantize_w, K = Kp) can be laid out for the hardware once;
+ * arcquant_amd/agemm.py:mx_repack_w builds both arrays (pure data movement, the same codes and E8M0 bytes), mx_unrepack_w inverts it.
+ * N % 16 == 0, K % 128 == 0.  With row block b = n / 16, r = n % 16, step t = k / 128, q = (k % 128) / 32:
+ *   MRW   [N/16][K/128][64 lanes][16 bytes], no padding, N * K / 2 bytes:
+ *           MRW[((b * (K/128) + t) * 64 + 16*q + r) * 16 + j] = QW[n][64*t + 16*q + j],  j = 0 .. 15
+ *         lane 16*q + r of tile (b, t) holds row 16*b + r, K elements [128*t + 32*q, +32): the B operand of one scaled 16x16x128 MFMA.
+ *   MRSF  [N/16][R][8][64 lanes][4 bytes], R = ceil((K/128) / 32) rounds of 32 steps, (N/16) * R * 2048 bytes:
+ *           MRSF[(((b * R + t/32) * 8 + t%8) * 64 + 16*q + r) * 4 + (t/8)%4] = SFW[n][4*t + q]
+ *         the aligned dword of (round, wave = t % 8, lane) holds that lane's scale byte in the four steps 32*round + 8*u + wave, u = 0 .. 3.
+ *         Bytes of steps t >= K/128 (a partial last round) are PADDING: mx_repack_w writes 127 (E8M0 2^0); no result depends on them
+ *         (a step past K/128 issues no MFMA), they exist so that every dword the kernel fetches lies inside the array.
+ * A / SFA stay in the row-major form the quantisers write.  For every output the sum is arcq_gemm_mxfp4's at M <= 64 (K steps s = w mod 8
+ * accumulated in ascending order per w, the eight partial sums added w = 0 .. 7, then the same epilogue), so the results are BIT FOR BIT
+ * those of arcq_gemm_mxfp4 / arcq_gemm_mxfp4_silu_mul on (QW, SFW).  The weight is read once whatever M is. */
+int64_t arcq_mx_repacked_w_bytes(int64_t N, int64_t K);    /* N * K / 2; 0 unless N % 16 == 0 and K % 128 == 0 (both positive) */
+int64_t arcq_mx_repacked_sf_bytes(int64_t N, int64_t K);   /* (N/16) * ceil(K/4096) * 2048; 0 likewise */
+int arcq_gemm_mxfp4_repacked_supported(int64_t M, int64_t N, int64_t K);   /* 1 <= M <= 64, N % 16 == 0, K % 128 == 0 */
+/* arcq_gemm_mxfp4's contract (alpha, bias, residual -- may alias D --, out_dtype) with B given as (MRW, MRSF); no workspace.
+ *   Status, all before any HIP call and in this order: ARCQ_ERR_SHAPE for M or N < 0, K % 128 or N % 16; ARCQ_ERR_SHAPE for M > 64;
+ *   ARCQ_ERR_SHAPE for a bad out_dtype; M == 0 or N == 0 returns ARCQ_OK; ARCQ_ERR_NULL for a NULL operand; ARCQ_ERR_SHAPE for a
+ *   misaligned pointer (A, MRW, D 16 bytes; SFA, MRSF 4 bytes; bias, residual 2 bytes). */
+int arcq_gemm_mxfp4_repacked(const uint8_t *A, const uint8_t *MRW, const uint8_t *SFA, const uint8_t *MRSF, void *D, int64_t M,
+                             int64_t N, int64_t K, float alpha_host, const float *alpha_dev, const void *bias, const void *residual,
+                             int out_dtype, void *stream);
+/* arcq_gemm_mxfp4_silu_mul over (MRW, MRSF) of a weight whose rows interleave gate and up: ACT = bf16 [M, N/2].  Status as above. */
+int arcq_gemm_mxfp4_repacked_silu_mul(const uint8_t *A, const uint8_t *MRW, const uint8_t *SFA, const uint8_t *MRSF, void *ACT,
+                                      int64_t M, int64_t N, int64_t K, float alpha_host, const float *alpha_dev, const void *bias,
+                                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
