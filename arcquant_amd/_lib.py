@@ -69,6 +69,10 @@ SYMBOLS = {
     "arcq_gemm_mxfp4_repacked_supported": (_i32, [_i64, _i64, _i64]),
     "arcq_gemm_mxfp4_repacked": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p]),
     "arcq_gemm_mxfp4_repacked_silu_mul": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p]),
+    "arcq_gemm_mxfp4_rw_route": (_i32, [_i64, _i64, _i64]),
+    "arcq_gemm_mxfp4_rw": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p]),
+    "arcq_gemm_mxfp4_rw_silu_mul": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p]),
+    "arcq_gemm_mxfp4_rw_silu_mul_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _i64, _p]),
 }
 
 # include/arcq_harness.h: e2e-harness-only entry points (NOT the drop-in boundary)

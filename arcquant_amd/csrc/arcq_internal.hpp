@@ -144,6 +144,16 @@ int gemm_mx_repacked(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, c
                      float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, hipStream_t stream);
 int gemm_mx_repacked_silu_mul(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* ACT, int64_t M, int64_t N,
                               int64_t Kp, float alpha_host, const float* alpha_dev, const void* bias, hipStream_t stream);
+// gemm_mx_tile_rw.hip (M > 64, the tile kernel over MRW / MRSF) and gemm_mx_slice_rw.hip (the quantising kernel for M <= 64): every
+// M >= 1 over the repacked weight alone; the results are gemm_mx's, gemm_mx_silu_mul's and gemm_mx_silu_mul_quantize's, bit for bit
+int gemm_mx_rw_route(int64_t M, int64_t N, int64_t Kp);   // 1: the decode kernels, 2: the tile kernel, 0: no such shape
+int gemm_mx_rw(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* D, int64_t M, int64_t N, int64_t Kp,
+               float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, hipStream_t stream);
+int gemm_mx_rw_silu_mul(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* ACT, int64_t M, int64_t N, int64_t Kp,
+                        float alpha_host, const float* alpha_dev, const void* bias, hipStream_t stream);
+int gemm_mx_rw_silu_mul_quantize(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, uint8_t* QACT, uint8_t* SFACT,
+                                 int64_t M, int64_t N, int64_t Kp, float alpha_host, const float* alpha_dev, const void* bias, int64_t KE,
+                                 hipStream_t stream);
 
 // gemm_skinny.hip / gemm_tile.hip
 struct GemmArgs {

@@ -97,4 +97,38 @@ int arcq_gemm_mxfp4_repacked_silu_mul(const uint8_t* A, const uint8_t* MRW, cons
   return gemm_mx_repacked_silu_mul(A, MRW, SFA, MRSF, ACT, M, N, K, alpha_host, alpha_dev, bias, (hipStream_t)stream);
 }
 
+// ---- every M over the repacked weight alone: the namesakes' rules and order, the weight operands named MRW / MRSF
+int arcq_gemm_mxfp4_rw_route(int64_t M, int64_t N, int64_t K) { return gemm_mx_rw_route(M, N, K); }
+
+int arcq_gemm_mxfp4_rw(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* D, int64_t M, int64_t N, int64_t K,
+                       float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* stream) {
+  GemmRule r{"arcq_gemm_mxfp4_rw"};
+  r.k_mult = 128; r.n_mult = 16; r.max_m = (int64_t)65535 * 128; r.epi_align = 2; r.b = "MRW"; r.sfb = "MRSF";
+  const int rc = gemm_checks(r, A, MRW, SFA, MRSF, D, nullptr, M, N, K, bias, residual, out_dtype);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_rw(A, MRW, SFA, MRSF, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, (hipStream_t)stream);
+}
+
+int arcq_gemm_mxfp4_rw_silu_mul(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* ACT, int64_t M, int64_t N,
+                                int64_t K, float alpha_host, const float* alpha_dev, const void* bias, void* stream) {
+  GemmRule r{"arcq_gemm_mxfp4_rw_silu_mul"};
+  r.k_mult = 128; r.n_mult = 16; r.max_m = (int64_t)65535 * 128; r.epi_align = 2; r.b = "MRW"; r.sfb = "MRSF"; r.d = "ACT";
+  const int rc = gemm_checks(r, A, MRW, SFA, MRSF, ACT, nullptr, M, N, K, bias, nullptr, ARCQ_OUT_BF16);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_rw_silu_mul(A, MRW, SFA, MRSF, ACT, M, N, K, alpha_host, alpha_dev, bias, (hipStream_t)stream);
+}
+
+int arcq_gemm_mxfp4_rw_silu_mul_quantize(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, uint8_t* QACT, uint8_t* SFACT,
+                                         int64_t M, int64_t N, int64_t K, float alpha_host, const float* alpha_dev, const void* bias, int64_t KE,
+                                         void* stream) {
+  GemmRule r{"arcq_gemm_mxfp4_rw_silu_mul_quantize"};
+  r.k_mult = 128; r.n_mult = 128; r.max_m = (int64_t)65535 * 128; r.epi_align = 2; r.b = "MRW"; r.sfb = "MRSF"; r.d = "QACT";
+  // the KE rule and the NULL SFACT: where arcq_gemm_mxfp4_silu_mul_quantize reports them
+  if (N >= 0 && (N % 128 == 0) && (KE < 0 || (KE % 64) || KE > N / 2 || N / 2 > 32767))
+    return fail(ARCQ_ERR_SHAPE, "%s: need KE %% 64 == 0 and 0 <= KE <= N/2 <= 32767 (N=%lld KE=%lld)", r.who, (long long)N, (long long)KE);
+  const int rc = gemm_checks(r, A, MRW, SFA, MRSF, SFACT ? QACT : nullptr, nullptr, M, N, K, bias, nullptr, ARCQ_OUT_BF16);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_rw_silu_mul_quantize(A, MRW, SFA, MRSF, QACT, SFACT, M, N, K, alpha_host, alpha_dev, bias, KE, (hipStream_t)stream);
+}
+
 }  // extern "C"

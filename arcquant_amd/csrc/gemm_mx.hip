@@ -35,187 +35,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gemm_mx_common.hpp"
-#include "quantize_mx_device.hpp"
+#include "gemm_mx_tile_common.hpp"
 
 namespace arcq {
 
-// One (row, block) of the quantised activation: the block's 32 bf16 activations at `src` (LDS, 16-byte aligned) -> codes and scale byte at
-// block b of row m, the residual block when b is in the outlier tail, and, from the owner of the row's last block, the padding blocks.
-__device__ __forceinline__ void mx_quantize_act_block(const MxArgs& p, const uint8_t* src, int m, int b) {
-  const int KQ2 = p.N >> 1, K2 = KQ2 + p.KE, Kp2 = (K2 + 127) & ~127;
-  const int B = KQ2 >> 5, P = (KQ2 - p.KE) >> 5, Bp = Kp2 >> 5;
-  float v[32];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const uint4 u = *reinterpret_cast<const uint4*>(src + c * 16);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      v[8 * c + 2 * d] = bf16_bits_to_f32(w[d] & 0xffffu);
-      v[8 * c + 2 * d + 1] = bf16_bits_to_f32(w[d] >> 16);
-    }
-  }
-  uint8_t* qrow = p.QACT + (size_t)m * (size_t)(Kp2 >> 1);
-  uint8_t* srow = p.SFACT + (size_t)m * (size_t)Bp;
-  mx_store_x_block(qrow, srow, b, B + (b - P), b >= P, v);
-  if (b == B - 1)
-    for (int pb = K2 >> 5; pb < Bp; ++pb) {         // [K2, Kp2): code 0, scale 2^0 (K2 % 64 == 0: none or two blocks)
-      *reinterpret_cast<uint4*>(qrow + (size_t)pb * 16) = make_uint4(0, 0, 0, 0);
-      srow[pb] = 127;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------- tiled
-constexpr int kMxTile = 128;
-constexpr int kMxOpBytes = kMxTile * 64;                     // one operand tile of one K step: 128 rows x 64 bytes
-constexpr int kMxBufBytes = 2 * kMxOpBytes + 2 * kMxTile * 4;   // A, B, then one scale dword per row of A and of B
-// kEpiSiluMulQuant: the tile's 128 x 64 bf16 activations in the staging buffers, rows of 128 bytes padded to 144 (unpadded, the 16
-// lanes of a ds_read_b128 group -- 8 rows x 2 blocks -- would all start on banks 0 and 16; 36 r + 16 b mod 64 spreads them to 2-way at
-// worst, on four reads per thread)
-constexpr int kMxActRowBytes = 64 * 2 + 16;
-static_assert(kMxTile * kMxActRowBytes <= 2 * kMxBufBytes, "the activation image reuses the staging buffers");
-
-// LDS byte offset of 16-byte chunk c (0..3) of staged row r.  The chunk index is XORed with (r >> 2) & 3: the 16 lanes of each
-// ds_read_b128 lane group read 16 different rows at one logical chunk; rows equal mod 4 would share banks in a plain 64-byte
-// layout, the swizzle gives them four different chunks (conflict-free, and no padding: 4 workgroups fit a CU's LDS).
-__device__ __forceinline__ int mx_lds_off(int r, int c) { return r * 64 + ((c ^ (r >> 2)) & 3) * 16; }
-
+// (geometry, LDS image and mx_quantize_act_block: gemm_mx_tile_common.hpp; the statements: gemm_mx_tile_body.inc, shared with
+// gemm_mx_tile_rw.hip, which stages B from the repacked weight)
 template <int kEpi>
 __global__ __launch_bounds__(256) void mx_tile_kernel(MxArgs p) {
-  __shared__ __attribute__((aligned(16))) uint8_t lds[2 * kMxBufBytes];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int m0 = blockIdx.y * kMxTile, n0 = blockIdx.x * kMxTile;
-  const size_t rowb = (size_t)(p.Kp >> 1), rows = (size_t)(p.Kp >> 5);
-  const int steps = p.Kp >> 7;
-
-  // staging: thread t moves 16-byte chunks t and t + 256 of each operand tile (row = chunk / 4) and one scale dword
-  const int cr = tid >> 2, cc = tid & 3;
-  const uint8_t* gA0 = p.A + (size_t)min(m0 + cr, p.M - 1) * rowb + cc * 16;
-  const uint8_t* gA1 = p.A + (size_t)min(m0 + cr + 64, p.M - 1) * rowb + cc * 16;
-  const uint8_t* gB0 = p.B + (size_t)min(n0 + cr, p.N - 1) * rowb + cc * 16;
-  const uint8_t* gB1 = p.B + (size_t)min(n0 + cr + 64, p.N - 1) * rowb + cc * 16;
-  const uint8_t* gS = tid < kMxTile ? p.SFA + (size_t)min(m0 + tid, p.M - 1) * rows
-                                    : p.SFB + (size_t)min(n0 + tid - kMxTile, p.N - 1) * rows;
-  const int l0 = mx_lds_off(cr, cc), l1 = mx_lds_off(cr + 64, cc);
-  // the load of a step past the end re-reads the last step (stashed where nothing reads it): no branch around the loads
-  uint4 ra0, ra1, rb0, rb1;
-  uint32_t rs;
-  auto load = [&](int s) __attribute__((always_inline)) {
-    const size_t o = (size_t)min(s, steps - 1) * 64;
-    ra0 = *reinterpret_cast<const uint4*>(gA0 + o);
-    ra1 = *reinterpret_cast<const uint4*>(gA1 + o);
-    rb0 = *reinterpret_cast<const uint4*>(gB0 + o);
-    rb1 = *reinterpret_cast<const uint4*>(gB1 + o);
-    rs = *reinterpret_cast<const uint32_t*>(gS + o / 16);
-  };
-  auto stash = [&](int buf) __attribute__((always_inline)) {
-    uint8_t* L = lds + buf * kMxBufBytes;
-    *reinterpret_cast<uint4*>(L + l0) = ra0;
-    *reinterpret_cast<uint4*>(L + l1) = ra1;
-    *reinterpret_cast<uint4*>(L + kMxOpBytes + l0) = rb0;
-    *reinterpret_cast<uint4*>(L + kMxOpBytes + l1) = rb1;
-    reinterpret_cast<uint32_t*>(L + 2 * kMxOpBytes)[tid] = rs;
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-  const int r32 = lane & 31, h = lane >> 5;
-  auto compute = [&](int buf) __attribute__((always_inline)) {
-    const uint8_t* L = lds + buf * kMxBufBytes;
-    const uint32_t* LS = reinterpret_cast<const uint32_t*>(L + 2 * kMxOpBytes);
-    uint32_t sa[2], sb[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      sa[i] = LS[wm * 64 + i * 32 + r32];
-      sb[i] = LS[kMxTile + wn * 64 + i * 32 + r32];
-    }
-#pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {            // two K-64 halves of the step: logical chunk 2 sub + h of each row
-      const int sh = 8 * (2 * sub + h);
-      i32x8 a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        a[i] = frag(*reinterpret_cast<const uint4*>(L + mx_lds_off(wm * 64 + i * 32 + r32, 2 * sub + h)));
-        b[i] = frag(*reinterpret_cast<const uint4*>(L + kMxOpBytes + mx_lds_off(wn * 64 + i * 32 + r32, 2 * sub + h)));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[i], b[j], acc[i][j], 4, 4, 0, (int)(sa[i] >> sh), 0,
-                                                                      (int)(sb[j] >> sh));
-    }
-  };
-
-  // the loads of step s + 1 are issued before step s computes and stored to the other LDS buffer after it.  The scheduling
-  // barriers pin that order: left to itself the compiler hoists the LDS stores above the MFMAs (or sinks the loads below
-  // them), and every step then waits out the full global latency.
-  load(0);
-  stash(0);
-  __syncthreads();
-  for (int s = 0; s < steps; ++s) {
-    load(s + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    compute(s & 1);
-    __builtin_amdgcn_sched_barrier(0);
-    stash((s + 1) & 1);
-    __syncthreads();
-  }
-
-  const float alpha = p.alpha_host * (p.alpha_dev ? *p.alpha_dev : 1.0f);
-  if constexpr (kEpi == kEpiSiluMulQuant) {
-    // every wave is past its last read of the staging buffers (the barrier that ends the K loop); N % 128 == 0: no column is outside
-    const bool odd = lane & 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int nl = wn * 64 + j * 32 + r32;                 // y-column within the tile
-        const float bias = p.bias ? bf16_bits_to_f32(p.bias[n0 + nl]) : 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const uint32_t pk = mx_silu_pair(mx_y_bits(alpha, acc[i][j][r], p.bias, bias), mx_y_bits(alpha, acc[i][j][r + 1], p.bias, bias), odd);
-          const int ml = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h + (odd ? 1 : 0);
-          if (!(lane & 2)) *reinterpret_cast<uint32_t*>(lds + ml * kMxActRowBytes + (nl >> 1) * 2) = pk;   // rows >= M hold clamped rows' values
-        }
-      }
-    __syncthreads();
-    const int ml = tid >> 1, bl = tid & 1;                     // thread -> (row, block): a lane pair stores 32 adjacent code bytes
-    if (m0 + ml < p.M) mx_quantize_act_block(p, lds + ml * kMxActRowBytes + bl * 64, m0 + ml, (n0 >> 6) + bl);
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn * 64 + j * 32 + r32;
-      if (n >= p.N) continue;
-      if constexpr (kEpi == kEpiSiluMul) {
-        const bool odd = lane & 1;
-        const float bias = p.bias ? bf16_bits_to_f32(p.bias[n]) : 0.0f;
-        uint16_t* act = reinterpret_cast<uint16_t*>(p.D) + (n >> 1);
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {                    // rows r and r + 1 of the register tile are adjacent rows of D
-          const uint32_t pk = mx_silu_pair(mx_y_bits(alpha, acc[i][j][r], p.bias, bias), mx_y_bits(alpha, acc[i][j][r + 1], p.bias, bias), odd);
-          const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h + (odd ? 1 : 0);
-          if (!(lane & 2) && m < p.M) *reinterpret_cast<uint32_t*>(act + (size_t)m * (size_t)(p.N >> 1)) = pk;
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-          if (m < p.M) mx_store(p, alpha, m, n, acc[i][j][r]);
-        }
-      }
-    }
+  constexpr bool kRepackedB = false;
+#include "gemm_mx_tile_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------- small M
@@ -289,10 +119,7 @@ __global__ __launch_bounds__(64 * kMxSmallWaves) void mx_small_kernel(MxArgs p) 
 // wave w takes the steps s = w (mod 8) in ascending order, the eight partial sums are added w = 0 .. 7.  Waves 0 .. 3 each finish one
 // 16-column fragment and put its activations into LDS (rows of 64 bytes padded to 80: 20 r mod 64 is a different multiple of 4 for each
 // of the 16 rows); 16 threads then quantise one row's block each.
-constexpr int kMxSliceCols = 64;
-constexpr int kMxSliceFrags = kMxSliceCols / 16;
 constexpr int kMxSliceUnroll = 2;
-constexpr int kMxSliceActRowBytes = 32 * 2 + 16;
 
 __global__ __launch_bounds__(64 * kMxSmallWaves) void mx_slice_quant_kernel(MxArgs p) {
   __shared__ __attribute__((aligned(16))) float part[kMxSmallWaves][kMxSliceFrags][64][4];
@@ -333,30 +160,7 @@ __global__ __launch_bounds__(64 * kMxSmallWaves) void mx_slice_quant_kernel(MxAr
                                                                     (int)(sb[u][j] >> sh));
       }
   }
-#pragma unroll
-  for (int j = 0; j < kMxSliceFrags; ++j) *reinterpret_cast<f32x4*>(part[wave][j][lane]) = acc[j];
-  __syncthreads();
-  if (wave < kMxSliceFrags) {                                  // wave j: fragment j, y-columns [16 j, 16 j + 16) of the slice
-    const float alpha = p.alpha_host * (p.alpha_dev ? *p.alpha_dev : 1.0f);
-    f32x4 t = *reinterpret_cast<const f32x4*>(part[0][wave][lane]);
-#pragma unroll
-    for (int w = 1; w < kMxSmallWaves; ++w) {
-      const f32x4 o = *reinterpret_cast<const f32x4*>(part[w][wave][lane]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) t[r] += o[r];
-    }
-    const bool odd = lane & 1;
-    const int nl = wave * 16 + r16;
-    const float bias = p.bias ? bf16_bits_to_f32(p.bias[n0 + nl]) : 0.0f;
-#pragma unroll
-    for (int r = 0; r < 4; r += 2) {
-      const uint32_t pk = mx_silu_pair(mx_y_bits(alpha, t[r], p.bias, bias), mx_y_bits(alpha, t[r + 1], p.bias, bias), odd);
-      const int ml = 4 * q + r + (odd ? 1 : 0);
-      if (!(lane & 2)) *reinterpret_cast<uint32_t*>(act + ml * kMxSliceActRowBytes + (nl >> 1) * 2) = pk;
-    }
-  }
-  __syncthreads();
-  if (tid < 16 && m0 + tid < p.M) mx_quantize_act_block(p, act + tid * kMxSliceActRowBytes, m0 + tid, (int)blockIdx.x);
+#include "gemm_mx_slice_finish.inc"
 }
 
 template <int kEpi>

@@ -1,4 +1,5 @@
-// What the MXFP4 GEMM units share (gemm_mx.hip: the reference-layout weight; gemm_mx_rw.hip: the repacked weight): the parameter
+// What the MXFP4 GEMM units share (gemm_mx.hip: the reference-layout weight; gemm_mx_rw.hip, gemm_mx_tile_rw.hip and gemm_mx_slice_rw.hip: the
+// repacked weight; the tiled and the quantising kernels share more: gemm_mx_tile_common.hpp): the parameter
 // block, the operand fragment of the block-scaled fp4 MFMA and the epilogues.  One text, so that a result cannot depend on which
 // layout the weight came in.
 #pragma once
@@ -16,9 +17,9 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct MxArgs {
   const uint8_t* A;
-  const uint8_t* B;       // gemm_mx_rw.hip: MRW (arcq.h "MXFP4 repacked weight")
+  const uint8_t* B;       // the units over the repacked weight: MRW (arcq.h "MXFP4 repacked weight")
   const uint8_t* SFA;
-  const uint8_t* SFB;     // gemm_mx_rw.hip: MRSF
+  const uint8_t* SFB;     // the units over the repacked weight: MRSF
   void* D;
   int M, N, Kp;
   float alpha_host;

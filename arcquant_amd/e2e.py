@@ -88,14 +88,19 @@ class QLinear:
         if release_reference:
             self.W = self.SFW = None
 
-    def mx_repack(self):
-        """Second copy of an MXFP4 weight in MFMA operand order for calls of at most agemm.MX_REPACKED_MAX_M tokens (agemm.mx_repack_w)."""
+    def mx_repack(self, release_reference=False):
+        """Second copy of an MXFP4 weight in MFMA operand order for calls of at most agemm.MX_REPACKED_MAX_M tokens (agemm.mx_repack_w).
+        release_reference: keep ONLY that copy (W / SFW dropped; every M then runs through agemm.mx_matmul_rw)."""
         self.MRW, self.MRSF = agemm.mx_repack_w(self.W, self.SFW)
+        if release_reference:
+            self.W = self.SFW = None
 
     def matmul(self, A, SFA, scale, ops=agemm, **kw):
         """GEMM against this weight (+ its bias, in the epilogue): the repacked kernel for decode-sized token counts where available.
         ``ops``: the module whose ``matmul_repacked`` / ``matmul_rw`` is called (the ctypes mirror or the extension module)."""
         kw.setdefault("bias", self.bias)
+        if self.quant_type == "MXFP4" and self.W is None:     # repacked only: one copy for every M
+            return agemm.mx_matmul_rw(A, self.MRW, SFA, self.MRSF, scale, self.out_f, **kw)
         if self.MRW is not None and A.shape[0] <= agemm.MX_REPACKED_MAX_M:
             return agemm.mx_matmul_repacked(A, self.MRW, SFA, self.MRSF, scale, self.out_f, **kw)
         if self.quant_type == "MXFP4":
@@ -108,6 +113,8 @@ class QLinear:
 
     def bytes(self):
         if self.quant_type == "MXFP4":   # Kp/2 code bytes + Kp/32 scale bytes per row (a decode step reads one copy, whichever it is)
+            if self.W is None:           # repacked only: the MRW / MRSF it holds (MRSF padded to whole rounds)
+                return self.MRW.numel() + self.MRSF.numel()
             return self.W.numel() + self.SFW.numel()
         if self.W is None:           # repacked only: the padded RW / RSF it holds
             return self.RW.numel() + self.RSF.numel()
@@ -130,8 +137,8 @@ class DecoderModel:
 
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
                  repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False, kv_cache: str = "bf16",
-                 kv_fused_step: bool = False, kv_paged_prefill: bool = False, mx_repacked_decode: bool = False, rope: bool = False,
-                 rope_theta: float = 1e6, rope_tables=None):
+                 kv_fused_step: bool = False, kv_paged_prefill: bool = False, mx_repacked_decode: bool = False,
+                 mx_repacked_only: bool = False, rope: bool = False, rope_theta: float = 1e6, rope_tables=None):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
@@ -141,6 +148,9 @@ class DecoderModel:
         mx_repacked_decode (quant_type="MXFP4", fused=True only, not with mx_quantised_epilogue): every linear additionally keeps its weight
         as agemm.mx_repack_w lays it out; calls of at most agemm.MX_REPACKED_MAX_M tokens run q|k|v, o, gate|up and down through
         agemm.mx_matmul_repacked / mx.matmul_silu_mul_repacked.  Same logits, bit for bit.
+        mx_repacked_only (quant_type="MXFP4", fused=True only, not with mx_repacked_decode): every linear keeps ONLY its repacked weight and
+        every GEMM, at any token count, runs over it (agemm.mx_matmul_rw, mx.matmul_silu_mul_rw; with mx_quantised_epilogue the gate|up call is
+        mx.matmul_silu_mul_quantize_rw).  Same logits, bit for bit, at half of mx_repacked_decode's weight memory.
         kv_cache="int4" (attention="cache", head dimension 128): the reference's int4 paged cache (arcquant_amd.kvcache)
         instead of the dense bf16 one -- a prefill writes its k / v through init_kv_quantize_i4, a decode step appends with
         append_kv_quantize_i4 and attends with batch_decode_i4.  "bf16" (default) is the dense cache.
@@ -181,8 +191,12 @@ class DecoderModel:
         if mx_repacked_decode and (quant_type != "MXFP4" or not fused or mx_quantised_epilogue):
             raise ValueError("DecoderModel: mx_repacked_decode needs quant_type='MXFP4' and fused=True, and has no form of the quantising "
                              "epilogue (mx_quantised_epilogue)")
+        if mx_repacked_only and (quant_type != "MXFP4" or not fused or mx_repacked_decode):
+            raise ValueError("DecoderModel: mx_repacked_only needs quant_type='MXFP4' and fused=True, and replaces mx_repacked_decode (it keeps "
+                             "the repacked copy alone; NVFP4 has repacked_only)")
         self.quant_type = quant_type
         self.mx_quantised_epilogue = mx_quantised_epilogue
+        self.mx_repacked_only = mx_repacked_only
         self.mx_repacked_decode = mx_repacked_decode
         self.cfg, self.device, self.batch, self.max_len, self.fused = cfg, device, batch, max_len, fused
         self.repacked_only = repacked_only
@@ -226,10 +240,10 @@ class DecoderModel:
             for L in self.layers:
                 for name in ("qkv", "o", "gateup", "down"):
                     L[name].repack(release_reference=repacked_only)
-        if mx_repacked_decode:
+        if mx_repacked_decode or mx_repacked_only:
             for L in self.layers:
                 for name in ("qkv", "o", "gateup", "down"):
-                    L[name].mx_repack()
+                    L[name].mx_repack(release_reference=mx_repacked_only)
         self.idx_h = torch.arange(h, dtype=torch.int16, device=device)
         self.idx_i = torch.arange(it, dtype=torch.int16, device=device)
         self.inv_idx_i = torch.argsort(self.idx_i.long()).to(torch.int16)     # act_scatter_index of the gate|up epilogue
@@ -381,7 +395,8 @@ class DecoderModel:
             mx.rmsnorm_quantize_x -> mx.matmul_silu_mul (+bias) -> mx_reorder_quantize_x -> down mx_matmul (+bias, +residual)
         (a decode step may take mx_matmul + mx.silu_mul_quantize_x instead of the middle two: mx_decode_route; with
         mx_quantised_epilogue the middle two are mx.matmul_silu_mul_quantize at every T -- idx_i is the identity; with mx_repacked_decode a
-        call of at most agemm.MX_REPACKED_MAX_M tokens takes every GEMM over the repacked weight); fused=False, the
+        call of at most agemm.MX_REPACKED_MAX_M tokens takes every GEMM over the repacked weight, with mx_repacked_only every call does:
+        the *_rw forms); fused=False, the
         reference's call structure (model/qQwenLayer.py): separate q, k, v and gate, up GEMMs, bias / SiLU*up / residual as torch ops.
         Every activation quantiser is one launch either way -- MXFP4 has no per-tensor scale to find first."""
         cfg = self.cfg
@@ -403,10 +418,15 @@ class DecoderModel:
                 hcur = L["o"].matmul(qa, sfa, 1.0, residual=hcur)
                 A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln2"], cfg.eps, self.idx_h, ke)
                 Gt = L["gateup"]                            # one weight with gate and up rows interleaved (g0, u0, g1, u1, ...)
-                if self.mx_quantised_epilogue:
+                if self.mx_quantised_epilogue and Gt.W is None:
+                    qa, sfa = mx.matmul_silu_mul_quantize_rw(A, Gt.MRW, SFA, Gt.MRSF, 1.0, Gt.out_f, ke, bias=Gt.bias)
+                elif self.mx_quantised_epilogue:
                     qa, sfa = mx.matmul_silu_mul_quantize(A, Gt.W, SFA, Gt.SFW, 1.0, ke, bias=Gt.bias)
                 elif T <= 64 and self.mx_decode_route == "quantiser":
                     qa, sfa = mx.silu_mul_quantize_x(Gt.matmul(A, SFA, 1.0), self.idx_i, ke, layout=agemm.GU_PAIRS)
+                elif Gt.W is None:
+                    act = mx.matmul_silu_mul_rw(A, Gt.MRW, SFA, Gt.MRSF, 1.0, Gt.out_f, bias=Gt.bias)
+                    qa, sfa = agemm.mx_reorder_quantize_x(act, self.idx_i, ke)
                 elif Gt.MRW is not None and T <= agemm.MX_REPACKED_MAX_M:
                     act = mx.matmul_silu_mul_repacked(A, Gt.MRW, SFA, Gt.MRSF, 1.0, Gt.out_f, bias=Gt.bias)
                     qa, sfa = agemm.mx_reorder_quantize_x(act, self.idx_i, ke)
@@ -554,9 +574,11 @@ class DecoderModel:
 
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
                  attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False, kv_cache="bf16",
-                 kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6, mx_repacked_decode=False):
+                 kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6, mx_repacked_decode=False,
+                 mx_repacked_only=False):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
-    weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds."""
+    weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds.  mx_repacked_only:
+    the same for quant_type="MXFP4"."""
     cfg = dataclasses.replace(MODEL_CFGS[name])
     if layers:
         cfg.num_layers = layers
@@ -565,7 +587,8 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         mem0 = torch.cuda.memory_allocated(device)
         model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
                              quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
-                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mx_repacked_decode)
+                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mx_repacked_decode,
+                             mx_repacked_only=mx_repacked_only)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -626,6 +649,8 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         res["mx_quantised_epilogue"] = True
     if mx_repacked_decode:
         res["mx_repacked_decode"] = True
+    if mx_repacked_only:
+        res.update(mx_repacked_only=True, model_resident_bytes=int(model_bytes))
     if kv_cache != "bf16":
         res["kv_cache"] = kv_cache
     if kv_fused_step:
@@ -639,7 +664,8 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
 
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
                    fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False,
-                   kv_cache="bf16", kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6, mx_repacked_decode=False):
+                   kv_cache="bf16", kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6, mx_repacked_decode=False,
+                   mx_repacked_only=False):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -668,9 +694,12 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         return round(float(t.mean()), 3), round(1.96 * float(t.std(unbiased=False)), 3), max(peaks)
 
     with torch.no_grad():
+        mem0 = torch.cuda.memory_allocated(device)
         model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
                              quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
-                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mx_repacked_decode)
+                             kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mx_repacked_decode,
+                             mx_repacked_only=mx_repacked_only)
+        model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
 
@@ -715,6 +744,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         res["mx_quantised_epilogue"] = True
     if mx_repacked_decode:
         res["mx_repacked_decode"] = True
+    if mx_repacked_only:
+        res.update(mx_repacked_only=True, model_resident_bytes=int(model_bytes))
     if kv_cache != "bf16":
         res["kv_cache"] = kv_cache
     if kv_fused_step:
@@ -890,15 +921,20 @@ if __name__ == "__main__":
     mrd = "--mx-repacked-decode" in sys.argv     # MXFP4, the fused model only: decode GEMMs over the repacked weight (agemm.mx_repack_w)
     if mrd and (qt != "MXFP4" or qe):
         sys.exit("--mx-repacked-decode needs --quant-type MXFP4 and excludes --mx-quantised-epilogue")
+    mro = "--mx-repacked-only" in sys.argv       # MXFP4, the fused model only: one weight copy per linear, every GEMM over the repacked weight
+    if mro and (qt != "MXFP4" or mrd):
+        sys.exit("--mx-repacked-only needs --quant-type MXFP4 and replaces --mx-repacked-decode")
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
             print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
-                                            kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mrd)), flush=True)
+                                            kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mrd,
+                                            mx_repacked_only=mro)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
-            if ((ro or qe or mrd) and not fused) or (kvc == "int4" and att != "cache"):
+            if ((ro or qe or mrd or mro) and not fused) or (kvc == "int4" and att != "cache"):
                 continue
             print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
-                                          kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mrd)), flush=True)
+                                          kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mrd,
+                                          mx_repacked_only=mro)), flush=True)
             torch.cuda.empty_cache()

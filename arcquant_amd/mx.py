@@ -4,7 +4,9 @@ quantisers and the gate|up GEMM with SiLU*up in its epilogue -- what ``agemm.rms
 slots.  ``matmul_silu_mul_quantize`` ends the family: the gate|up GEMM that writes the down projection's quantised input itself, which
 NVFP4's per-tensor scale rules out (``gate_up_rows`` lays the weight out for it).  The decode path over a weight repacked into MFMA
 operand order is here too: ``mx_repack_w`` / ``mx_unrepack_w``, ``mx_matmul_repacked`` and ``matmul_silu_mul_repacked`` (1 <= M <= 64, bit
-for bit the results of ``mx_matmul`` / ``matmul_silu_mul``).
+for bit the results of ``mx_matmul`` / ``matmul_silu_mul``), and the three GEMMs over the repacked weight ALONE at every M --
+``mx_matmul_rw``, ``matmul_silu_mul_rw``, ``matmul_silu_mul_quantize_rw`` (``mx_rw_route`` says which kernel serves a shape) -- with
+which a layer keeps one weight copy.
 
 The plain MXFP4 quantisers and GEMM stay in ``agemm`` (``mx_reorder_quantize_{x,w}``, ``mx_matmul``).  This module is a ctypes mirror
 only: the extension module ``agemm.so`` does not bind these operators.  Validation follows the mirror's order (``agemm._need`` ...):
@@ -161,8 +163,9 @@ def mx_repacked_supported(M: int, N: int, K: int) -> bool:
     return bool(_lib.lib().arcq_gemm_mxfp4_repacked_supported(int(M), int(N), int(K)))
 
 
-def _need_mx_repacked(A, MRW, SFA, MRSF, N, who):
+def _need_mx_repacked(A, MRW, SFA, MRSF, N, who, any_m=False):
     # A / SFA are the activations of an [M, K] call, (MRW, MRSF) the repacked MXFP4 weight of N rows over this K -> (M, N, K)
+    # any_m: the *_rw calls, which serve every M (the boundary bounds it as arcq_gemm_mxfp4 does)
     _need(A, torch.uint8, "A", 2)
     _need(MRW, torch.uint8, "MRW", 1)
     _need(SFA, torch.uint8, "SFA", 2)
@@ -176,7 +179,7 @@ def _need_mx_repacked(A, MRW, SFA, MRSF, N, who):
         raise RuntimeError(f"{who}: MRW / MRSF do not belong to a [{N}, {K}] MXFP4 weight")
     if tuple(SFA.shape) != (M, K // 32):
         raise RuntimeError(f"{who}: SFA must be [rows, K/32]")
-    if not mx_repacked_supported(M, N, K):
+    if not any_m and not mx_repacked_supported(M, N, K):
         raise RuntimeError(f"{who}: M={M} is outside the repacked path (1 <= M <= {MX_REPACKED_MAX_M}; see mx_repacked_supported)")
     return M, N, K
 
@@ -213,6 +216,75 @@ def matmul_silu_mul_repacked(A: torch.Tensor, MRW: torch.Tensor, SFA: torch.Tens
                                                           alpha_host, alpha_p, bias_p, _stream(A))
     _lib.check(st, "mx.matmul_silu_mul_repacked")
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def mx_rw_route(M: int, N: int, K: int) -> int:
+    """Which kernel serves an ``mx_matmul_rw`` call of this shape: 1 = the decode kernels (M <= 64: the call is ``mx_matmul_repacked``), 2 =
+    the tile kernel over the repacked weight, 0 = no such shape (M < 1, N % 16, K % 128)."""
+    return int(_lib.lib().arcq_gemm_mxfp4_rw_route(int(M), int(N), int(K)))
+
+
+def mx_matmul_rw(A: torch.Tensor, MRW: torch.Tensor, SFA: torch.Tensor, MRSF: torch.Tensor, scale, N: int, *, bias=None, residual=None,
+                 out_dtype=torch.bfloat16, out=None, scale_host: float = 1.0):
+    """``mx_matmul`` at EVERY M over the repacked weight alone (``mx_repack_w``; arguments as ``mx_matmul_repacked``): up to 64 rows the
+    decode kernel, above it the tile kernel with its B operand staged from ``(MRW, MRSF)``.  Bit for bit the result of ``mx_matmul`` on
+    the un-repacked operands, so a layer can keep this one copy of its weight."""
+    M, N, K = _need_mx_repacked(A, MRW, SFA, MRSF, N, "mx.mx_matmul_rw", any_m=True)
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, A, "mx.mx_matmul_rw")
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device("mx.mx_matmul_rw", A, MRW, SFA, MRSF, alpha_dev, out, bias, residual)
+    with _on(A.device):
+        st = _lib.lib().arcq_gemm_mxfp4_rw(A.data_ptr(), MRW.data_ptr(), SFA.data_ptr(), MRSF.data_ptr(), out.data_ptr(), M, N, K, alpha_host,
+                                           alpha_p, bias_p, residual_p, oc, _stream(A))
+    _lib.check(st, "mx.mx_matmul_rw")
+    return out
+
+
+def matmul_silu_mul_rw(A: torch.Tensor, MRW: torch.Tensor, SFA: torch.Tensor, MRSF: torch.Tensor, scale, N: int, *, scale_host: float = 1.0,
+                       bias=None, out=None):
+    """``matmul_silu_mul`` at every M over the repacked gate|up weight alone (arguments as ``matmul_silu_mul_repacked``).  Returns ``act``
+    bf16 [M, N/2], bit for bit what ``matmul_silu_mul`` returns on the un-repacked weight."""
+    M, N, K = _need_mx_repacked(A, MRW, SFA, MRSF, N, "mx.matmul_silu_mul_rw", any_m=True)
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, _ = _out(out, M, N // 2, torch.bfloat16, A, "mx.matmul_silu_mul_rw")
+    bias_p = _opt(bias, torch.bfloat16, "bias", (N,))
+    _same_device("mx.matmul_silu_mul_rw", A, MRW, SFA, MRSF, alpha_dev, out, bias)
+    with _on(A.device):
+        st = _lib.lib().arcq_gemm_mxfp4_rw_silu_mul(A.data_ptr(), MRW.data_ptr(), SFA.data_ptr(), MRSF.data_ptr(), out.data_ptr(), M, N, K,
+                                                    alpha_host, alpha_p, bias_p, _stream(A))
+    _lib.check(st, "mx.matmul_silu_mul_rw")
+    return out
+
+
+def matmul_silu_mul_quantize_rw(A: torch.Tensor, MRW: torch.Tensor, SFA: torch.Tensor, MRSF: torch.Tensor, scale, N: int, KE: int, *,
+                                scale_host: float = 1.0, bias=None):
+    """``matmul_silu_mul_quantize`` at every M over the repacked gate|up weight alone: ``(MRW, MRSF, N)`` in place of ``(B, SFB)``, the
+    other arguments and the result -- (QX, SFX) of the down projection's input -- byte for byte the same.  N % 128 == 0, KE % 64 == 0,
+    0 <= KE <= N/2 <= 32767."""
+    for t, name, rank in ((A, "A", 2), (MRW, "MRW", 1), (SFA, "SFA", 2), (MRSF, "MRSF", 1)):
+        _need(t, torch.uint8, name, rank)
+    M, K, N, KE = A.shape[0], A.shape[1] * 2, int(N), int(KE)
+    if K % 128:
+        raise RuntimeError(f"mx.matmul_silu_mul_quantize_rw: K={K} is not a padded MXFP4 K (a multiple of 128)")
+    if N <= 0 or N % 128:
+        raise RuntimeError(f"mx.matmul_silu_mul_quantize_rw: N={N} must be a positive multiple of 128 (N/2 activations in whole pairs of 32-blocks)")
+    if KE % 64 or KE < 0 or KE > N // 2 or N // 2 > 32767:
+        raise RuntimeError(f"Value error in mx.matmul_silu_mul_quantize_rw: KQ={N // 2}, KE={KE} is not valid")
+    if (MRW.numel(), MRSF.numel()) != _mx_repacked_bytes(N, K):
+        raise RuntimeError(f"mx.matmul_silu_mul_quantize_rw: MRW / MRSF do not belong to a [{N}, {K}] MXFP4 weight")
+    if tuple(SFA.shape) != (M, K // 32):
+        raise RuntimeError("mx.matmul_silu_mul_quantize_rw: SFA must be [rows, K/32]")
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    bias_p = _opt(bias, torch.bfloat16, "bias", (N,))
+    _same_device("mx.matmul_silu_mul_quantize_rw", A, MRW, SFA, MRSF, alpha_dev, bias)
+    QX, SFX = _outputs(M, N // 2, KE, A)
+    with _on(A.device):
+        st = _lib.lib().arcq_gemm_mxfp4_rw_silu_mul_quantize(A.data_ptr(), MRW.data_ptr(), SFA.data_ptr(), MRSF.data_ptr(), QX.data_ptr(),
+                                                             SFX.data_ptr(), M, N, K, alpha_host, alpha_p, bias_p, KE, _stream(A))
+    _lib.check(st, "mx.matmul_silu_mul_quantize_rw")
+    return QX, SFX
 
 
 def matmul_silu_mul_quantize(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor, SFB: torch.Tensor, scale, KE: int, *, scale_host: float = 1.0,

@@ -89,7 +89,8 @@ class QLinearLayer(nn.Module):
     """Weight quantised once at construction; forward = ARC-NVFP4 GEMM (+ bias) on pre-quantised activations."""
 
     def __init__(self, originalLayer: nn.Linear, select_num, reorder_index, out_reorder_index=None, quant_type="NVFP4",
-                 repack_for_decode: bool = False, repacked_only: bool = False, mx_repack_for_decode: bool = False):
+                 repack_for_decode: bool = False, repacked_only: bool = False, mx_repack_for_decode: bool = False,
+                 mx_repacked_only: bool = False):
         """``repack_for_decode`` (extension, default off = the reference's behaviour and memory): additionally keep the
         weight in MFMA-operand-order tiles (``agemm.repack_w``) and use ``agemm.matmul_repacked`` for calls of at most 16
         tokens.  ``repacked_only`` (extension): keep ONLY that copy -- ``W`` / ``scale_w`` are registered as None, every call
@@ -97,7 +98,10 @@ class QLinearLayer(nn.Module):
         an LDS-transposing kernel: there up to fp32 summation order); ``agemm.unrepack_w(RW, RSF, ...)`` rebuilds the
         reference-layout pair.  ``mx_repack_for_decode`` (extension, quant_type='MXFP4' only): additionally keep the weight as
         ``agemm.mx_repack_w`` lays it out (``MRW`` / ``MRSF``); calls of at most ``agemm.MX_REPACKED_MAX_M`` tokens run through
-        ``agemm.mx_matmul_repacked``, longer ones through ``agemm.mx_matmul`` -- the same bits either way."""
+        ``agemm.mx_matmul_repacked``, longer ones through ``agemm.mx_matmul`` -- the same bits either way.  ``mx_repacked_only``
+        (extension, quant_type='MXFP4' only): keep ONLY ``MRW`` / ``MRSF`` -- ``W`` / ``scale_w`` are registered as None and every call, at
+        any token count, runs through ``agemm.mx_matmul_rw`` (the same bits again); ``agemm.mx_unrepack_w(MRW, MRSF, out_features, Kp)``
+        rebuilds the reference-layout pair."""
         super().__init__()
         if quant_type not in ("NVFP4", "MXFP4"):
             raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4 and MXFP4 are)")
@@ -105,6 +109,8 @@ class QLinearLayer(nn.Module):
             raise ValueError("repack_for_decode / repacked_only apply to the NVFP4 weight layout only, not to quant_type='MXFP4'")
         if mx_repack_for_decode and quant_type != "MXFP4":
             raise ValueError("mx_repack_for_decode applies to quant_type='MXFP4' only (NVFP4 has repack_for_decode / repacked_only)")
+        if mx_repacked_only and quant_type != "MXFP4":
+            raise ValueError("mx_repacked_only applies to quant_type='MXFP4' only (NVFP4 has repacked_only)")
         self.in_features = originalLayer.in_features
         self.out_features = originalLayer.out_features
         if originalLayer.bias is not None:
@@ -121,14 +127,14 @@ class QLinearLayer(nn.Module):
         quantize_w = MXFP4_reorder_quantize_w if quant_type == "MXFP4" else NVFP4_reorder_quantize_w
         W, scale_w, scale = quantize_w(w, idx, self.select_num)
         RW, RSF = agemm.repack_w(W, scale_w) if (repack_for_decode or repacked_only) else (None, None)
-        if repacked_only:
+        MRW, MRSF = agemm.mx_repack_w(W, scale_w) if (mx_repack_for_decode or mx_repacked_only) else (None, None)
+        if repacked_only or mx_repacked_only:
             W = scale_w = None
         self.register_buffer("W", W)
         self.register_buffer("scale_w", scale_w)
         self.register_buffer("scale", scale)
         self.register_buffer("RW", RW)
         self.register_buffer("RSF", RSF)
-        MRW, MRSF = agemm.mx_repack_w(W, scale_w) if mx_repack_for_decode else (None, None)
         self.register_buffer("MRW", MRW)
         self.register_buffer("MRSF", MRSF)
 
@@ -138,7 +144,9 @@ class QLinearLayer(nn.Module):
         # `y = matmul(...); y = y + bias` (model/qLinearLayer.py:74-76): the bias add runs in the GEMM epilogue with the same
         # two roundings (the bf16 product, then the bf16 sum), so the result is bit-identical to the two torch steps
         bias = self.bias if self.bias is None or self.bias.dtype == torch.bfloat16 else None
-        if getattr(self, "MRW", None) is not None and qx.shape[0] <= agemm.MX_REPACKED_MAX_M:
+        if self.quant_type == "MXFP4" and self.W is None:         # mx_repacked_only: the one copy serves every token count
+            y = agemm.mx_matmul_rw(qx, self.MRW, scale_x, self.MRSF, scale * self.scale, self.out_features, bias=bias)
+        elif getattr(self, "MRW", None) is not None and qx.shape[0] <= agemm.MX_REPACKED_MAX_M:
             y = agemm.mx_matmul_repacked(qx, self.MRW, scale_x, self.MRSF, scale * self.scale, self.out_features, bias=bias)
         elif self.quant_type == "MXFP4":
             y = agemm.mx_matmul(qx, self.W, scale_x, self.scale_w, scale * self.scale, bias=bias)

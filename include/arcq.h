@@ -366,6 +366,28 @@ int arcq_gemm_mxfp4_repacked_silu_mul(const uint8_t *A, const uint8_t *MRW, cons
                                       int64_t M, int64_t N, int64_t K, float alpha_host, const float *alpha_dev, const void *bias,
                                       void *stream);
 
+/* ---- MXFP4 repacked weight, every batch size: one weight copy per layer ----------------------------------------------------------
+ * The three GEMMs of the MXFP4 path over (MRW, MRSF) alone, for ANY M >= 0, so that a layer need not keep (QW, SFW) beside them.
+ * M <= 64 runs the decode kernels above (arcq_gemm_mxfp4_rw at such an M IS arcq_gemm_mxfp4_repacked; the quantising form has a decode
+ * kernel of its own: four row blocks = one 32-block of activations per workgroup, the same K split and sum order).  M > 64 runs the
+ * 128 x 128 tile kernel of arcq_gemm_mxfp4 with its B operand staged from (MRW, MRSF): a wave fetches whole 1 KB spans of MRW, the four
+ * scale bytes of a row and step are gathered from their four MRSF dwords, and what the MFMAs read from LDS is byte for byte what the
+ * reference-layout kernel stages.  Results are BIT FOR BIT those of arcq_gemm_mxfp4, arcq_gemm_mxfp4_silu_mul and
+ * arcq_gemm_mxfp4_silu_mul_quantize on (QW, SFW), at every M.  No result depends on MRSF's padding bytes.  No workspace.
+ *   Status, all before any HIP call and in the order of the reference-layout namesake: ARCQ_ERR_SHAPE for M or N < 0, K % 128, N % 16
+ *   (N % 128 and the KE rule for the quantising form); ARCQ_ERR_SHAPE for a bad out_dtype; M == 0 or N == 0 returns ARCQ_OK; ARCQ_ERR_NULL
+ *   for a NULL operand; ARCQ_ERR_UNSUPPORTED for M beyond arcq_gemm_mxfp4's limit; ARCQ_ERR_SHAPE for a misaligned pointer (A, MRW, D /
+ *   ACT / QACT 16 bytes; SFA, MRSF 4 bytes; bias, residual 2 bytes). */
+int arcq_gemm_mxfp4_rw_route(int64_t M, int64_t N, int64_t K);   /* 1: the decode kernels (the call IS arcq_gemm_mxfp4_repacked), 2: the tile kernel over MRW, 0: invalid shape */
+int arcq_gemm_mxfp4_rw(const uint8_t *A, const uint8_t *MRW, const uint8_t *SFA, const uint8_t *MRSF, void *D, int64_t M, int64_t N,
+                       int64_t K, float alpha_host, const float *alpha_dev, const void *bias, const void *residual, int out_dtype,
+                       void *stream);
+int arcq_gemm_mxfp4_rw_silu_mul(const uint8_t *A, const uint8_t *MRW, const uint8_t *SFA, const uint8_t *MRSF, void *ACT, int64_t M,
+                                int64_t N, int64_t K, float alpha_host, const float *alpha_dev, const void *bias, void *stream);
+int arcq_gemm_mxfp4_rw_silu_mul_quantize(const uint8_t *A, const uint8_t *MRW, const uint8_t *SFA, const uint8_t *MRSF, uint8_t *QACT,
+                                         uint8_t *SFACT, int64_t M, int64_t N, int64_t K, float alpha_host, const float *alpha_dev,
+                                         const void *bias, int64_t KE, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
