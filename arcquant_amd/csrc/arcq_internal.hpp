@@ -194,6 +194,13 @@ int gemm_repacked(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipS
 int gemm_repacked_mid_supported(int64_t M, int64_t N, int64_t K);                                          // gemm_rowmid.hip: 16 < M <= 64
 int gemm_repacked_mid(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipStream_t stream);
 int gemm_repacked_stream(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipStream_t stream);   // gemm_stream.hip (A-B)
+// The M <= 16 repacked kernels (gemm_rowblock.hip, gemm_stream.hip) address D and the residual with the 32-bit ELEMENT offset
+// m * N + n (finish4<uint32_t>, gemm_common.hpp): the last one, M * N - 1, must fit.  The predicates say no beyond it and the
+// launchers refuse by name.
+inline bool repacked_out_fits(int64_t M, int64_t N) { return M * N <= ((int64_t)1 << 32); }
+inline int repacked_out_refused(const char* who, int64_t M, int64_t N) {
+  return fail(ARCQ_ERR_UNSUPPORTED, "%s: M * N = %lld elements exceed the decode kernels' 32-bit output offsets", who, (long long)(M * N));
+}
 // kEpiSiluMul on the M <= 16 repacked kernels (D stays gate|up, absmax_slots gets max |silu(g) * u| per row block): 0, or the error set
 inline int repacked_silu_args_check(const GemmArgs& a) {
   if (a.epilogue == kEpiSiluMul && (!a.absmax_slots || (a.N % 4) || a.bias || a.residual || a.out_dtype != ARCQ_OUT_BF16))

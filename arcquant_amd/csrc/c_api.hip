@@ -61,7 +61,8 @@ int gemm_checks(const GemmRule& r, const void* A, const void* B, const void* SFA
   if (M == 0 || N == 0) return 1;                              // nothing to do
   if (r.prefill_only && M <= kSkinnyMaxM) return fail(ARCQ_ERR_UNSUPPORTED, "%s: %s", r.who, r.prefill_only);
   if (!A || !B || !SFA || !SFB || !D || (r.slots && !absmax_slots)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", r.who);
-  if ((r.max_m && (M > r.max_m || M * N > ((int64_t)1 << 40))) || N > INT32_MAX / 2 || K > INT32_MAX / 2)
+  // (max_m == 0: the kernel's predicate bounds M, but only an M that survives the parameter blocks' int reaches it)
+  if ((r.max_m ? (M > r.max_m || M * N > ((int64_t)1 << 40)) : M > INT32_MAX) || N > INT32_MAX / 2 || K > INT32_MAX / 2)
     return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", r.who);
   if ((bits(A) | bits(B) | bits(D)) & 15) return fail(ARCQ_ERR_SHAPE, "%s: A, %s and %s must be 16-byte aligned", r.who, r.b, r.d);
   if ((bits(SFA) | bits(SFB) | (r.slots ? bits(absmax_slots) : 0)) & 3)
@@ -347,7 +348,7 @@ static int fused_common_checks(const char* who, const void* X, const int16_t* id
   if (out_dtype != ARCQ_OUT_BF16 && out_dtype != ARCQ_OUT_F32) return fail(ARCQ_ERR_SHAPE, "%s: bad out_dtype %d", who, out_dtype);
   if (M == 0 || N == 0) return 1;                              // nothing to do
   if (!X || !idx || !RW || !RSF || !D) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", who);
-  if (N > INT32_MAX / 2 || KQ > 32767) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
+  if (M > INT32_MAX || N > INT32_MAX / 2 || KQ > 32767) return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", who);
   if ((bits(X) | bits(idx) | bits(RW) | bits(D)) & 15)
     return fail(ARCQ_ERR_SHAPE, "%s: X, reorder_index, RW and D must be 16-byte aligned", who);
   if (bits(RSF) & 3) return fail(ARCQ_ERR_SHAPE, "%s: RSF must be 4-byte aligned", who);

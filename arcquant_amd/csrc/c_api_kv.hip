@@ -88,6 +88,8 @@ int write_call(const char* who, KvWriteArgs& a, bool init, void* stream) {
   if ((rc = geometry(who, a.B, a.L, a.layer, a.N, a.P, a.format)) || (a.quantize && (rc = dtype_ok(who, a.dtype))) || (rc = ntok_ok(who, a.ntok)) ||
       (a.quantize && (rc = int4_only(who, a.format, kQuantiserWrites))))
     return rc;
+  // the quantising writers launch one workgroup per 16 (token, K | V, head) rows (kv_write): the count must fit the grid
+  if (a.quantize && a.ntok * 2 * a.N > 16 * (int64_t)INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: ntok * 2 N rows are out of range", who);
   if (a.B == 0 || a.ntok == 0) return ARCQ_OK;
   if ((rc = none_null(who, {a.kv_data, a.kv_param, a.kv_indptr, a.kv_indices, a.last_page_offset, a.k, a.v, when(init, a.seqlen_indptr),
                             when(!a.quantize, a.k_param), when(!a.quantize, a.v_param)})) ||

@@ -321,7 +321,7 @@ static int rowblock_lds_bytes(int M, int64_t K, int slices, int* a_stride) {
 // the PACKED activations fit LDS (gemm_rowmid.hip)
 int gemm_repacked_supported(int64_t M, int64_t N, int64_t K) {
   if (M > 16) return gemm_repacked_mid_supported(M, N, K);
-  if (M < 1 || N < 1 || K < 64 || (K % 64)) return 0;
+  if (M < 1 || N < 1 || K < 64 || (K % 64) || !repacked_out_fits(M, N)) return 0;
   int stride;
   return rowblock_lds_bytes((int)M, K, 8, &stride) <= 160 * 1024 ? 1 : 0;
 }
@@ -359,6 +359,7 @@ int gemm_repacked(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipS
   if (use_stream) return gemm_repacked_stream(a, RW, RSF, stream);
   const bool silu = a.epilogue == kEpiSiluMul;              // here: D stays gate|up, absmax_slots gets max |silu(g) * u| per row block
   if (const int err = repacked_silu_args_check(a)) return err;
+  if (!repacked_out_fits(a.M, a.N)) return repacked_out_refused(kRbWho, a.M, a.N);
   if (!gemm_repacked_supported(a.M, a.N, a.K))
     return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4_repacked: M=%d K=%d outside the repacked path (M <= 16, activation image <= 160 KB)", a.M, a.K);
   RowblockParams p;

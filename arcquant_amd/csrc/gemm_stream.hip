@@ -630,7 +630,7 @@ struct StreamGeom {
 
 // 1 = the shape fits this kernel (M <= 16, the fp16 image and -- for kSrcRms -- the staged rows fit the 160 KB of LDS)
 static int stream_geometry(int src, int64_t M, int64_t N, int64_t K, int64_t KQ, StreamGeom* g) {
-  if (M < 1 || M > 16 || N < 1 || K < 64 || (K % 64)) return 0;
+  if (M < 1 || M > 16 || N < 1 || K < 64 || (K % 64) || !repacked_out_fits(M, N)) return 0;
   const int64_t cap = 160 * 1024;
   g->pairs = (int)repacked_pairs(K);
   g->row_blocks = (int)((N + 15) / 16);
@@ -696,6 +696,7 @@ static void fill_common(StreamParams& p, const StreamGeom& g, const GemmArgs& a,
 int gemm_repacked_stream(const GemmArgs& a, const uint8_t* RW, const uint8_t* RSF, hipStream_t stream) {
   const bool silu = a.epilogue == kEpiSiluMul;              // here: D stays gate|up, absmax_slots gets max |silu(g) * u| per row block
   if (const int err = repacked_silu_args_check(a)) return err;
+  if (a.M <= 16 && !repacked_out_fits(a.M, a.N)) return repacked_out_refused("arcq_gemm_nvfp4_repacked", a.M, a.N);
   StreamGeom g;
   if (!stream_geometry(kSrcPacked, a.M, a.N, a.K, 0, &g))
     return fail(ARCQ_ERR_UNSUPPORTED, "arcq_gemm_nvfp4_repacked: M=%d K=%d outside the repacked path (M <= 16, activation image <= 160 KB)", a.M, a.K);
@@ -711,6 +712,7 @@ int gemm_fused(const FusedArgs& f, hipStream_t stream) {
   StreamGeom g;
   const int64_t K = (int64_t)f.KQ + f.KE;
   if (f.kind != kSrcRms && f.kind != kSrcDyn) return fail(ARCQ_ERR_SHAPE, "%s: unknown source kind %d", who, f.kind);
+  if (f.M >= 1 && f.M <= 16 && !repacked_out_fits(f.M, f.N)) return repacked_out_refused(who, f.M, f.N);
   if (!gemm_fused_supported(f.kind, f.M, f.N, f.KQ, f.KE) || !stream_geometry(f.kind, f.M, f.N, K, f.KQ, &g))
     return fail(ARCQ_ERR_UNSUPPORTED, "%s: M=%d N=%d KQ=%d KE=%d outside the fused decode path (see arcq_linear_fused_supported)", who, f.M, f.N, f.KQ, f.KE);
   GemmArgs a{};

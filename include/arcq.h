@@ -165,7 +165,7 @@ int arcq_quantize_x_dyn_slots(const void *X, const int16_t *reorder_index, uint8
  * first and in the second tile; K padded to a multiple of 256 and N to a multiple of 16 with zero scales.  Sizes from
  * arcq_repacked_{w,sf}_bytes; arcquant_amd/agemm.py:repack_w builds both from the reference layout (pure data movement,
  * nothing is re-quantised).  A / SFA stay in the reference layout.  arcq_gemm_repacked_supported tells whether a shape
- * can take this path -- M <= 16 and the fp16 image of the activations fits LDS, or a decode batch 16 < M <= 128 on a
+ * can take this path -- M <= 16, M * N <= 2^32 (32-bit output offsets) and the fp16 image of the activations fits LDS, or a decode batch 16 < M <= 128 on a
  * weight where reading it once beats the tiled GEMM (activations fetched per tile pair or kept packed in LDS; gemm_rowmid.hip) --;
  * results equal arcq_gemm_nvfp4's up to fp32 accumulation order. */
 int64_t arcq_repacked_w_bytes(int64_t N, int64_t K);
