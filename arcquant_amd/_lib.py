@@ -73,6 +73,12 @@ SYMBOLS = {
     "arcq_gemm_mxfp4_rw": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p]),
     "arcq_gemm_mxfp4_rw_silu_mul": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p]),
     "arcq_gemm_mxfp4_rw_silu_mul_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _i64, _p]),
+    "arcq_mx_linear_fused_supported": (_i32, [_i32, _i64, _i64, _i64, _i64]),
+    "arcq_mx_linear_fused_workgroups": (_i64, [_i32, _i64, _i64, _i64]),
+    "arcq_mx_linear_fused_lds_bytes": (_i64, [_i32, _i64, _i64]),
+    "arcq_mx_linear_rmsnorm_repacked": (_i32, [_p, _p, _f32, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p]),
+    "arcq_mx_linear_rmsnorm_silu_repacked": (_i32, [_p, _p, _f32, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p, _p, _p]),
+    "arcq_mx_linear_quantize_repacked": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p]),
 }
 
 # include/arcq_harness.h: e2e-harness-only entry points (NOT the drop-in boundary)

@@ -750,7 +750,7 @@ def dynamic_matmul_repacked(X: torch.Tensor, reorder_index: torch.Tensor, KE: in
 # ---- MXFP4 repacked weight (include/arcq.h "MXFP4 repacked weight"): the layout functions and the decode GEMM over it live in
 # arcquant_amd/mx.py with the other MXFP4 operators that only the ctypes mirror has; they are reachable under this module's name too.
 # (Resolved on first use: mx imports this module's validators.)
-_FROM_MX = ("MX_REPACKED_MAX_M", "mx_repack_w", "mx_unrepack_w", "mx_repacked_supported", "mx_matmul_repacked", "mx_matmul_rw",
+_FROM_MX = ("MX_REPACKED_MAX_M", "mx_repack_w", "mx_unrepack_w", "mx_repacked_supported", "mx_linear_fused_supported", "mx_matmul_repacked", "mx_matmul_rw",
             "matmul_silu_mul_rw", "matmul_silu_mul_quantize_rw", "mx_rw_route")
 
 

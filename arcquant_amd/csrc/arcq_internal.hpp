@@ -57,6 +57,7 @@ struct GemmRule {
   bool slots = false;                   // takes absmax_slots (non-NULL, 4-byte aligned)
   int epi_align = 1;                    // bias and residual alignment in bytes
   const char* prefill_only = nullptr;   // set: M <= 16 is ARCQ_ERR_UNSUPPORTED with this text, reported before a NULL pointer
+  bool no_a = false;                    // the fused linears: the activation operand is the quantiser's, A / SFA are neither required nor named
 };
 // In the order every entry point reports them: divisibility, out_dtype, empty shape (returns 1: nothing to do), prefill_only, NULL, size
 // limits, 16-byte operands, 4-byte operands, bias / residual.  Returns ARCQ_OK to go on or the recorded failure; no HIP call.
@@ -70,7 +71,9 @@ int gemm_checks(const GemmRule& r, const void* A, const void* B, const void* SFA
 //   kQuantNvContig arcq_quantize_x_dyn_slots with reorder_index == NULL: no index; the KQ range is part of the shape fault
 //   kQuantMx       MXFP4 rows: no variant; the range is part of the shape fault; X, reorder_index, QX 16-byte, SFX unaligned
 //   kQuantMxFused  MXFP4 fused sources: as kQuantMx, the range spelled out in the text, `extra` among the 16-byte inputs
-enum : int { kQuantNv = 0, kQuantNvContig = 1, kQuantMx = 2, kQuantMxFused = 3 };
+//   kQuantMxLinear the prologue of the MXFP4 fused linears: kQuantMxFused with `extra`, kQuantMx without; no outputs (Q / SF are neither
+//                  required nor named)
+enum : int { kQuantNv = 0, kQuantNvContig = 1, kQuantMx = 2, kQuantMxFused = 3, kQuantMxLinear = 4 };
 enum : int { kQuantStatic = 0, kQuantState = 1, kQuantSlots = 2 };
 struct QuantRule {
   const char* who;
@@ -144,6 +147,13 @@ int gemm_mx_repacked(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, c
                      float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, hipStream_t stream);
 int gemm_mx_repacked_silu_mul(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* ACT, int64_t M, int64_t N,
                               int64_t Kp, float alpha_host, const float* alpha_dev, const void* bias, hipStream_t stream);
+// gemm_mx_linear_rw.hip: the MXFP4 fused decode linear (arcq.h "MXFP4 fused decode linear"); kind = ARCQ_SRC_RMSNORM | ARCQ_SRC_PLAIN
+int64_t gemm_mx_linear_lds_bytes(int kind, int64_t KQ, int64_t KE);
+int gemm_mx_linear_supported(int kind, int64_t M, int64_t N, int64_t KQ, int64_t KE);
+int64_t gemm_mx_linear_workgroups(int kind, int64_t N, int64_t KQ, int64_t KE);
+int gemm_mx_linear(int kind, bool silu, const void* X, const void* Wn, float eps, const int16_t* idx, const uint8_t* MRW, const uint8_t* MRSF, void* D,
+                   int64_t M, int64_t N, int64_t KQ, int64_t KE, float alpha_host, const float* alpha_dev, const void* bias, const void* residual,
+                   int out_dtype, const char* who, hipStream_t stream);
 // gemm_mx_tile_rw.hip (M > 64, the tile kernel over MRW / MRSF) and gemm_mx_slice_rw.hip (the quantising kernel for M <= 64): every
 // M >= 1 over the repacked weight alone; the results are gemm_mx's, gemm_mx_silu_mul's and gemm_mx_silu_mul_quantize's, bit for bit
 int gemm_mx_rw_route(int64_t M, int64_t N, int64_t Kp);   // 1: the decode kernels, 2: the tile kernel, 0: no such shape

@@ -60,10 +60,15 @@ int gemm_checks(const GemmRule& r, const void* A, const void* B, const void* SFA
   if (out_dtype != ARCQ_OUT_BF16 && out_dtype != ARCQ_OUT_F32) return fail(ARCQ_ERR_SHAPE, "%s: bad out_dtype %d", r.who, out_dtype);
   if (M == 0 || N == 0) return 1;                              // nothing to do
   if (r.prefill_only && M <= kSkinnyMaxM) return fail(ARCQ_ERR_UNSUPPORTED, "%s: %s", r.who, r.prefill_only);
-  if (!A || !B || !SFA || !SFB || !D || (r.slots && !absmax_slots)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", r.who);
+  if ((!r.no_a && (!A || !SFA)) || !B || !SFB || !D || (r.slots && !absmax_slots)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", r.who);
   // (max_m == 0: the kernel's predicate bounds M, but only an M that survives the parameter blocks' int reaches it)
   if ((r.max_m ? (M > r.max_m || M * N > ((int64_t)1 << 40)) : M > INT32_MAX) || N > INT32_MAX / 2 || K > INT32_MAX / 2)
     return fail(ARCQ_ERR_UNSUPPORTED, "%s: shape too large", r.who);
+  if (r.no_a) {
+    if ((bits(B) | bits(D)) & 15) return fail(ARCQ_ERR_SHAPE, "%s: %s and %s must be 16-byte aligned", r.who, r.b, r.d);
+    if (bits(SFB) & 3) return fail(ARCQ_ERR_SHAPE, "%s: %s must be 4-byte aligned", r.who, r.sfb);
+    return check_epi_align(r.who, bias, residual, r.epi_align);
+  }
   if ((bits(A) | bits(B) | bits(D)) & 15) return fail(ARCQ_ERR_SHAPE, "%s: A, %s and %s must be 16-byte aligned", r.who, r.b, r.d);
   if ((bits(SFA) | bits(SFB) | (r.slots ? bits(absmax_slots) : 0)) & 3)
     return fail(ARCQ_ERR_SHAPE, r.slots ? "%s: SFA, %s and absmax_slots must be 4-byte aligned" : "%s: SFA and %s must be 4-byte aligned", r.who, r.sfb);
@@ -71,7 +76,7 @@ int gemm_checks(const GemmRule& r, const void* A, const void* B, const void* SFA
 }
 
 int quant_checks(const QuantRule& r, const QuantArgs& a) {
-  const bool nv = r.family == kQuantNv, mx = r.family == kQuantMx || r.family == kQuantMxFused;
+  const bool nv = r.family == kQuantNv, lin = r.family == kQuantMxLinear, mx = r.family == kQuantMx || r.family == kQuantMxFused || lin;
   if (r.layout && a.layout != ARCQ_GU_HALVES && a.layout != ARCQ_GU_PAIRS) return fail(ARCQ_ERR_SHAPE, "%s: unknown layout %d", r.who, a.layout);
   // pinned quirks: the dynamic entries report scale_out / state / slots ahead of the shape, and arcq_rmsnorm_quantize_x a misaligned norm weight
   if (r.dyn == kQuantState && (!a.scale_out || !a.dyn)) return fail(ARCQ_ERR_NULL, "%s: NULL scale_out / state", r.who);
@@ -84,7 +89,7 @@ int quant_checks(const QuantRule& r, const QuantArgs& a) {
   const int64_t rows = r.x_alone && a.rows < 0 ? 0 : a.rows, rows_said = r.x_alone ? 0 : rows;
   if (rows < 0 || a.KQ <= 0 || (a.KQ % 64) || (a.KE % 64) || a.KE < 0 || a.KE > a.KQ || (!nv && (a.KQ < r.kq_min || a.KQ > r.kq_max))) {
     char range[48] = "";
-    if (r.family == kQuantMxFused) snprintf(range, sizeof(range), ", %lld<=KQ<=%lld", (long long)r.kq_min, (long long)r.kq_max);
+    if (r.family == kQuantMxFused || (lin && r.extra)) snprintf(range, sizeof(range), ", %lld<=KQ<=%lld", (long long)r.kq_min, (long long)r.kq_max);
     else if (!nv) snprintf(range, sizeof(range), "<=%lld", (long long)r.kq_max);
     return fail(ARCQ_ERR_SHAPE, "%s: need KQ%%64==0, KE%%64==0, 0<=KE<=KQ%s (%s=%lld KQ=%lld KE=%lld)", r.who, range,
                 r.family == kQuantNvContig ? "M" : "rows", (long long)rows_said, (long long)a.KQ, (long long)a.KE);
@@ -96,15 +101,19 @@ int quant_checks(const QuantRule& r, const QuantArgs& a) {
     return fail(ARCQ_ERR_UNSUPPORTED, "%s: KQ=%lld outside the reference's RMSNorm range [%lld, %lld]", r.who, (long long)a.KQ, (long long)r.kq_min,
                 (long long)r.kq_max);
   if (rows == 0) return 1;                                     // nothing to do
-  if (!a.X || (r.family != kQuantNvContig && !a.idx) || !a.Q || !a.SF || (r.extra && !a.extra)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", r.who);
+  if (!a.X || (r.family != kQuantNvContig && !a.idx) || (!lin && (!a.Q || !a.SF)) || (r.extra && !a.extra)) return fail(ARCQ_ERR_NULL, "%s: NULL pointer", r.who);
   if (r.x_alone && (bits(a.X) & 15)) return fail(ARCQ_ERR_SHAPE, "%s: %s must be 16-byte aligned", r.who, r.x_alone);
   if (rows > INT32_MAX) return fail(ARCQ_ERR_UNSUPPORTED, "%s: too many rows", r.who);
   // 16-byte row / index loads; NVFP4: 8-byte code stores, 4-byte scale stores; MXFP4: 16-byte code stores (Kp/2 is a multiple of 64), scale bytes
-  const bool in_bad = (bits(a.X) | bits(a.idx) | bits(a.extra)) & 15, out_bad = mx ? (bits(a.Q) & 15) != 0 : (bits(a.Q) & 7) || (bits(a.SF) & 3);
+  const bool in_bad = (bits(a.X) | bits(a.idx) | bits(a.extra)) & 15,
+             out_bad = lin ? false : mx ? (bits(a.Q) & 15) != 0 : (bits(a.Q) & 7) || (bits(a.SF) & 3);
   static const char* const kAlignText[] = {"%s: X and reorder_index must be 16-byte aligned", "%s: X must be 16-byte, QX 8-byte and SFX 4-byte aligned",
                                            "%s: X, reorder_index and the packed output must be 16-byte aligned",
-                                           "%s: the inputs, reorder_index and the packed output must be 16-byte aligned"};
-  if (in_bad || (!nv && out_bad)) return fail(ARCQ_ERR_SHAPE, kAlignText[r.family], r.who);
+                                           "%s: the inputs, reorder_index and the packed output must be 16-byte aligned",
+                                           "%s: X, the norm weight and reorder_index must be 16-byte aligned"};
+  static_assert(sizeof(kAlignText) / sizeof(kAlignText[0]) == kQuantMxLinear + 1, "one text per family");
+  // (kQuantMxLinear without a norm weight has X and reorder_index alone: kQuantNv's text)
+  if (in_bad || (!nv && out_bad)) return fail(ARCQ_ERR_SHAPE, kAlignText[lin && !r.extra ? kQuantNv : r.family], r.who);
   if (out_bad) return fail(ARCQ_ERR_SHAPE, "%s: the packed output must be 8-byte and the scale buffer 4-byte aligned", r.who);
   return ARCQ_OK;
 }

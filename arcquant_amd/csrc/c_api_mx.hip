@@ -131,4 +131,69 @@ int arcq_gemm_mxfp4_rw_silu_mul_quantize(const uint8_t* A, const uint8_t* MRW, c
   return gemm_mx_rw_silu_mul_quantize(A, MRW, SFA, MRSF, QACT, SFACT, M, N, K, alpha_host, alpha_dev, bias, KE, (hipStream_t)stream);
 }
 
+// ---- MXFP4 fused decode linear (arcq.h): the quantiser's rules (quant_checks, family kQuantMxLinear) and the repacked GEMM's
+// (gemm_checks, no_a) reported in ONE order -- every shape fault, out_dtype, empty, every NULL, unsupported, every alignment -- by
+// running the two validators three times over stand-in operands that let one kind of fault through at a time: a valid aligned
+// stand-in for every pointer (shape faults only), then one wherever the operand is not NULL (NULL faults only), then the operands.
+// (An M or N beyond the parameter block's int is gemm_checks' "shape too large", ARCQ_ERR_UNSUPPORTED, in the first pass.)
+static const void* const kMxLinStandIn = reinterpret_cast<const void*>(uintptr_t{256});
+static const void* there(const void* p) { return p ? kMxLinStandIn : nullptr; }
+
+static int mx_linear_checks(const char* who, int kind, bool silu, const void* X, const void* Wn, const int16_t* idx, const uint8_t* MRW, const uint8_t* MRSF,
+                            void* D, int64_t M, int64_t N, int64_t KQ, int64_t KE, const void* bias, const void* residual, int out_dtype) {
+  const bool rms = kind == ARCQ_SRC_RMSNORM;
+  QuantRule q{who};
+  q.family = kQuantMxLinear;
+  if (rms) { q.extra = true; q.kq_min = 2048; q.kq_max = 8192; }
+  GemmRule g{who};
+  g.k_mult = 128; g.n_mult = 16; g.max_m = 0; g.epi_align = 2; g.b = "MRW"; g.sfb = "MRSF"; g.d = silu ? "ACT" : "D"; g.no_a = true;
+  const void* const s = kMxLinStandIn;
+  if (const int rc = quant_checks(q, QuantArgs{s, rms ? s : nullptr, s, nullptr, nullptr, M, KQ, KE}); rc < 0) return rc;   // (1: M == 0, N's rules still apply)
+  const int64_t Kp = arcq_mx_k_padded(KQ + KE);
+  if (const int rc = gemm_checks(g, nullptr, s, nullptr, s, s, nullptr, M, N, Kp, nullptr, nullptr, out_dtype)) return rc;   // 1: nothing to do
+  if (const int rc = quant_checks(q, QuantArgs{there(X), rms ? there(Wn) : nullptr, there(idx), nullptr, nullptr, M, KQ, KE})) return rc;
+  if (const int rc = gemm_checks(g, nullptr, there(MRW), nullptr, there(MRSF), there(D), nullptr, M, N, Kp, nullptr, nullptr, out_dtype)) return rc;
+  if (!gemm_mx_linear_supported(kind, M, N, KQ, KE))
+    return fail(ARCQ_ERR_UNSUPPORTED, "%s: no fused kernel for this shape: need 1 <= M <= 16 and %lld <= %d bytes of LDS (M=%lld N=%lld KQ=%lld KE=%lld)",
+                who, (long long)gemm_mx_linear_lds_bytes(kind, KQ, KE), 81920, (long long)M, (long long)N, (long long)KQ, (long long)KE);
+  if (const int rc = quant_checks(q, QuantArgs{X, rms ? Wn : nullptr, idx, nullptr, nullptr, M, KQ, KE})) return rc;
+  return gemm_checks(g, nullptr, MRW, nullptr, MRSF, D, nullptr, M, N, Kp, bias, residual, out_dtype);
+}
+
+int arcq_mx_linear_fused_supported(int kind, int64_t M, int64_t N, int64_t KQ, int64_t KE) { return gemm_mx_linear_supported(kind, M, N, KQ, KE); }
+int64_t arcq_mx_linear_fused_workgroups(int kind, int64_t N, int64_t KQ, int64_t KE) { return gemm_mx_linear_workgroups(kind, N, KQ, KE); }
+int64_t arcq_mx_linear_fused_lds_bytes(int kind, int64_t KQ, int64_t KE) {
+  return (KQ <= 0 || KE < 0 || KQ > 32767 || KE > KQ) ? 0 : gemm_mx_linear_lds_bytes(kind, KQ, KE);
+}
+
+int arcq_mx_linear_rmsnorm_repacked(const void* X, const void* Wn, float eps, const int16_t* reorder_index, const uint8_t* MRW, const uint8_t* MRSF,
+                                    void* D, int64_t M, int64_t N, int64_t KQ, int64_t KE, float alpha_host, const float* alpha_dev, const void* bias,
+                                    const void* residual, int out_dtype, void* stream) {
+  const char* who = "arcq_mx_linear_rmsnorm_repacked";
+  if (const int rc = mx_linear_checks(who, ARCQ_SRC_RMSNORM, false, X, Wn, reorder_index, MRW, MRSF, D, M, N, KQ, KE, bias, residual, out_dtype))
+    return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_linear(ARCQ_SRC_RMSNORM, false, X, Wn, eps, reorder_index, MRW, MRSF, D, M, N, KQ, KE, alpha_host, alpha_dev, bias, residual, out_dtype,
+                        who, (hipStream_t)stream);
+}
+
+int arcq_mx_linear_rmsnorm_silu_repacked(const void* X, const void* Wn, float eps, const int16_t* reorder_index, const uint8_t* MRW, const uint8_t* MRSF,
+                                         void* ACT, int64_t M, int64_t N, int64_t KQ, int64_t KE, float alpha_host, const float* alpha_dev,
+                                         const void* bias, void* stream) {
+  const char* who = "arcq_mx_linear_rmsnorm_silu_repacked";
+  if (const int rc = mx_linear_checks(who, ARCQ_SRC_RMSNORM, true, X, Wn, reorder_index, MRW, MRSF, ACT, M, N, KQ, KE, bias, nullptr, ARCQ_OUT_BF16))
+    return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_linear(ARCQ_SRC_RMSNORM, true, X, Wn, eps, reorder_index, MRW, MRSF, ACT, M, N, KQ, KE, alpha_host, alpha_dev, bias, nullptr,
+                        ARCQ_OUT_BF16, who, (hipStream_t)stream);
+}
+
+int arcq_mx_linear_quantize_repacked(const void* X, const int16_t* reorder_index, const uint8_t* MRW, const uint8_t* MRSF, void* D, int64_t M, int64_t N,
+                                     int64_t KQ, int64_t KE, float alpha_host, const float* alpha_dev, const void* bias, const void* residual,
+                                     int out_dtype, void* stream) {
+  const char* who = "arcq_mx_linear_quantize_repacked";
+  if (const int rc = mx_linear_checks(who, ARCQ_SRC_PLAIN, false, X, nullptr, reorder_index, MRW, MRSF, D, M, N, KQ, KE, bias, residual, out_dtype))
+    return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx_linear(ARCQ_SRC_PLAIN, false, X, nullptr, 0.0f, reorder_index, MRW, MRSF, D, M, N, KQ, KE, alpha_host, alpha_dev, bias, residual,
+                        out_dtype, who, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -73,6 +73,28 @@ __device__ __forceinline__ void rms_stage_row(uint16_t* row_lds, const uint16_t*
   }
 }
 
+// The strides 128 .. 1 of the reduction tree below, by ONE whole wave: lane `tid` (0 .. 63) passes the stride-256 sums of columns tid, tid + 64, tid + 128 and
+// tid + 192; lane 0 returns the row's sum of squares (other lanes: not the sum).
+__device__ __forceinline__ float rms_tree_wave(float x0, float x1, float x2, float x3, int bdx, const int tid) {
+  const float y0 = (tid + 128 < bdx) ? x0 + x2 : x0;                 // stride 128: columns tid and tid + 64
+  const float y1 = (tid + 192 < bdx) ? x1 + x3 : x1;
+  float z = (tid + 64 < bdx) ? y0 + y1 : y0;                         // stride 64
+  const float up = __shfl_down(z, 32, 64);
+  if (tid < 32 && tid + 32 < bdx) z = z + up;                        // stride 32
+  float val = tid < 32 ? z : 0.0f;
+  val += __shfl_down(val, 16, 64);                                       // lane 0's cone = reference's
+  val += dpp_row_shl<8>(val);                                            // strides 8 .. 1 stay inside lane 0's row of 16 (DPP)
+  val += dpp_row_shl<4>(val);
+  val += dpp_row_shl<2>(val);
+  val += dpp_row_shl<1>(val);
+  return val;
+}
+// rstd of a row from its sum of squares
+__device__ __forceinline__ float rms_rstd_of(float sumsq, int KQ, float eps) {
+  const float var = sumsq / (float)KQ + eps;                             // rmsnorm.cu:157
+  return (float)(1.0 / sqrt((double)var));                               // oracle assumption A4
+}
+
 // Sum of squares of one row in the reference's association order (rmsnorm.cu:113-154), so that the
 // fp32 result is bit-identical to the oracle's: virtual thread v in [0, bdx = KQ/16) owns the 16-byte
 // chunks v and bdx + v and accumulates their 16 squares sequentially (the caller passes the partial sums of
@@ -88,25 +110,54 @@ __device__ __forceinline__ float rms_rstd_tree(float* s, int bdx, float p_lo, fl
   if (tid < bdx) s[tid] = s256;
   __syncthreads();                                                     // (also publishes the staged row)
   if (tid < 64) {
-    const float x0 = s[tid], x1 = s[tid + 64], x2 = s[tid + 128], x3 = s[tid + 192];
-    const float y0 = (tid + 128 < bdx) ? x0 + x2 : x0;                 // stride 128: columns tid and tid + 64
-    const float y1 = (tid + 192 < bdx) ? x1 + x3 : x1;
-    float z = (tid + 64 < bdx) ? y0 + y1 : y0;                         // stride 64
-    const float up = __shfl_down(z, 32, 64);
-    if (tid < 32 && tid + 32 < bdx) z = z + up;                        // stride 32
-    float val = tid < 32 ? z : 0.0f;
-    val += __shfl_down(val, 16, 64);                                       // lane 0's cone = reference's
-    val += dpp_row_shl<8>(val);                                            // strides 8 .. 1 stay inside lane 0's row of 16 (DPP)
-    val += dpp_row_shl<4>(val);
-    val += dpp_row_shl<2>(val);
-    val += dpp_row_shl<1>(val);
-    if (tid == 0) {
-      const float var = val / (float)KQ + eps;                             // rmsnorm.cu:157
-      s[256] = (float)(1.0 / sqrt((double)var));                           // oracle assumption A4
-    }
+    const float val = rms_tree_wave(s[tid], s[tid + 64], s[tid + 128], s[tid + 192], bdx, tid);
+    if (tid == 0) s[256] = rms_rstd_of(val, KQ, eps);
   }
   __syncthreads();
   return s[256];
+}
+// The same row, the same sums, by ONE wave and without a barrier (the prologue of gemm_mx_linear_rw.hip, where every wave of the workgroup
+// has a row of its own): lane l plays the virtual threads l, l + 64, ... (<= 8 of them), so the strides 256, 128 and 64 add values the
+// lane holds itself.  Stages the row in the padded LDS layout as rms_stage_row does and returns rstd in every lane.
+__device__ __forceinline__ float rms_stage_row_wave(uint16_t* row_lds, const uint16_t* xrow, int bdx, int KQ, float eps, const int lane) {
+  float p[8];
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {                       // two batches of eight chunk loads (32 VGPRs) in flight; KQ <= 4096 needs one
+    uint4 d[4][2];
+    if (256 * half < bdx) {                                    // (uniform)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)                                // clamped, so that the loads leave together (a clamped chunk is not used);
+#pragma unroll
+        for (int it = 0; it < 2; ++it)                           // 32-bit offsets from the wave's uniform row pointer
+          d[k][it] = *reinterpret_cast<const uint4*>(xrow + (uint32_t)min(it * bdx + lane + 64 * (4 * half + k), 2 * bdx - 1) * 8u);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int v = lane + 64 * (4 * half + k);
+      float acc = 0.0f;
+      if (v < bdx) {
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+          lds_put_chunk(row_lds, it * bdx + v, d[k][it]);
+          const uint32_t w4[4] = {d[k][it].x, d[k][it].y, d[k][it].z, d[k][it].w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            float a = bf16_bits_to_f32(w4[j] & 0xffffu), b = bf16_bits_to_f32(w4[j] >> 16);
+            acc = acc + a * a;
+            acc = acc + b * b;
+          }
+        }
+      }
+      p[4 * half + k] = acc;
+    }
+  }
+  float s[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s[k] = (lane + 64 * k + 256 < bdx) ? p[k] + p[k + 4] : p[k];      // stride 256
+  const float val = rms_tree_wave(s[0], s[1], s[2], s[3], bdx, lane);
+  float rstd = 0.0f;
+  if (lane == 0) rstd = rms_rstd_of(val, KQ, eps);                        // (one lane: the double-precision evaluation is ~35 half-rate instructions)
+  return __shfl(rstd, 0, 64);
 }
 
 }  // namespace arcq

@@ -121,6 +121,12 @@ class QLinear:
         return self.W.numel() + self.out_f * (self.in_f + self.KE) // 16
 
 
+# What mx_fused_linears=True / --mx-fused-linears without a list selects: the linears whose fused call beat the two-launch chain by
+# more than twice the larger band at M = 4 on MI355X (tools/mx_linear_bench.py, profiles/mxfp4_linear_fused.json).  None
+# did (o tied, q|k|v and gate|up lost 2.2 and 1.7 us), so the selection is empty: fusing a linear takes naming it.
+MX_FUSED_LINEARS_DEFAULT = ""
+
+
 class DecoderModel:
     """fused=False: the reference's call structure (model/qLlamaLayer.py: separate q/k/v and gate/up GEMMs, torch
     abs/max/div before each activation quantise, torch residual adds).  fused=True: q|k|v and gate|up as one GEMM each,
@@ -138,7 +144,7 @@ class DecoderModel:
     def __init__(self, cfg: ModelConfig, batch: int, max_len: int, device, fused: bool = False, attention: str = "current",
                  repacked_only: bool = False, quant_type: str = "NVFP4", mx_quantised_epilogue: bool = False, kv_cache: str = "bf16",
                  kv_fused_step: bool = False, kv_paged_prefill: bool = False, mx_repacked_decode: bool = False,
-                 mx_repacked_only: bool = False, rope: bool = False, rope_theta: float = 1e6, rope_tables=None):
+                 mx_repacked_only: bool = False, mx_fused_linears=None, rope: bool = False, rope_theta: float = 1e6, rope_tables=None):
         """attention="current": what benchmarks/modeling_arc.py:169-198 times -- K/V are appended to the cache and each
         sequence attends (causally) over its CURRENT tokens only; attention="cache": attend over the whole KV cache.
         repacked_only (fused=True only): every linear keeps ONLY its repacked weight -- the reference-layout copy is released after
@@ -151,6 +157,12 @@ class DecoderModel:
         mx_repacked_only (quant_type="MXFP4", fused=True only, not with mx_repacked_decode): every linear keeps ONLY its repacked weight and
         every GEMM, at any token count, runs over it (agemm.mx_matmul_rw, mx.matmul_silu_mul_rw; with mx_quantised_epilogue the gate|up call is
         mx.matmul_silu_mul_quantize_rw).  Same logits, bit for bit, at half of mx_repacked_decode's weight memory.
+        mx_fused_linears (needs mx_repacked_decode or mx_repacked_only): a subset of "qkv,o,gateup" (a string, or True for
+        MX_FUSED_LINEARS_DEFAULT) -- in a call of at most 16 tokens for which mx.linear_fused_supported holds, those linears run their
+        activation quantiser as the prologue of the repacked GEMM (mx.linear_rmsnorm_repacked, mx.linear_quantize_repacked,
+        mx.linear_rmsnorm_silu_repacked): one launch instead of two; every other call takes the unfused path.  Same logits, bit for bit.
+        down is never fused (an intermediate_size-wide prologue in every workgroup), and gate|up not together with mx_quantised_epilogue
+        (that kernel has no prologue), nor with mx_decode_route = "quantiser" (forward raises: the fused gate|up is the "epilogue" route's).
         kv_cache="int4" (attention="cache", head dimension 128): the reference's int4 paged cache (arcquant_amd.kvcache)
         instead of the dense bf16 one -- a prefill writes its k / v through init_kv_quantize_i4, a decode step appends with
         append_kv_quantize_i4 and attends with batch_decode_i4.  "bf16" (default) is the dense cache.
@@ -194,6 +206,18 @@ class DecoderModel:
         if mx_repacked_only and (quant_type != "MXFP4" or not fused or mx_repacked_decode):
             raise ValueError("DecoderModel: mx_repacked_only needs quant_type='MXFP4' and fused=True, and replaces mx_repacked_decode (it keeps "
                              "the repacked copy alone; NVFP4 has repacked_only)")
+        if mx_fused_linears is True:
+            mx_fused_linears = MX_FUSED_LINEARS_DEFAULT
+        mx_fuse = frozenset(filter(None, (mx_fused_linears or "").split(",")))
+        if mx_fuse - {"qkv", "o", "gateup"}:
+            raise ValueError(f"DecoderModel: mx_fused_linears must be a subset of 'qkv,o,gateup' (down is not fused), got {mx_fused_linears!r}")
+        if mx_fuse and not (mx_repacked_decode or mx_repacked_only):
+            raise ValueError("DecoderModel: mx_fused_linears needs mx_repacked_decode or mx_repacked_only (the fused linears run over the "
+                             "repacked weight)")
+        if "gateup" in mx_fuse and mx_quantised_epilogue:
+            raise ValueError("DecoderModel: mx_fused_linears='gateup' has no form of the quantising epilogue (mx_quantised_epilogue): that "
+                             "kernel has no prologue")
+        self.mx_fuse = mx_fuse
         self.quant_type = quant_type
         self.mx_quantised_epilogue = mx_quantised_epilogue
         self.mx_repacked_only = mx_repacked_only
@@ -399,26 +423,47 @@ class DecoderModel:
         the *_rw forms); fused=False, the
         reference's call structure (model/qQwenLayer.py): separate q, k, v and gate, up GEMMs, bias / SiLU*up / residual as torch ops.
         Every activation quantiser is one launch either way -- MXFP4 has no per-tensor scale to find first."""
+        if "gateup" in self.mx_fuse and self.mx_decode_route != "epilogue":
+            raise ValueError("DecoderModel: mx_fused_linears='gateup' is the fused form of the 'epilogue' decode route (SiLU*up in the GEMM); "
+                             f"mx_decode_route={self.mx_decode_route!r} has none")
         cfg = self.cfg
         bsz, q_len = tokens.shape
         h, ke, hd = cfg.hidden_size, cfg.select_num, cfg.hidden_size // cfg.num_heads
         T = bsz * q_len
         hcur = F.embedding(tokens, self.embed).reshape(T, h)
+        fz = self.mx_fuse if T <= mx.MX_LINEAR_MAX_M else ()
+
+        def fuses(name, kind, lin):                         # this call's `name` linear runs its quantiser as the GEMM's prologue
+            return name in fz and mx.linear_fused_supported(kind, T, lin.out_f, h, ke)
+
         for li, L in enumerate(self.layers):
-            A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln1"], cfg.eps, self.idx_h, ke)
             if self.fused:
-                qkv = L["qkv"].matmul(A, SFA, 1.0)
+                Q = L["qkv"]
+                if fuses("qkv", mx.SRC_RMSNORM, Q):
+                    qkv = mx.linear_rmsnorm_repacked(hcur, L["ln1"], cfg.eps, self.idx_h, ke, Q.MRW, Q.MRSF, 1.0, Q.out_f, bias=Q.bias)
+                else:
+                    A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln1"], cfg.eps, self.idx_h, ke)
+                    qkv = Q.matmul(A, SFA, 1.0)
                 if self.kv_cache == "int4":
                     att = self._attention_int4(li, qkv[:, :h], qkv[:, h:2 * h], qkv[:, 2 * h:], qkv, pos, bsz, q_len)
                 elif q_len == 1 and hd == 128 and self.decode_attention == "stream":
                     att = self._attn_decode_stream(qkv, L, pos)
                 else:
                     att = self._attention_torch(L, qkv[:, :h], qkv[:, h:2 * h], qkv[:, 2 * h:], qkv, pos, bsz, q_len)
-                qa, sfa = agemm.mx_reorder_quantize_x(att, self.idx_h, ke)
-                hcur = L["o"].matmul(qa, sfa, 1.0, residual=hcur)
-                A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln2"], cfg.eps, self.idx_h, ke)
+                O_ = L["o"]
+                if fuses("o", mx.SRC_PLAIN, O_):
+                    hcur = mx.linear_quantize_repacked(att, self.idx_h, ke, O_.MRW, O_.MRSF, 1.0, O_.out_f, bias=O_.bias, residual=hcur)
+                else:
+                    qa, sfa = agemm.mx_reorder_quantize_x(att, self.idx_h, ke)
+                    hcur = O_.matmul(qa, sfa, 1.0, residual=hcur)
                 Gt = L["gateup"]                            # one weight with gate and up rows interleaved (g0, u0, g1, u1, ...)
-                if self.mx_quantised_epilogue and Gt.W is None:
+                fuse_gu = fuses("gateup", mx.SRC_RMSNORM, Gt)
+                if not fuse_gu:
+                    A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln2"], cfg.eps, self.idx_h, ke)
+                if fuse_gu:
+                    act = mx.linear_rmsnorm_silu_repacked(hcur, L["ln2"], cfg.eps, self.idx_h, ke, Gt.MRW, Gt.MRSF, 1.0, Gt.out_f, bias=Gt.bias)
+                    qa, sfa = agemm.mx_reorder_quantize_x(act, self.idx_i, ke)
+                elif self.mx_quantised_epilogue and Gt.W is None:
                     qa, sfa = mx.matmul_silu_mul_quantize_rw(A, Gt.MRW, SFA, Gt.MRSF, 1.0, Gt.out_f, ke, bias=Gt.bias)
                 elif self.mx_quantised_epilogue:
                     qa, sfa = mx.matmul_silu_mul_quantize(A, Gt.W, SFA, Gt.SFW, 1.0, ke, bias=Gt.bias)
@@ -435,6 +480,7 @@ class DecoderModel:
                     qa, sfa = agemm.mx_reorder_quantize_x(act, self.idx_i, ke)
                 hcur = L["down"].matmul(qa, sfa, 1.0, residual=hcur)
             else:
+                A, SFA = mx.rmsnorm_quantize_x(hcur, L["ln1"], cfg.eps, self.idx_h, ke)
                 q, k, v = (self._ref_linear_mx(L[n], A, SFA) for n in ("q", "k", "v"))
                 att = (self._attention_int4(li, q, k, v, None, pos, bsz, q_len) if self.kv_cache == "int4" else
                        self._attention_torch(L, q, k, v, None, pos, bsz, q_len))
@@ -575,7 +621,7 @@ class DecoderModel:
 def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cuda:0", repeats=3, layers=None, fused=False,
                  attention="current", repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False, kv_cache="bf16",
                  kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6, mx_repacked_decode=False,
-                 mx_repacked_only=False):
+                 mx_repacked_only=False, mx_fused_linears=None):
     """Decode tok/s with the decode step replayed from a HIP graph (attention window fixed at prefill+steps).  repacked_only: one
     weight copy per linear (DecoderModel); the result then also reports it and the device memory the built model holds.  mx_repacked_only:
     the same for quant_type="MXFP4"."""
@@ -588,7 +634,7 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         model = DecoderModel(cfg, batch, prefill + steps + 1, device, fused=fused, attention=attention, repacked_only=repacked_only,
                              quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
                              kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mx_repacked_decode,
-                             mx_repacked_only=mx_repacked_only)
+                             mx_repacked_only=mx_repacked_only, mx_fused_linears=mx_fused_linears)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         t0 = time.perf_counter()
@@ -651,6 +697,8 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
         res["mx_repacked_decode"] = True
     if mx_repacked_only:
         res.update(mx_repacked_only=True, model_resident_bytes=int(model_bytes))
+    if model.mx_fuse:
+        res["mx_fused_linears"] = ",".join(sorted(model.mx_fuse))
     if kv_cache != "bf16":
         res["kv_cache"] = kv_cache
     if kv_fused_step:
@@ -665,7 +713,7 @@ def bench_decode(name="qwen2.5-7b", batch=4, prefill=1024, steps=16, device="cud
 def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, device="cuda:0", repeats=10, warmup=2, steps=4,
                    fused=True, attention="cache", graph=True, layers=None, repacked_only=False, quant_type="NVFP4", mx_quantised_epilogue=False,
                    kv_cache="bf16", kv_fused_step=False, kv_paged_prefill=False, rope=False, rope_theta=1e6, mx_repacked_decode=False,
-                   mx_repacked_only=False):
+                   mx_repacked_only=False, mx_fused_linears=None):
     """The reference's latency protocol (benchmarks/benchmark_e2e_arc.py): three timed modules -- prefill (:133-140), decode
     for `decode_steps` steps over a GROWING cache (:142-155) and prefill + decode (:157-166) -- each run `warmup` times
     untimed and `steps` times timed between two device synchronisations, repeated `repeats` times (:81-115); reported as
@@ -698,7 +746,7 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         model = DecoderModel(cfg, batch, prefill + decode_steps, device, fused=fused, attention=attention, repacked_only=repacked_only,
                              quant_type=quant_type, mx_quantised_epilogue=mx_quantised_epilogue, kv_cache=kv_cache, kv_fused_step=kv_fused_step,
                              kv_paged_prefill=kv_paged_prefill, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mx_repacked_decode,
-                             mx_repacked_only=mx_repacked_only)
+                             mx_repacked_only=mx_repacked_only, mx_fused_linears=mx_fused_linears)
         model_bytes = torch.cuda.memory_allocated(device) - mem0
         tok = torch.randint(100, 200, (batch, prefill), device=device)
         nxt = torch.full((batch, 1), 100, device=device, dtype=torch.int64)          # benchmark_e2e_arc.py:150
@@ -746,6 +794,8 @@ def bench_protocol(name="qwen2.5-7b", batch=4, prefill=1024, decode_steps=128, d
         res["mx_repacked_decode"] = True
     if mx_repacked_only:
         res.update(mx_repacked_only=True, model_resident_bytes=int(model_bytes))
+    if model.mx_fuse:
+        res["mx_fused_linears"] = ",".join(sorted(model.mx_fuse))
     if kv_cache != "bf16":
         res["kv_cache"] = kv_cache
     if kv_fused_step:
@@ -924,17 +974,27 @@ if __name__ == "__main__":
     mro = "--mx-repacked-only" in sys.argv       # MXFP4, the fused model only: one weight copy per linear, every GEMM over the repacked weight
     if mro and (qt != "MXFP4" or mrd):
         sys.exit("--mx-repacked-only needs --quant-type MXFP4 and replaces --mx-repacked-decode")
+    mfl = None                                   # --mx-fused-linears[=LIST]: LIST a subset of qkv,o,gateup; without one, the linears measured faster
+    for arg in sys.argv:
+        if arg == "--mx-fused-linears" or arg.startswith("--mx-fused-linears="):
+            mfl = arg.partition("=")[2] if "=" in arg else MX_FUSED_LINEARS_DEFAULT
+            if set(filter(None, mfl.split(","))) - {"qkv", "o", "gateup"}:
+                sys.exit("--mx-fused-linears takes a subset of qkv,o,gateup")
+    if mfl and not (mrd or mro):
+        sys.exit("--mx-fused-linears needs --mx-repacked-decode or --mx-repacked-only")
+    if mfl and qe and "gateup" in mfl.split(","):
+        sys.exit("--mx-fused-linears=gateup excludes --mx-quantised-epilogue")
     if "--protocol" in sys.argv:      # the reference's own benchmark protocol (growing cache, mean +- 1.96 sigma)
         for graph in (True, False):
             print(json.dumps(bench_protocol(name, graph=graph, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
                                             kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mrd,
-                                            mx_repacked_only=mro)), flush=True)
+                                            mx_repacked_only=mro, mx_fused_linears=mfl)), flush=True)
             torch.cuda.empty_cache()
     else:
         for fused, att in ((False, "current"), (True, "current"), (True, "cache")):
-            if ((ro or qe or mrd or mro) and not fused) or (kvc == "int4" and att != "cache"):
+            if ((ro or qe or mrd or mro or mfl) and not fused) or (kvc == "int4" and att != "cache"):
                 continue
             print(json.dumps(bench_decode(name, fused=fused, attention=att, repacked_only=ro, quant_type=qt, mx_quantised_epilogue=qe, kv_cache=kvc,
                                           kv_fused_step=kfs, kv_paged_prefill=kpp, rope=rope, rope_theta=rope_theta, mx_repacked_decode=mrd,
-                                          mx_repacked_only=mro)), flush=True)
+                                          mx_repacked_only=mro, mx_fused_linears=mfl)), flush=True)
             torch.cuda.empty_cache()

@@ -319,6 +319,111 @@ def matmul_silu_mul_quantize(A: torch.Tensor, B: torch.Tensor, SFA: torch.Tensor
     return QX, SFX
 
 
+# ---- the fused decode linears (include/arcq.h "MXFP4 fused decode linear"): the activation quantiser as the prologue of the repacked
+# decode GEMM, one launch, bit for bit the two calls it replaces.  ``linear_fused_supported`` is also agemm.mx_linear_fused_supported.
+SRC_RMSNORM, SRC_PLAIN = 1, 3
+MX_LINEAR_MAX_M = 16
+
+
+@functools.lru_cache(maxsize=4096)
+def linear_fused_supported(kind: int, M: int, N: int, KQ: int, KE: int) -> bool:
+    """Whether the fused MXFP4 decode linear can run this shape: a valid shape for ``kind`` (SRC_RMSNORM: 2048 <= KQ <= 8192; SRC_PLAIN),
+    1 <= M <= 16 and an LDS image that leaves two workgroups per CU (``linear_fused_lds_bytes`` <= 81920).  Callers fall back to the
+    quantiser followed by ``mx_matmul_repacked`` / ``matmul_silu_mul_repacked`` otherwise."""
+    return bool(_lib.lib().arcq_mx_linear_fused_supported(int(kind), int(M), int(N), int(KQ), int(KE)))
+
+
+mx_linear_fused_supported = linear_fused_supported
+
+
+def linear_fused_workgroups(kind: int, N: int, KQ: int, KE: int) -> int:
+    """Workgroups of a fused launch (pure host arithmetic): min(N / 16, 512); workgroup g takes the row blocks g, g + grid, ...; 0 for an
+    unsupported shape."""
+    return int(_lib.lib().arcq_mx_linear_fused_workgroups(int(kind), int(N), int(KQ), int(KE)))
+
+
+def linear_fused_lds_bytes(kind: int, KQ: int, KE: int) -> int:
+    """The LDS a fused launch of this K takes (the budget formula of include/arcq.h)."""
+    return int(_lib.lib().arcq_mx_linear_fused_lds_bytes(int(kind), int(KQ), int(KE)))
+
+
+def _need_mx_linear(who, kind, X, W, reorder_index, KE, MRW, MRSF, N):
+    # X [M, KQ] bf16 (and the norm weight) against the repacked MXFP4 weight of N rows over Kp = mx_k_padded(KQ + KE) -> (M, N, KQ, KE)
+    _need(X, torch.bfloat16, "X", 2)
+    if kind == SRC_RMSNORM:
+        _need(W, torch.bfloat16, "W", 1)
+    _need(reorder_index, torch.int16, "reorder_index", 1)
+    _need(MRW, torch.uint8, "MRW", 1)
+    _need(MRSF, torch.uint8, "MRSF", 1)
+    (M, KQ), KE, N = X.shape, int(KE), int(N)
+    if reorder_index.numel() != KQ or (kind == SRC_RMSNORM and W.numel() != KQ):
+        raise RuntimeError(f"{who}: W / reorder_index must have X.shape[1] = {KQ} entries")
+    if KQ % 64 or KE % 64 or KE < 0 or KE > KQ or KQ > 32767 or (kind == SRC_RMSNORM and not (2048 <= KQ <= 8192)):
+        raise RuntimeError(f"Value error in {who}: KQ={KQ}, KE={KE} is not valid" + (" (2048 <= KQ <= 8192)" if kind == SRC_RMSNORM else ""))
+    if N <= 0 or N % 16:
+        raise RuntimeError(f"{who}: N={N} must be a positive multiple of 16")
+    if (MRW.numel(), MRSF.numel()) != _mx_repacked_bytes(N, mx_k_padded(KQ + KE)):
+        raise RuntimeError(f"{who}: MRW / MRSF do not belong to a [{N}, {mx_k_padded(KQ + KE)}] MXFP4 weight")
+    if not linear_fused_supported(kind, M, N, KQ, KE):
+        raise RuntimeError(f"{who}: M={M}, KQ={KQ}, KE={KE} is outside the fused path (1 <= M <= {MX_LINEAR_MAX_M} and the LDS budget; see "
+                           f"linear_fused_supported)")
+    return M, N, KQ, KE
+
+
+def linear_rmsnorm_repacked(X: torch.Tensor, W: torch.Tensor, eps: float, reorder_index: torch.Tensor, KE: int, MRW: torch.Tensor,
+                            MRSF: torch.Tensor, scale, N: int, *, bias=None, residual=None, out_dtype=torch.bfloat16, out=None,
+                            scale_host: float = 1.0):
+    """``mx_matmul_repacked(*rmsnorm_quantize_x(X, W, eps, reorder_index, KE), ...)`` in ONE launch for 1 <= M <= 16: the RMSNorm and the
+    MXFP4-ARC quantiser run as the GEMM's prologue and nothing quantised is written to memory.  Bit for bit the result of the two
+    calls.  ``W`` is the norm weight; ``residual`` may be ``out``."""
+    who = "mx.linear_rmsnorm_repacked"
+    M, N, KQ, KE = _need_mx_linear(who, SRC_RMSNORM, X, W, reorder_index, KE, MRW, MRSF, N)
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, X, who)
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device(who, X, W, reorder_index, MRW, MRSF, alpha_dev, out, bias, residual)
+    with _on(X.device):
+        st = _lib.lib().arcq_mx_linear_rmsnorm_repacked(X.data_ptr(), W.data_ptr(), float(eps), reorder_index.data_ptr(), MRW.data_ptr(),
+                                                        MRSF.data_ptr(), out.data_ptr(), M, N, KQ, KE, alpha_host, alpha_p, bias_p, residual_p, oc,
+                                                        _stream(X))
+    _lib.check(st, who)
+    return out
+
+
+def linear_rmsnorm_silu_repacked(X: torch.Tensor, W: torch.Tensor, eps: float, reorder_index: torch.Tensor, KE: int, MRW: torch.Tensor,
+                                 MRSF: torch.Tensor, scale, N: int, *, bias=None, out=None, scale_host: float = 1.0):
+    """``matmul_silu_mul_repacked(*rmsnorm_quantize_x(X, W, eps, reorder_index, KE), ...)`` in ONE launch for 1 <= M <= 16 (the gate|up
+    weight's rows interleave gate and up).  Returns ``act`` bf16 [M, N/2], bit for bit the result of the two calls."""
+    who = "mx.linear_rmsnorm_silu_repacked"
+    M, N, KQ, KE = _need_mx_linear(who, SRC_RMSNORM, X, W, reorder_index, KE, MRW, MRSF, N)
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, _ = _out(out, M, N // 2, torch.bfloat16, X, who)
+    bias_p = _opt(bias, torch.bfloat16, "bias", (N,))
+    _same_device(who, X, W, reorder_index, MRW, MRSF, alpha_dev, out, bias)
+    with _on(X.device):
+        st = _lib.lib().arcq_mx_linear_rmsnorm_silu_repacked(X.data_ptr(), W.data_ptr(), float(eps), reorder_index.data_ptr(), MRW.data_ptr(),
+                                                             MRSF.data_ptr(), out.data_ptr(), M, N, KQ, KE, alpha_host, alpha_p, bias_p, _stream(X))
+    _lib.check(st, who)
+    return out
+
+
+def linear_quantize_repacked(X: torch.Tensor, reorder_index: torch.Tensor, KE: int, MRW: torch.Tensor, MRSF: torch.Tensor, scale, N: int, *,
+                             bias=None, residual=None, out_dtype=torch.bfloat16, out=None, scale_host: float = 1.0):
+    """``mx_matmul_repacked(*agemm.mx_reorder_quantize_x(X, reorder_index, KE), ...)`` in ONE launch for 1 <= M <= 16.  Bit for bit the
+    result of the two calls; ``residual`` may be ``out``."""
+    who = "mx.linear_quantize_repacked"
+    M, N, KQ, KE = _need_mx_linear(who, SRC_PLAIN, X, None, reorder_index, KE, MRW, MRSF, N)
+    alpha_host, alpha_dev, alpha_p = _alpha(scale, scale_host)
+    out, oc = _out(out, M, N, out_dtype, X, who)
+    bias_p, residual_p = _opt(bias, torch.bfloat16, "bias", (N,)), _opt(residual, torch.bfloat16, "residual", (M, N))
+    _same_device(who, X, reorder_index, MRW, MRSF, alpha_dev, out, bias, residual)
+    with _on(X.device):
+        st = _lib.lib().arcq_mx_linear_quantize_repacked(X.data_ptr(), reorder_index.data_ptr(), MRW.data_ptr(), MRSF.data_ptr(), out.data_ptr(), M, N,
+                                                         KQ, KE, alpha_host, alpha_p, bias_p, residual_p, oc, _stream(X))
+    _lib.check(st, who)
+    return out
+
+
 def gate_up_rows(gate_w: torch.Tensor, up_w: torch.Tensor, reorder_index=None, gate_b=None, up_b=None):
     """The gate|up weight of ``matmul_silu_mul`` / ``matmul_silu_mul_quantize`` from the two projections' [KQ2, in_features] weights: rows
     g0, u0, g1, u1, ... where pair j is channel ``reorder_index[j]`` (None: channel j).  With the consumer's reorder_index the GEMM's

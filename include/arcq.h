@@ -388,6 +388,49 @@ int arcq_gemm_mxfp4_rw_silu_mul_quantize(const uint8_t *A, const uint8_t *MRW, c
                                          uint8_t *SFACT, int64_t M, int64_t N, int64_t K, float alpha_host, const float *alpha_dev,
                                          const void *bias, int64_t KE, void *stream);
 
+/* ---- MXFP4 fused decode linear: the activation quantiser runs as the prologue of the repacked decode GEMM -------------------------
+ * One launch replaces  [arcq_mx_rmsnorm_quantize_x | arcq_mx_quantize_x]  ->  arcq_gemm_mxfp4_repacked (+ bias) (+ residual) or
+ * arcq_gemm_mxfp4_repacked_silu_mul of a decode step.  (MRW, MRSF) are those of the repacked weight for (N, Kp), Kp =
+ * arcq_mx_k_padded(KQ + KE).  Every workgroup quantises the M <= 16 token rows itself, with the quantisers' own statements (the
+ * RMSNorm row, the MXFP4 block rule, residual and padding blocks) into an image in LDS, and multiplies every row block it owns from
+ * that image in the decode kernel's sum order: the result is BIT FOR BIT that of the two calls.  Nothing quantised is written to
+ * global memory; no workspace, no host synchronisation, capturable in a HIP graph.
+ *   kind       ARCQ_SRC_RMSNORM (the row is bf16(x * wn * rstd)) or ARCQ_SRC_PLAIN (the row is X); ARCQ_SRC_DYNAMIC has no MXFP4
+ *              meaning: there is no per-tensor scale.
+ *   shape      KQ % 64 == 0, KE % 64 == 0, 0 <= KE <= KQ <= 32767; 2048 <= KQ <= 8192 for ARCQ_SRC_RMSNORM; N % 16 == 0.
+ *   supported  arcq_mx_linear_fused_supported(kind, M, N, KQ, KE) is 1 when the shape is valid, 1 <= M <= 16 and the kernel's LDS fits two
+ *              workgroups per CU with at least one row staged:   steps * 1088 + 32 + max(16384, (R + w) * row) <= 81920 bytes   for
+ *              R = 1, where steps = Kp / 128 (1 KB of codes and 64 scale bytes per K step of the image), row = KQ * 9 / 4 (a padded
+ *              row of the quantisers' staging), w = 1 for ARCQ_SRC_RMSNORM (the norm weight) and 0 for ARCQ_SRC_PLAIN.  A launch
+ *              stages R = the largest of 8, 4, 2, 1 rows per pass that satisfies it (arcq_mx_linear_fused_lds_bytes returns the left
+ *              side for that R).  Callers fall back to the two calls otherwise.
+ *   grid       arcq_mx_linear_fused_workgroups(kind, N, KQ, KE): min(N / 16, 512) workgroups, each of which takes the row blocks g,
+ *              g + grid, ... (0 for an unsupported shape; pure host arithmetic).
+ *   Status, all before any HIP call, in this order: ARCQ_ERR_SHAPE for a shape outside the rules above (the quantiser's rules first,
+ *   then M or N < 0 and N % 16); ARCQ_ERR_SHAPE for a bad out_dtype; M == 0 or N == 0 returns ARCQ_OK; ARCQ_ERR_NULL for a NULL operand
+ *   (X, the norm weight, reorder_index; then MRW, MRSF, D / ACT); ARCQ_ERR_UNSUPPORTED for a valid shape that
+ *   arcq_mx_linear_fused_supported refuses; ARCQ_ERR_SHAPE for a misaligned pointer (X, the norm weight, reorder_index, MRW, D / ACT 16
+ *   bytes; MRSF 4 bytes; bias, residual 2 bytes).
+ * It is a capability, not a recommendation: every workgroup repeats the quantisation of all M * KQ elements (see DESIGN.md 3.6 "the
+ * prologue-fused linear" for what was measured on MI355X, the losses included). */
+#define ARCQ_SRC_PLAIN 3     /* beside ARCQ_SRC_RMSNORM */
+int arcq_mx_linear_fused_supported(int kind, int64_t M, int64_t N, int64_t KQ, int64_t KE);
+int64_t arcq_mx_linear_fused_workgroups(int kind, int64_t N, int64_t KQ, int64_t KE);
+int64_t arcq_mx_linear_fused_lds_bytes(int kind, int64_t KQ, int64_t KE);   /* the left side of the budget above */
+/* D = alpha * matmul(mx_rmsnorm_quantize_x(X, Wn, eps, reorder_index, KE), W) (+ bias) (+ residual, which may alias D); arguments as in
+ * arcq_mx_rmsnorm_quantize_x and arcq_gemm_mxfp4_repacked, alpha = alpha_host * (alpha_dev ? *alpha_dev : 1). */
+int arcq_mx_linear_rmsnorm_repacked(const void *X, const void *Wn, float eps, const int16_t *reorder_index, const uint8_t *MRW,
+                                    const uint8_t *MRSF, void *D, int64_t M, int64_t N, int64_t KQ, int64_t KE, float alpha_host,
+                                    const float *alpha_dev, const void *bias, const void *residual, int out_dtype, void *stream);
+/* The gate|up projection: the weight's rows interleave gate and up; ACT = bf16 [M, N/2] as arcq_gemm_mxfp4_repacked_silu_mul writes it. */
+int arcq_mx_linear_rmsnorm_silu_repacked(const void *X, const void *Wn, float eps, const int16_t *reorder_index, const uint8_t *MRW,
+                                         const uint8_t *MRSF, void *ACT, int64_t M, int64_t N, int64_t KQ, int64_t KE, float alpha_host,
+                                         const float *alpha_dev, const void *bias, void *stream);
+/* D = alpha * matmul(mx_quantize_x(X, reorder_index, KE), W) (+ bias) (+ residual, which may alias D). */
+int arcq_mx_linear_quantize_repacked(const void *X, const int16_t *reorder_index, const uint8_t *MRW, const uint8_t *MRSF, void *D,
+                                     int64_t M, int64_t N, int64_t KQ, int64_t KE, float alpha_host, const float *alpha_dev,
+                                     const void *bias, const void *residual, int out_dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
