@@ -16,6 +16,8 @@ VARIANT_G16 = 0
 VARIANT_G32 = 1
 OUT_BF16 = 0
 OUT_F32 = 1
+MX_B_E3M2 = 0
+MX_B_E2M1 = 1
 
 # every symbol include/arcq.h declares: (name, restype, argtypes)
 _p, _i64, _i32, _f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
@@ -60,6 +62,10 @@ SYMBOLS = {
     "arcq_mx_quantize_x": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "arcq_mx_quantize_w": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
     "arcq_gemm_mxfp4": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p, _i32, _p, _i64, _p]),
+    "arcq_mx6_code_bytes": (_i64, [_i64, _i64]),
+    "arcq_mx6_quantize_x": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "arcq_mx6_quantize_w": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _p]),
+    "arcq_gemm_mxfp6": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i32, _f32, _p, _p, _p, _i32, _p]),
     "arcq_mx_rmsnorm_quantize_x": (_i32, [_p, _p, _f32, _p, _p, _p, _i64, _i64, _i64, _p]),
     "arcq_mx_silu_mul_quantize_x": (_i32, [_p, _p, _p, _p, _i64, _i64, _i64, _i32, _p]),
     "arcq_gemm_mxfp4_silu_mul": (_i32, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _f32, _p, _p, _p]),

@@ -754,10 +754,17 @@ _FROM_MX = ("MX_REPACKED_MAX_M", "mx_repack_w", "mx_unrepack_w", "mx_repacked_su
             "matmul_silu_mul_rw", "matmul_silu_mul_quantize_rw", "mx_rw_route")
 
 
+_FROM_MX6 = ("mx6_reorder_quantize_x", "mx6_reorder_quantize_w", "mx6_matmul")       # quant_type='MXFP6' (arcquant_amd/mx6.py)
+
+
 def __getattr__(name):
     if name in _FROM_MX:
         from . import mx
         value = globals()[name] = getattr(mx, name)
+        return value
+    if name in _FROM_MX6:
+        from . import mx6
+        value = globals()[name] = getattr(mx6, name)
         return value
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 

@@ -139,6 +139,11 @@ int gemm_mx_silu_mul(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, con
                      float alpha_host, const float* alpha_dev, const void* bias, hipStream_t stream);
 int gemm_mx_silu_mul_quantize(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, uint8_t* QACT, uint8_t* SFACT, int64_t M,
                               int64_t N, int64_t Kp, float alpha_host, const float* alpha_dev, const void* bias, int64_t KE, hipStream_t stream);
+// quantize_mx6.hip / gemm_mx6.hip: the MXFP6 path (arcq.h "MXFP6-ARC"); b_format = ARCQ_MX_B_E3M2 | ARCQ_MX_B_E2M1 (validated by the caller)
+int mx6_quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE, hipStream_t stream);
+int mx6_quantize_w(const void* W, const int16_t* idx, uint8_t* QW, uint8_t* SFW, int64_t N, int64_t KQ, int64_t KE, hipStream_t stream);
+int gemm_mx6(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t Kp, int b_format,
+             float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, hipStream_t stream);
 // gemm_mx_rw.hip: M <= 64 over the MXFP4 repacked weight (arcq.h "MXFP4 repacked weight"); the sums are gemm_mx's, bit for bit
 int64_t gemm_mx_repacked_w_bytes(int64_t N, int64_t Kp);
 int64_t gemm_mx_repacked_sf_bytes(int64_t N, int64_t Kp);

@@ -1,4 +1,4 @@
-// extern "C" entry points of the MXFP4 path (declared in include/arcq.h): layout helpers and argument validation.  Every
+// extern "C" entry points of the MXFP4 and MXFP6 paths (declared in include/arcq.h): layout helpers and argument validation.  Every
 // shape, NULL and alignment check runs before the first HIP call.
 #include <hip/hip_runtime.h>
 
@@ -31,6 +31,29 @@ int arcq_gemm_mxfp4(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, cons
   const int rc = gemm_checks(r, A, B, SFA, SFB, D, nullptr, M, N, K, bias, residual, out_dtype);
   if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
   return gemm_mx(A, B, SFA, SFB, D, M, N, K, alpha_host, alpha_dev, bias, residual, out_dtype, (hipStream_t)stream);
+}
+
+// ---- MXFP6 (arcq.h "MXFP6-ARC"): the quantisers' checks are arcq_mx_quantize_x's, the GEMM's arcq_gemm_mxfp4's after b_format
+int64_t arcq_mx6_code_bytes(int64_t rows, int64_t K) { return rows <= 0 ? 0 : rows * (arcq_mx_k_padded(K) / 4 * 3); }
+
+int arcq_mx6_quantize_x(const void* X, const int16_t* reorder_index, uint8_t* QX, uint8_t* SFX, int64_t M, int64_t KQ, int64_t KE,
+                        void* stream) {
+  return mx6_quantize_x(X, reorder_index, QX, SFX, M, KQ, KE, (hipStream_t)stream);
+}
+
+int arcq_mx6_quantize_w(const void* W, const int16_t* reorder_index, uint8_t* QW, uint8_t* SFW, int64_t N, int64_t KQ, int64_t KE,
+                        void* stream) {
+  return mx6_quantize_w(W, reorder_index, QW, SFW, N, KQ, KE, (hipStream_t)stream);
+}
+
+int arcq_gemm_mxfp6(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t K,
+                    int b_format, float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, void* stream) {
+  GemmRule r{"arcq_gemm_mxfp6"};
+  r.k_mult = 128; r.n_mult = 16; r.max_m = (int64_t)65535 * 128; r.epi_align = 2;
+  if (b_format != ARCQ_MX_B_E3M2 && b_format != ARCQ_MX_B_E2M1) return fail(ARCQ_ERR_SHAPE, "%s: unknown b_format %d", r.who, b_format);
+  const int rc = gemm_checks(r, A, B, SFA, SFB, D, nullptr, M, N, K, bias, residual, out_dtype);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx6(A, B, SFA, SFB, D, M, N, K, b_format, alpha_host, alpha_dev, bias, residual, out_dtype, (hipStream_t)stream);
 }
 
 int arcq_mx_rmsnorm_quantize_x(const void* X, const void* Wn, float eps, const int16_t* reorder_index, uint8_t* QX, uint8_t* SFX, int64_t M,

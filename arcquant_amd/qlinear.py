@@ -7,12 +7,14 @@ Mirrors, with the same names, argument meaning and tuple protocol:
   * ``MXFP4_rmsnorm_quantize_x``  RMSNorm + ``MXFP4_reorder_quantize_x`` in one launch (arcquant_amd/mx.py)
   * ``MXFP4_reorder_quantize_{w,x}``  the packed form of the reference's MXFP4 branch (model/quantize.py:219-268 as called by
     the commented-out model/qLinearLayer.py:58 and model/qQwenLayer.py:81-83), on the block-scaled fp4 MFMA
+  * ``MXFP6_reorder_quantize_{w,x}``  the same with e3m2 elements (quantize_mxfp6_tensor of model/quantize.py), on the scaled MFMA's
+    e3m2 operand form; ``mx6_weight="e2m1"`` keeps the weight at four bits (W4A6)
 
 so that the decoder-layer wrappers of the reference (qLlamaLayer.py / qQwenLayer.py) run unchanged on
 top of ``arcquant_amd.agemm``.  What differs from the reference, deliberately:
   * no ``torch.cuda.synchronize()`` after every op and no ``.item()`` on the scale: the per-tensor scales
     stay on the device (0-dim fp32 tensors) and everything is ordered on torch's current stream;
-  * ``quant_type`` 'NVFP4' and 'MXFP4' are built; 'INT4' (a fake-quant study path of the reference) is not.
+  * ``quant_type`` 'NVFP4', 'MXFP4' and 'MXFP6' are built; 'INT4' (a fake-quant study path of the reference) is not.
     MXFP4 is real packed e2m1 + E8M0 data here, where the reference dequantises it in place (DESIGN.md "MXFP4").
 """
 from __future__ import annotations
@@ -59,6 +61,18 @@ def MXFP4_reorder_quantize_x(x: torch.Tensor, reorder_index: torch.Tensor, selec
     return qx, scale_x, _unit_scale(x)
 
 
+def MXFP6_reorder_quantize_w(w: torch.Tensor, reorder_index: torch.Tensor, select_num: int):
+    """(qw [N, 3 Kp/4] e3m2, scale_w [N, Kp/32] E8M0, scale = 1): ``MXFP4_reorder_quantize_w`` with six-bit elements."""
+    qw, scale_w = agemm.mx6_reorder_quantize_w(w.contiguous(), reorder_index, select_num)
+    return qw, scale_w, _unit_scale(w)
+
+
+def MXFP6_reorder_quantize_x(x: torch.Tensor, reorder_index: torch.Tensor, select_num: int):
+    """(qx [M, 3 Kp/4] e3m2, scale_x [M, Kp/32] E8M0, scale = 1): ``MXFP4_reorder_quantize_x`` with six-bit elements."""
+    qx, scale_x = agemm.mx6_reorder_quantize_x(x.contiguous(), reorder_index, select_num)
+    return qx, scale_x, _unit_scale(x)
+
+
 def MXFP4_rmsnorm_quantize_x(x: torch.Tensor, norm_weight: torch.Tensor, eps: float, reorder_index: torch.Tensor, select_num: int):
     """(qx, scale_x, scale = 1): RMSNorm fused into ``MXFP4_reorder_quantize_x`` (one launch, ``mx.rmsnorm_quantize_x``); the same tuple
     protocol, so the result feeds ``QLinearLayer.forward`` directly."""
@@ -72,7 +86,9 @@ def reorder_quantize_x(x, reorder_index, select_num, quant_type="NVFP4"):
         return NVFP4_reorder_quantize_x(x, reorder_index, select_num)
     if quant_type == "MXFP4":
         return MXFP4_reorder_quantize_x(x, reorder_index, select_num)
-    raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4 and MXFP4 are)")
+    if quant_type == "MXFP6":
+        return MXFP6_reorder_quantize_x(x, reorder_index, select_num)
+    raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4, MXFP4 and MXFP6 are)")
 
 
 def find_qlinear_layers(module, name=""):
@@ -90,7 +106,7 @@ class QLinearLayer(nn.Module):
 
     def __init__(self, originalLayer: nn.Linear, select_num, reorder_index, out_reorder_index=None, quant_type="NVFP4",
                  repack_for_decode: bool = False, repacked_only: bool = False, mx_repack_for_decode: bool = False,
-                 mx_repacked_only: bool = False):
+                 mx_repacked_only: bool = False, mx6_weight: str | None = None):
         """``repack_for_decode`` (extension, default off = the reference's behaviour and memory): additionally keep the
         weight in MFMA-operand-order tiles (``agemm.repack_w``) and use ``agemm.matmul_repacked`` for calls of at most 16
         tokens.  ``repacked_only`` (extension): keep ONLY that copy -- ``W`` / ``scale_w`` are registered as None, every call
@@ -101,12 +117,18 @@ class QLinearLayer(nn.Module):
         ``agemm.mx_matmul_repacked``, longer ones through ``agemm.mx_matmul`` -- the same bits either way.  ``mx_repacked_only``
         (extension, quant_type='MXFP4' only): keep ONLY ``MRW`` / ``MRSF`` -- ``W`` / ``scale_w`` are registered as None and every call, at
         any token count, runs through ``agemm.mx_matmul_rw`` (the same bits again); ``agemm.mx_unrepack_w(MRW, MRSF, out_features, Kp)``
-        rebuilds the reference-layout pair."""
+        rebuilds the reference-layout pair.  ``mx6_weight`` (quant_type='MXFP6' only): the weight's element, "e3m2" (the default:
+        ``MXFP6_reorder_quantize_w``) or "e2m1" (``MXFP4_reorder_quantize_w``: the activations keep six bits, the weight four);
+        either way forward takes ``MXFP6_reorder_quantize_x``'s tuple and runs ``agemm.mx6_matmul``."""
         super().__init__()
-        if quant_type not in ("NVFP4", "MXFP4"):
-            raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4 and MXFP4 are)")
-        if quant_type == "MXFP4" and (repack_for_decode or repacked_only):
-            raise ValueError("repack_for_decode / repacked_only apply to the NVFP4 weight layout only, not to quant_type='MXFP4'")
+        if quant_type not in ("NVFP4", "MXFP4", "MXFP6"):
+            raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4, MXFP4 and MXFP6 are)")
+        if quant_type != "NVFP4" and (repack_for_decode or repacked_only):
+            raise ValueError(f"repack_for_decode / repacked_only apply to the NVFP4 weight layout only, not to quant_type={quant_type!r}")
+        if mx6_weight is not None and quant_type != "MXFP6":
+            raise ValueError("mx6_weight applies to quant_type='MXFP6' only")
+        if quant_type == "MXFP6" and (mx6_weight or "e3m2") not in ("e3m2", "e2m1"):
+            raise ValueError(f"mx6_weight must be 'e3m2' or 'e2m1', got {mx6_weight!r}")
         if mx_repack_for_decode and quant_type != "MXFP4":
             raise ValueError("mx_repack_for_decode applies to quant_type='MXFP4' only (NVFP4 has repack_for_decode / repacked_only)")
         if mx_repacked_only and quant_type != "MXFP4":
@@ -119,12 +141,16 @@ class QLinearLayer(nn.Module):
             self.bias = None
         self.select_num = int(select_num)
         self.quant_type = quant_type
+        self.mx6_weight = (mx6_weight or "e3m2") if quant_type == "MXFP6" else None
         dev = originalLayer.weight.device
         if dev.type != "cuda":
             raise RuntimeError("QLinearLayer: the weight must be on the GPU (quantisation runs there)")
         idx = reorder_index.to(device=dev, dtype=torch.int16)
         w = originalLayer.weight.data.to(torch.bfloat16)
-        quantize_w = MXFP4_reorder_quantize_w if quant_type == "MXFP4" else NVFP4_reorder_quantize_w
+        if quant_type == "MXFP6":
+            quantize_w = MXFP6_reorder_quantize_w if self.mx6_weight == "e3m2" else MXFP4_reorder_quantize_w
+        else:
+            quantize_w = MXFP4_reorder_quantize_w if quant_type == "MXFP4" else NVFP4_reorder_quantize_w
         W, scale_w, scale = quantize_w(w, idx, self.select_num)
         RW, RSF = agemm.repack_w(W, scale_w) if (repack_for_decode or repacked_only) else (None, None)
         MRW, MRSF = agemm.mx_repack_w(W, scale_w) if (mx_repack_for_decode or mx_repacked_only) else (None, None)
@@ -144,7 +170,9 @@ class QLinearLayer(nn.Module):
         # `y = matmul(...); y = y + bias` (model/qLinearLayer.py:74-76): the bias add runs in the GEMM epilogue with the same
         # two roundings (the bf16 product, then the bf16 sum), so the result is bit-identical to the two torch steps
         bias = self.bias if self.bias is None or self.bias.dtype == torch.bfloat16 else None
-        if self.quant_type == "MXFP4" and self.W is None:         # mx_repacked_only: the one copy serves every token count
+        if self.quant_type == "MXFP6":
+            y = agemm.mx6_matmul(qx, self.W, scale_x, self.scale_w, scale * self.scale, b_format=self.mx6_weight, bias=bias)
+        elif self.quant_type == "MXFP4" and self.W is None:         # mx_repacked_only: the one copy serves every token count
             y = agemm.mx_matmul_rw(qx, self.MRW, scale_x, self.MRSF, scale * self.scale, self.out_features, bias=bias)
         elif getattr(self, "MRW", None) is not None and qx.shape[0] <= agemm.MX_REPACKED_MAX_M:
             y = agemm.mx_matmul_repacked(qx, self.MRW, scale_x, self.MRSF, scale * self.scale, self.out_features, bias=bias)

@@ -298,6 +298,43 @@ int arcq_gemm_mxfp4(const uint8_t *A, const uint8_t *B, const uint8_t *SFA, cons
                     int64_t K, float alpha_host, const float *alpha_dev, const void *bias, const void *residual, int out_dtype,
                     void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- MXFP6-ARC (quant_type='MXFP6': quantize_mxfp6_tensor of the reference, model/quantize.py) ------------------------------------
+ * MXFP4-ARC in everything but the element:
+ *   shape, augmented K concatenation, scales   as MXFP4 above: KQ % 64 == 0, KE % 64 == 0, 0 <= KE <= KQ <= 32767, K = KQ + KE,
+ *              Kp = arcq_mx_k_padded(K); [0, KQ) the reordered row, [KQ, K) residual (x) or copy (w) of reordered channels [KQ-KE, KQ),
+ *              [K, Kp) padding with code 0 and scale byte 127; scales [rows, Kp/32] u8 E8M0, row-major
+ *   element    e3m2 (OCP MX): bit 5 sign, bits 4:2 exponent with bias 3, bits 1:0 mantissa; subnormals 0.0625 * {1, 2, 3}; maximum 28;
+ *              no Inf, no NaN
+ *   codes      [rows, 3*Kp/4] u8: block b of a row is the 24 bytes at 24*b, element i of the block occupies bits [6i, 6i+6) of that
+ *              192-bit little-endian string -- the six-register operand of v_mfma_scale_f32_*_f8f6f4 as the hardware reads it (pinned
+ *              with exact data by tests/test_mx6_gpu.py::test_lane_and_bit_map_exact).  Rows are 16-byte aligned, blocks 8-byte aligned
+ *   block      amax = max|v| over the 32 values: e = the smallest integer with amax <= 28 * 2^e, clamped to [-127, 127], 0 for an
+ *              all-zero block, computed exactly; code = e3m2_RNE(v * 2^-e), ties to the even code, sign of zero kept, never saturating
+ *   residual   res = v - deq(code) * 2^e, exact in bf16; its blocks are quantised like any other block */
+int64_t arcq_mx6_code_bytes(int64_t rows, int64_t K); /* rows * 3 * arcq_mx_k_padded(K) / 4 (0 for rows <= 0 or K <= 0) */
+
+/* X [M,KQ] bf16, reorder_index [KQ] int16, QX [M, 3*Kp/4] u8, SFX [M, Kp/32] u8.  Contract, alignments (X, reorder_index and QX 16
+ * bytes) and status codes: arcq_mx_quantize_x's. */
+int arcq_mx6_quantize_x(const void *X, const int16_t *reorder_index, uint8_t *QX, uint8_t *SFX, int64_t M, int64_t KQ, int64_t KE,
+                        void *stream);
+/* as above; the slots [KQ, K) are copies of the codes and scales of reordered channels [KQ-KE, KQ) */
+int arcq_mx6_quantize_w(const void *W, const int16_t *reorder_index, uint8_t *QW, uint8_t *SFW, int64_t N, int64_t KQ, int64_t KE,
+                        void *stream);
+
+#define ARCQ_MX_B_E3M2 0 /* B [N, 3*K/4] e3m2, written by arcq_mx6_quantize_w                                     */
+#define ARCQ_MX_B_E2M1 1 /* B [N, K/2] e2m1, written by arcq_mx_quantize_w with the same KQ, KE, reorder_index: W4A6 */
+
+/* D[m,n] = alpha * sum_{k<K} deq(A[m,k]) * deq(B[n,k]), fp32 accumulation, on the block-scaled MFMA with e3m2 activations.
+ *   A [M, 3*K/4] e3m2 and SFA [M, K/32] as written by arcq_mx6_quantize_x; B and SFB [N, K/32] by the quantiser b_format names (the two
+ *   weight layouts agree element for element); K = Kp (K % 128 == 0); any M >= 0; N % 16 == 0.  alpha, bias, residual (may alias D),
+ *   out_dtype and the roundings: arcq_gemm_mxfp4's.
+ *   Status: arcq_gemm_mxfp4's in its order (ARCQ_ERR_SHAPE for K % 128, N % 16, a bad out_dtype or a misaligned pointer -- A, B, D 16
+ *   bytes; SFA, SFB 4 bytes; bias, residual 2 bytes --, ARCQ_ERR_NULL for a NULL operand; M == 0 or N == 0 returns ARCQ_OK), with
+ *   ARCQ_ERR_SHAPE for an unknown b_format reported first; all before any HIP call. */
+int arcq_gemm_mxfp6(const uint8_t *A, const uint8_t *B, const uint8_t *SFA, const uint8_t *SFB, void *D, int64_t M, int64_t N,
+                    int64_t K, int b_format, float alpha_host, const float *alpha_dev, const void *bias, const void *residual,
+                    int out_dtype, void *stream);
+
 /* ---- MXFP4 decoder-layer operators: the fused quantisers and the SiLU*up GEMM epilogue ------------------------------------------
  * MXFP4 has no per-tensor scale, so none of them needs an abs-max pass, a `state` buffer or abs-max slots: each is ONE launch.
  *
