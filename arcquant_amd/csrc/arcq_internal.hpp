@@ -294,6 +294,7 @@ struct KvDecodeArgs {
 };
 int kv_decode_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P);   // slices per sequence; > 1 needs the workspace
 int kv_decode(const KvDecodeArgs& a, hipStream_t stream);
+int kv_decode_combine_slices(const KvDecodeArgs& a, int S, hipStream_t stream, const char* who);   // the S records of a.workspace -> a.o
 struct KvStepArgs {                        // what the decode step takes beside KvDecodeArgs (whose q is then strided too)
   const void *k, *v;                       // 16-bit [B, N, 128], tokens kv_stride elements apart
   int64_t q_stride, kv_stride;
@@ -313,6 +314,10 @@ struct KvPrefillArgs {
   int dtype;
 };
 int kv_prefill(const KvPrefillArgs& a, hipStream_t stream);
+
+// kv_decode_gqa.hip: int4 decode attention with the g <= 16 query heads of a kv head in one pass on MFMA (arguments validated by c_api_kv.hip)
+int kv_decode_gqa_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P);   // its own slice rule; > 1 needs the workspace
+int kv_decode_gqa(const KvDecodeArgs& a, hipStream_t stream);
 
 // kv_rope.hip: rotary position embedding in front of the quantising writers, and alone (arguments validated by c_api_kv.hip)
 struct KvRopeArgs {

@@ -56,9 +56,13 @@ int strides_ok(const char* who, int64_t q_stride, int64_t Nq, int64_t kv_stride,
 int batch_heads_ok(const char* who, int64_t B, int64_t Nq) {
   return B * Nq > kMaxDim ? fail(ARCQ_ERR_SHAPE, "%s: B * Nq = %lld is out of range", who, (long long)(B * Nq)) : ARCQ_OK;
 }
-int workspace_ok(const char* who, const void* workspace, int64_t workspace_bytes, int64_t need) {  // the slices' records: none without slices
+// the slices' records: none without slices.  `query`: the size function that answers `need`
+int workspace_ok(const char* who, const void* workspace, int64_t workspace_bytes, int64_t need, const char* query = "arcq_kv_decode_workspace_bytes") {
   if (need <= 0 || (workspace && workspace_bytes >= need)) return ARCQ_OK;
-  return fail(ARCQ_ERR_WORKSPACE, "%s: workspace of %lld bytes, need %lld (arcq_kv_decode_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
+  return fail(ARCQ_ERR_WORKSPACE, "%s: workspace of %lld bytes, need %lld (%s)", who, (long long)workspace_bytes, (long long)need, query);
+}
+int group_ok(const char* who, int64_t Nq, int64_t N, int64_t most) {      // the query heads per kv head one pass takes (heads_ok has checked Nq % N)
+  return Nq / N > most ? fail(ARCQ_ERR_UNSUPPORTED, "%s: %lld query heads per kv head, at most %lld", who, (long long)(Nq / N), (long long)most) : ARCQ_OK;
 }
 
 // ---- pointer lists.  A pointer that a call does not need goes in as when(false, p): neither NULL nor misaligned.  NULL is aligned, so
@@ -227,6 +231,30 @@ int arcq_kv_batch_decode(void* o, const void* q, const void* kv_data, const void
     return rc;
   KvDecodeArgs a{o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, B, Nq, L, layer_idx, N, P, nnz, format, dtype, workspace};
   return kv_decode(a, (hipStream_t)stream);
+}
+
+int64_t arcq_kv_decode_gqa_workspace_bytes(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P) {
+  if (B <= 0 || Nq <= 0 || N <= 0 || Nq % N) return 0;
+  const int64_t S = kv_decode_gqa_splits(B, Nq, N, nnz, P);
+  return S <= 1 ? 0 : B * Nq * S * 130 * (int64_t)sizeof(float);
+}
+
+int arcq_kv_batch_decode_gqa(void* o, const void* q, const void* kv_data, const void* kv_param, const int32_t* kv_indptr, const int32_t* kv_indices,
+                             const int32_t* last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int64_t nnz,
+                             int format, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "arcq_kv_batch_decode_gqa";
+  int rc;
+  if ((rc = geometry(who, B, L, layer_idx, N, P, format)) || (rc = dtype_ok(who, dtype)) || (rc = heads_ok(who, Nq, N)) || (rc = pages_ok(who, nnz, P)) ||
+      (rc = batch_heads_ok(who, B, Nq)) || (rc = int4_only(who, format, "GQA decode attention reads")) || (rc = group_ok(who, Nq, N, 16)))
+    return rc;
+  if (B == 0) return ARCQ_OK;
+  if ((rc = none_null(who, {o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset})) ||
+      (rc = aligned16(who, {o, q, kv_data}, "o, q and kv_data")) ||
+      (rc = aligned4(who, {kv_param, kv_indptr, kv_indices, last_page_offset, workspace}, "kv_param, the index tensors and the workspace")) ||
+      (rc = workspace_ok(who, workspace, workspace_bytes, arcq_kv_decode_gqa_workspace_bytes(B, Nq, N, nnz, P), "arcq_kv_decode_gqa_workspace_bytes")))
+    return rc;
+  KvDecodeArgs a{o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, B, Nq, L, layer_idx, N, P, nnz, format, dtype, workspace};
+  return kv_decode_gqa(a, (hipStream_t)stream);
 }
 
 int arcq_kv_batch_prefill(void* o, const void* q, const int32_t* qo_indptr, const void* kv_data, const void* kv_param, const int32_t* kv_indptr,

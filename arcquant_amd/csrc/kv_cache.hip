@@ -33,7 +33,6 @@
 
 namespace arcq {
 
-constexpr int kKvRec = kKvD + 2;         // a merge record: max, sum, 128 accumulators
 constexpr int kKvWaves = 4;
 
 // ---- writers (KvWriteParams, kv_locate and kv_quantize_row: kv_device.hpp)
@@ -491,6 +490,15 @@ static int launch_kv_decode(const typename KvParamsOf<STEP>::type& p, const KvDe
   return launch_kv_decode_gc<FMT, STEP, 4>(p, bf, a, stream, who);
 }
 
+// the S slice records per (sequence, query head) in a.workspace -> a.o (kv_decode below and kv_decode_gqa.hip)
+int kv_decode_combine_slices(const KvDecodeArgs& a, int S, hipStream_t stream, const char* who) {
+  KvDecodeParams p{};
+  p.o = a.o; p.ws = (float*)a.workspace; p.S = S;
+  const dim3 grid((unsigned)(a.B * a.Nq));
+  if (a.dtype == ARCQ_KV_BF16) return launch_kernel<kv_decode_combine<true>>(grid, dim3(kKvD), 0, stream, who, p);
+  return launch_kernel<kv_decode_combine<false>>(grid, dim3(kKvD), 0, stream, who, p);
+}
+
 int kv_decode_step(const KvDecodeArgs& a, const KvStepArgs& st, hipStream_t stream) {
   KvStepParams p = kv_decode_params<KvStepParams>(a);
   p.k = (const uint16_t*)st.k; p.v = (const uint16_t*)st.v; p.cnt = (int32_t*)st.state;
@@ -503,9 +511,7 @@ int kv_decode(const KvDecodeArgs& a, hipStream_t stream) {
   const KvDecodeParams p = kv_decode_params<KvDecodeParams>(a);
   const int rc = a.format == ARCQ_KV_INT4 ? launch_kv_decode<ARCQ_KV_INT4, false>(p, a, stream, who) : launch_kv_decode<ARCQ_KV_16BIT, false>(p, a, stream, who);
   if (rc != ARCQ_OK || p.S <= 1) return rc;
-  const dim3 grid((unsigned)(a.B * a.Nq));
-  if (a.dtype == ARCQ_KV_BF16) return launch_kernel<kv_decode_combine<true>>(grid, dim3(kKvD), 0, stream, who, p);
-  return launch_kernel<kv_decode_combine<false>>(grid, dim3(kKvD), 0, stream, who, p);
+  return kv_decode_combine_slices(a, p.S, stream, who);
 }
 
 }  // namespace arcq

@@ -10,6 +10,7 @@ namespace arcq {
 
 constexpr int kKvD = 128;
 constexpr float kKvIdle = -3.0e38f;
+constexpr int kKvRec = kKvD + 2;         // a merge record of the decode kernels: max, sum, 128 accumulators
 
 struct KvTables {
   const int32_t* indptr;

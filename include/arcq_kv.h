@@ -77,6 +77,21 @@ int arcq_kv_batch_decode(void *o, const void *q, const void *kv_data, const void
                          const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
                          int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Bytes of fp32 scratch arcq_kv_batch_decode_gqa needs for this call (0: none, the workspace may be NULL).  Its own rule: a slice of that
+ * kernel is B * N workgroups, whatever g is. */
+int64_t arcq_kv_decode_gqa_workspace_bytes(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P);
+
+/* arcq_kv_batch_decode of an ARCQ_KV_INT4 cache for GQA models, 1 <= g = Nq / N <= 16: the same arguments, contract and result, computed
+ * on the matrix cores with the g query heads of a kv head as the columns of one MFMA tile -- every K and V row is read and converted once,
+ * whatever g is (arcq_kv_batch_decode: ceil(g / 4) passes).  Scores on the exact 4-bit codes, softmax in fp32, the weights p_t s_t rounded
+ * once to `dtype` for the matrix cores as in arcq_kv_batch_prefill, one rounding of the result to `dtype`: the results of the two decode
+ * entry points agree within their error bounds, not bit for bit.  A sequence without positions gives zeros.  ARCQ_KV_16BIT and g > 16:
+ * ARCQ_ERR_UNSUPPORTED before any launch.  workspace_bytes >= arcq_kv_decode_gqa_workspace_bytes(B, Nq, N, nnz, P) (0: workspace may be
+ * NULL).  No state, no host read of a device table: the call can be captured into a HIP graph. */
+int arcq_kv_batch_decode_gqa(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                             const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
+                             int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Causal prefill attention over the pages: several query tokens per sequence, each attending over everything the cache holds up to and
  * including its own position.  o, q = `dtype` [ntok, Nq, 128], contiguous, Nq = g * N.  qo_indptr = int32 [B + 1] on the device,
  * non-decreasing from 0 with qo_indptr[B] <= ntok (the caller's contract, like the other tables): sequence b has

@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Decode attention of GQA models over the int4 paged KV cache: kvcache.batch_decode_gqa_i4 (the g query heads of a kv head in one pass on
+MFMA, kv_decode_gqa.hip) against kvcache.batch_decode_i4 (the VALU kernel, ceil(g / 4) passes) on the same pages and queries, in one
+process on one device; writes profiles/kv_int4_decode_gqa.json (the evidence behind DESIGN.md 11 "GQA decode on MFMA").
+
+    python tools/kv_gqa_bench.py [--rounds 3] [--out profiles/kv_int4_decode_gqa.json]
+
+Shapes: (Nq, N) = (28, 4), (32, 8), (64, 8) -- Qwen2.5-7B, Llama-3-8B, Llama-3-70B -- at batch sizes 1, 4, 16 and 1040, 4096, 16384
+positions, bf16, P = 16.  Method (tools/kv_bench.py's): a record's launches -- one per layer over separate layers' caches, enough layers
+that a round reads >= 600 MB (more than L2 and MALL hold; at most 512 layers, `cold` says whether that was reached) -- are replayed from
+one HIP graph, warmed for ~40 ms and timed for >= 10 ms between two events; us is per launch.  Bytes are the pages read once:
+2 * B * N * T * (64 + 4).  The two kernels ALTERNATE for `--rounds` rounds; a record keeps the best round of each and `round_spread`.
+Before a shape is timed the two results are compared (max |difference| is recorded).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import torch  # noqa: E402
+
+from arcquant_amd import _lib, kvcache  # noqa: E402
+from kv_bench import alternate, random_cache  # noqa: E402
+
+P = 16
+COLD_BYTES, MAX_LAYERS = 600e6, 512
+HEADS = ((28, 4), (32, 8), (64, 8))
+
+
+def record(B, Nq, N, T, dev, rounds):
+    lib = _lib.lib()
+    nbytes = 2 * B * N * T * 68
+    layers = int(max(2, min(MAX_LAYERS, -(-COLD_BYTES // nbytes))))
+    c = random_cache(B, N, T, layers, dev)
+    tables = c.tables(T)
+    q = torch.randn(B, Nq, 128, device=dev).to(torch.bfloat16)
+    o = {"gqa": torch.empty_like(q), "i4": torch.empty_like(q)}
+    fns = {"gqa": kvcache.batch_decode_gqa_i4, "i4": kvcache.batch_decode_i4}
+    for n, fn in fns.items():
+        fn(o[n], q, **tables, layer_idx=layers - 1)
+    diff = float((o["gqa"].float() - o["i4"].float()).abs().max())
+    chains = {n: [lambda layer=layer, n=n: fns[n](o[n], q, **tables, layer_idx=layer) for layer in range(layers)] for n in fns}
+    us, spread = alternate(chains, rounds)
+    nnz = tables["kv_indices"].numel()
+    return {"Nq": Nq, "N": N, "g": Nq // N, "B": B, "positions": T, "page_size": P, "dtype": "bf16", "layers_rotated": layers,
+            "cold": layers * nbytes >= COLD_BYTES, "bytes": nbytes, "gqa_us": round(us["gqa"], 2), "i4_us": round(us["i4"], 2),
+            "gqa_GBps": round(nbytes / us["gqa"] / 1e3, 1), "i4_GBps": round(nbytes / us["i4"] / 1e3, 1), "speedup": round(us["i4"] / us["gqa"], 3),
+            "round_spread": spread, "max_abs_diff": diff,
+            "gqa_slices": int(lib.arcq_kv_decode_gqa_workspace_bytes(B, Nq, N, nnz, P)) // (B * Nq * 130 * 4) or 1,
+            "i4_slices": int(lib.arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P)) // (B * Nq * 130 * 4) or 1}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kv_int4_decode_gqa.json"))
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    records = []
+    with torch.no_grad():
+        for Nq, N in HEADS:
+            for B in (1, 4, 16):
+                for T in (1040, 4096, 16384):
+                    records.append(record(B, Nq, N, T, dev, a.rounds))
+                    print(json.dumps(records[-1]), flush=True)
+                    torch.cuda.empty_cache()
+    res = {"tool": "tools/kv_gqa_bench.py", "device": torch.cuda.get_device_name(0), "records": records}
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
