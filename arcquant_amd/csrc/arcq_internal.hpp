@@ -314,6 +314,8 @@ struct KvPrefillArgs {
   int dtype;
 };
 int kv_prefill(const KvPrefillArgs& a, hipStream_t stream);
+// kv_prefill16.hip: the same attention over the 16-bit pages of a.dtype (a.kv_param is not read)
+int kv_prefill16(const KvPrefillArgs& a, hipStream_t stream);
 
 // kv_decode_gqa.hip: int4 decode attention with the g <= 16 query heads of a kv head in one pass on MFMA (arguments validated by c_api_kv.hip)
 int kv_decode_gqa_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P);   // its own slice rule; > 1 needs the workspace

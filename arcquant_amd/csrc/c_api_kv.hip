@@ -274,6 +274,23 @@ int arcq_kv_batch_prefill(void* o, const void* q, const int32_t* qo_indptr, cons
   return kv_prefill(a, (hipStream_t)stream);
 }
 
+int arcq_kv_batch_prefill_16bit(void* o, const void* q, const int32_t* qo_indptr, const void* kv_data, const void* kv_param, const int32_t* kv_indptr,
+                                const int32_t* kv_indices, const int32_t* last_page_offset, int64_t ntok, int64_t B, int64_t Nq, int64_t L,
+                                int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int dtype, void* stream) {
+  const char* who = "arcq_kv_batch_prefill_16bit";
+  int rc;
+  if ((rc = geometry(who, B, L, layer_idx, N, P, ARCQ_KV_16BIT)) || (rc = dtype_ok(who, dtype)) || (rc = heads_ok(who, Nq, N)) ||
+      (rc = pages_ok(who, nnz, P)) || (rc = ntok_ok(who, ntok)))
+    return rc;
+  if (B == 0 || ntok == 0) return ARCQ_OK;
+  if ((rc = none_null(who, {o, q, qo_indptr, kv_data, kv_indptr, kv_indices, last_page_offset})) ||      // (kv_param is never read: it may be NULL)
+      (rc = aligned16(who, {o, q, kv_data}, "o, q and kv_data")) ||
+      (rc = aligned4(who, {kv_param, qo_indptr, kv_indptr, kv_indices, last_page_offset}, "kv_param and the index tensors")))
+    return rc;
+  KvPrefillArgs a{o, q, qo_indptr, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, ntok, B, Nq, L, layer_idx, N, P, dtype};
+  return kv_prefill16(a, (hipStream_t)stream);
+}
+
 int64_t arcq_kv_decode_step_state_bytes(int64_t B, int64_t Nq, int64_t N) {
   if (B <= 0 || Nq <= 0 || N <= 0 || Nq % N) return 0;
   return B * N * kv_decode_chunks(Nq, N) * (int64_t)sizeof(int32_t);

@@ -12,7 +12,8 @@ Extensions: ``append_kv_quantize_i4`` / ``init_kv_quantize_i4`` quantise fp16 / 
 five torch launches per tensor, then the append); ``batch_decode_*`` also takes bf16 and ``Nq = g * N`` query heads (GQA: query head h
 reads kv head h // g).  ``asym_quantize_and_pack_i4`` / ``unpack_i4_and_asym_dequantize`` are the torch formulas for callers that keep the
 reference's flow, ``PagedKVCacheI4`` holds the pages and builds the tables.  ``batch_prefill_i4`` (kvprefill.py) is the causal attention
-of several query tokens per sequence over the int4 pages: chunked prefill, a second turn, speculative verification.
+of several query tokens per sequence over the int4 pages: chunked prefill, a second turn, speculative verification; ``batch_prefill_f16``
+(kvprefill.py) is the same over the 16-bit pages.
 ``batch_decode_gqa_i4`` (kvgqa.py) is ``batch_decode_i4`` for GQA models, 1 <= g <= 16, on the matrix cores.
 
 This module is a ctypes mirror only.  Validation follows the mirror's order (``agemm._need`` ...): dtype / rank / contiguity, then the size
@@ -28,7 +29,7 @@ from .agemm import _need, _on, _same_device, _stream
 # extensions in modules of their own, as kvstep is: decode attention for GQA models on the matrix cores, causal prefill attention over the
 # int4 pages (several query tokens per sequence), and rotary position embedding at write time, fused into the quantising writers
 from .kvgqa import batch_decode_gqa_i4  # noqa: F401
-from .kvprefill import batch_prefill_i4  # noqa: F401
+from .kvprefill import batch_prefill_f16, batch_prefill_i4  # noqa: F401
 from .kvrope import rope_append_kv_quantize_i4, rope_init_kv_quantize_i4, rope_qk_, rope_tables  # noqa: F401
 
 

@@ -104,13 +104,31 @@ int arcq_kv_batch_decode_gqa(void *o, const void *q, const void *kv_data, const 
  * matrix cores (fp16: a weight below 2^-14 is rounded on the subnormal grid, 2^-25 absolute), one rounding of the result to `dtype`.
  * n_b = 1 for every b is arcq_kv_batch_decode's contract; n_b = 0 writes nothing for that sequence; rows of o at or beyond qo_indptr[B]
  * are not written, and nothing else is.  B == 0 or ntok == 0 returns ARCQ_OK without a launch.  ARCQ_KV_INT4 only (ARCQ_KV_16BIT:
- * ARCQ_ERR_UNSUPPORTED).  No workspace, no state, no host read of a device table: the call can be captured into a HIP graph.
- * nnz = entries of kv_indices (range-checked only).
+ * ARCQ_ERR_UNSUPPORTED; that cache has arcq_kv_batch_prefill_16bit below).  No workspace, no state, no host read of a device table: the
+ * call can be captured into a HIP graph.  nnz = entries of kv_indices (range-checked only).
  * KNOWN LIMIT: the kv range of a sequence is not split over workgroups.  A launch has one workgroup per (sequence, kv head, 128 / g query
  * tokens), so a few query tokens over a very long cache (speculative verification at batch size 1) run on B * N workgroups. */
 int arcq_kv_batch_prefill(void *o, const void *q, const int32_t *qo_indptr, const void *kv_data, const void *kv_param,
                           const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int64_t ntok, int64_t B,
                           int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *stream);
+
+/* arcq_kv_batch_prefill over an ARCQ_KV_16BIT cache: kv_data = `dtype` values [pages, L, 2, N, P, 128], the element type of q and o.  The
+ * arguments are arcq_kv_batch_prefill's without `format`, and so is the contract, word for word: the n_b query tokens of sequence b are
+ * its LAST positions, already written (arcq_kv_init), n_b <= T_b; query i attends over positions 0 .. T_b - n_b + i; query head h reads
+ * kv head h / g;
+ *     o[qo_indptr[b] + i, h] = softmax_{t <= T_b - n_b + i}(q[qo_indptr[b] + i, h] . K[t] / sqrt(128)) V[t],   no RoPE,
+ * products of the 16-bit values on the matrix cores with fp32 accumulation, softmax in fp32, the weights p_t rounded once to `dtype`
+ * for the matrix cores (fp16: a weight below 2^-14 is rounded on the subnormal grid, 2^-25 absolute), the row sum over the unrounded
+ * weights, one rounding of the result to `dtype`.  n_b = 1 for every b is arcq_kv_batch_decode's contract on this format; n_b = 0 writes
+ * nothing for that sequence; rows of o at or beyond qo_indptr[B] are not written, and nothing else is.  kv_param is what the `_f16`
+ * writers store and decode never applies: it is NOT READ and may be NULL (if given, 4-byte aligned).  No row past T_b and no page the
+ * sequence does not own is read.  B == 0 or ntok == 0 returns ARCQ_OK without a launch.  No workspace, no state, no host read of a device
+ * table: the call can be captured into a HIP graph.  nnz = entries of kv_indices (range-checked only).
+ * KNOWN LIMIT, as above: the kv range of a sequence is not split over workgroups. */
+int arcq_kv_batch_prefill_16bit(void *o, const void *q, const int32_t *qo_indptr, const void *kv_data, const void *kv_param,
+                                const int32_t *kv_indptr, const int32_t *kv_indices, const int32_t *last_page_offset, int64_t ntok,
+                                int64_t B, int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int dtype,
+                                void *stream);
 
 /* Bytes of the decode step's state: one int32 arrival counter per (sequence, kv head, chunk of <= 4 of its g = Nq / N query heads). */
 int64_t arcq_kv_decode_step_state_bytes(int64_t B, int64_t Nq, int64_t N);

@@ -17,6 +17,10 @@ rounds; a record keeps the best round of each and `round_spread`, the largest (m
 FLOPs are the causal ones, 4 * 128 * (positions a query attends to) per query row; the roof is BASELINE.md's bf16-MFMA 2.52 PFLOP/s.
 Bytes are what the kernel must read and write once: 2 * B * N * T * 68 of pages + 2 * tokens * Nq * 256 of q and o.
 `--harness-layers` > 0 adds e2e.bench_decode (bs = 4, prefill 1024, that many layers) with the flag unset and set, alternating twice.
+
+The 16-bit table (`--table f16` alone, `--f16-out profiles/kv_f16_prefill.json`; DESIGN.md 11 "Prefill over a 16-bit cache"): the same
+shapes and method for kvcache.batch_prefill_f16 over bf16 pages, against torch gather + SDPA over the same 16-bit pages and against
+batch_prefill_i4 over the int4 pages those values were dequantised from, the three alternating.  Bytes: 256 per row instead of 68.
 """
 from __future__ import annotations
 
@@ -96,6 +100,51 @@ def shape(B, N, cached, n_new, layers, dev, rounds):
     return rec
 
 
+def shape_f16(B, N, cached, n_new, layers, dev, rounds):
+    """The 16-bit table: kvcache.batch_prefill_f16 over bf16 pages against torch gather + SDPA over the SAME pages, and against
+    batch_prefill_i4 over the int4 pages those bf16 values were dequantised from (the same logical cache), alternating in one run."""
+    T, g = cached + n_new, NQ // N
+    c = kvcache.PagedKVCacheI4(B, P, T, dev, layers, N)
+    c.pages.copy_(torch.randint(0, 256, c.pages.shape, dtype=torch.uint8, device=dev))
+    c.scales[..., 0] = 0.4
+    c.scales[..., 1] = 3.0
+    pages16 = torch.empty(c.pages.shape[:-1] + (D,), dtype=torch.bfloat16, device=dev)
+    for layer in range(layers):
+        pages16[:, layer] = kvcache.unpack_i4_and_asym_dequantize(c.pages[:, layer], c.scales[:, layer, ..., 0:1], c.scales[:, layer, ..., 1:2])
+    tables = c.prefill_tables(T, n_new)
+    qo = tables.pop("qo_indptr")
+    tables16 = dict(tables, kv_data=pages16)
+    q = torch.randn(B * n_new, NQ, D, device=dev).to(torch.bfloat16)
+    o = torch.empty_like(q)
+    cnt = c.page_cnt_from_length(T)
+    own = tables["kv_indices"].view(B, cnt).long()
+    mask = torch.arange(T, device=dev).unsqueeze(0) <= (cached + torch.arange(n_new, device=dev)).unsqueeze(1)        # [n_new, T]
+    q4 = q.view(B, n_new, NQ, D).transpose(1, 2)
+
+    def gather(layer):
+        def f():
+            kv = pages16[own, layer].permute(0, 2, 3, 1, 4, 5).reshape(B, 2, N, cnt * P, D)[:, :, :, :T]
+            k, v = kv[:, 0], kv[:, 1]
+            if g > 1:
+                k, v = k.repeat_interleave(g, dim=1), v.repeat_interleave(g, dim=1)
+            return F.scaled_dot_product_attention(q4, k, v, attn_mask=mask)
+        return f
+    chains = {"prefill_f16": [lambda layer=layer: kvcache.batch_prefill_f16(o, q, qo, **tables16, layer_idx=layer) for layer in range(layers)],
+              "gather_sdpa": [gather(layer) for layer in range(layers)],
+              "prefill_i4": [lambda layer=layer: kvcache.batch_prefill_i4(o, q, qo, **tables, layer_idx=layer) for layer in range(layers)]}
+    us, spread = alternate(chains, rounds)
+    flops = 4 * D * B * NQ * (n_new * cached + n_new * (n_new + 1) // 2)
+    nbytes = 2 * B * N * T * 256 + 2 * B * n_new * NQ * D * 2
+    return {"what": "causal prefill attention, 16-bit pages", "B": B, "query_heads": NQ, "kv_heads": N, "cached": cached, "new_tokens": n_new,
+            "page_size": P, "layers_rotated": layers, "causal_gflop": round(flops / 1e9, 2), "bytes": nbytes,
+            "workgroups": -(-n_new // (128 // g)) * B * N, "prefill_f16_us": round(us["prefill_f16"], 1),
+            "prefill_f16_tflops": round(flops / us["prefill_f16"] / 1e6, 1),
+            "prefill_f16_fraction_of_bf16_mfma_roof": round(flops / us["prefill_f16"] / 1e6 / ROOF_TFLOPS, 4),
+            "prefill_f16_GBps": round(nbytes / us["prefill_f16"] / 1e3, 1), "gather_sdpa_us": round(us["gather_sdpa"], 1),
+            "speedup_over_gather_sdpa": round(us["gather_sdpa"] / us["prefill_f16"], 2), "prefill_i4_us": round(us["prefill_i4"], 1),
+            "prefill_i4_us_over_prefill_f16_us": round(us["prefill_i4"] / us["prefill_f16"], 2), "round_spread": spread}
+
+
 def harness(layers):
     from arcquant_amd import e2e
     out = []
@@ -115,21 +164,26 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--harness-layers", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kv_int4_prefill.json"))
+    ap.add_argument("--f16-out", default=os.path.join(ROOT, "profiles", "kv_f16_prefill.json"))
+    ap.add_argument("--table", choices=("int4", "f16", "both"), default="both", help="f16: the 16-bit table alone (no int4 table, no harness)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    records = []
-    with torch.no_grad():
-        for N in (28, 4):
-            for B, cached, n_new in ((4, 0, 512), (4, 1024, 512), (4, 4096, 512), (1, 0, 2048)):
-                records.append(shape(B, N, cached, n_new, a.layers, dev, a.rounds))
-                print(json.dumps(records[-1]), flush=True)
-                torch.cuda.empty_cache()
-        res = {"tool": "tools/kv_prefill_bench.py", "device": torch.cuda.get_device_name(0), "bf16_mfma_roof_tflops": ROOF_TFLOPS, "records": records}
-        if a.harness_layers > 0:
-            res["harness"] = harness(a.harness_layers)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    for fn, out in ((shape, a.out), (shape_f16, a.f16_out)):
+        if a.table not in ("both", "int4" if fn is shape else "f16"):
+            continue
+        records = []
+        with torch.no_grad():
+            for N in (28, 4):
+                for B, cached, n_new in ((4, 0, 512), (4, 1024, 512), (4, 4096, 512), (1, 0, 2048)):
+                    records.append(fn(B, N, cached, n_new, a.layers, dev, a.rounds))
+                    print(json.dumps(records[-1]), flush=True)
+                    torch.cuda.empty_cache()
+            res = {"tool": "tools/kv_prefill_bench.py", "device": torch.cuda.get_device_name(0), "bf16_mfma_roof_tflops": ROOF_TFLOPS, "records": records}
+            if fn is shape and a.harness_layers > 0:
+                res["harness"] = harness(a.harness_layers)
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
