@@ -320,6 +320,8 @@ int kv_prefill16(const KvPrefillArgs& a, hipStream_t stream);
 // kv_decode_gqa.hip: int4 decode attention with the g <= 16 query heads of a kv head in one pass on MFMA (arguments validated by c_api_kv.hip)
 int kv_decode_gqa_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t P);   // its own slice rule; > 1 needs the workspace
 int kv_decode_gqa(const KvDecodeArgs& a, hipStream_t stream);
+// kv_decode_gqa16.hip: the same pass over the 16-bit pages of a.dtype (a.kv_param is not read; kv_decode_gqa_splits' slices)
+int kv_decode_gqa16(const KvDecodeArgs& a, hipStream_t stream);
 
 // kv_rope.hip: rotary position embedding in front of the quantising writers, and alone (arguments validated by c_api_kv.hip)
 struct KvRopeArgs {

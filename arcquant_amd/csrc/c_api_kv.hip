@@ -257,6 +257,24 @@ int arcq_kv_batch_decode_gqa(void* o, const void* q, const void* kv_data, const 
   return kv_decode_gqa(a, (hipStream_t)stream);
 }
 
+int arcq_kv_batch_decode_gqa_16bit(void* o, const void* q, const void* kv_data, const void* kv_param, const int32_t* kv_indptr,
+                                   const int32_t* kv_indices, const int32_t* last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
+                                   int64_t N, int64_t P, int64_t nnz, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "arcq_kv_batch_decode_gqa_16bit";
+  int rc;
+  if ((rc = geometry(who, B, L, layer_idx, N, P, ARCQ_KV_16BIT)) || (rc = dtype_ok(who, dtype)) || (rc = heads_ok(who, Nq, N)) ||
+      (rc = pages_ok(who, nnz, P)) || (rc = batch_heads_ok(who, B, Nq)) || (rc = group_ok(who, Nq, N, 16)))
+    return rc;
+  if (B == 0) return ARCQ_OK;
+  if ((rc = none_null(who, {o, q, kv_data, kv_indptr, kv_indices, last_page_offset})) ||                 // (kv_param is never read: it may be NULL)
+      (rc = aligned16(who, {o, q, kv_data}, "o, q and kv_data")) ||
+      (rc = aligned4(who, {kv_param, kv_indptr, kv_indices, last_page_offset, workspace}, "kv_param, the index tensors and the workspace")) ||
+      (rc = workspace_ok(who, workspace, workspace_bytes, arcq_kv_decode_gqa_workspace_bytes(B, Nq, N, nnz, P), "arcq_kv_decode_gqa_workspace_bytes")))
+    return rc;
+  KvDecodeArgs a{o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, B, Nq, L, layer_idx, N, P, nnz, ARCQ_KV_16BIT, dtype, workspace};
+  return kv_decode_gqa16(a, (hipStream_t)stream);
+}
+
 int arcq_kv_batch_prefill(void* o, const void* q, const int32_t* qo_indptr, const void* kv_data, const void* kv_param, const int32_t* kv_indptr,
                           const int32_t* kv_indices, const int32_t* last_page_offset, int64_t ntok, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
                           int64_t N, int64_t P, int64_t nnz, int format, int dtype, void* stream) {

@@ -14,7 +14,8 @@ reads kv head h // g).  ``asym_quantize_and_pack_i4`` / ``unpack_i4_and_asym_deq
 reference's flow, ``PagedKVCacheI4`` holds the pages and builds the tables.  ``batch_prefill_i4`` (kvprefill.py) is the causal attention
 of several query tokens per sequence over the int4 pages: chunked prefill, a second turn, speculative verification; ``batch_prefill_f16``
 (kvprefill.py) is the same over the 16-bit pages.
-``batch_decode_gqa_i4`` (kvgqa.py) is ``batch_decode_i4`` for GQA models, 1 <= g <= 16, on the matrix cores.
+``batch_decode_gqa_i4`` (kvgqa.py) is ``batch_decode_i4`` for GQA models, 1 <= g <= 16, on the matrix cores, and ``batch_decode_gqa_f16``
+(kvgqa.py) is ``batch_decode_f16`` for them.
 
 This module is a ctypes mirror only.  Validation follows the mirror's order (``agemm._need`` ...): dtype / rank / contiguity, then the size
 relations, and LAST where everything lives.  The CONTENTS of the index tensors are the caller's contract, as in the reference.
@@ -28,7 +29,7 @@ from ._kvargs import _DTYPES, HEAD_DIM, _cache, _dtype_of, _heads, _params, _row
 from .agemm import _need, _on, _same_device, _stream
 # extensions in modules of their own, as kvstep is: decode attention for GQA models on the matrix cores, causal prefill attention over the
 # int4 pages (several query tokens per sequence), and rotary position embedding at write time, fused into the quantising writers
-from .kvgqa import batch_decode_gqa_i4  # noqa: F401
+from .kvgqa import batch_decode_gqa_f16, batch_decode_gqa_i4  # noqa: F401
 from .kvprefill import batch_prefill_f16, batch_prefill_i4  # noqa: F401
 from .kvrope import rope_append_kv_quantize_i4, rope_init_kv_quantize_i4, rope_qk_, rope_tables  # noqa: F401
 
@@ -84,7 +85,8 @@ def _write(who, i4, quantize, init, kv_data, kv_param, kv_indptr, kv_indices, la
 
 
 def _decode(who, i4, o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, layer_idx, gqa=False):
-    """``gqa``: the MFMA kernel of kvgqa.batch_decode_gqa_i4 (its own entry point and workspace query, at most 16 query heads per kv head)."""
+    """``gqa``: the MFMA kernels of kvgqa.batch_decode_gqa_i4 / batch_decode_gqa_f16 (an entry point per format, their own workspace
+    query, at most 16 query heads per kv head)."""
     dtype = _dtype_of(f"kvcache.{who}", q)
     _need(q, dtype, "q", 3)
     _need(o, dtype, "o", 3)
@@ -94,15 +96,18 @@ def _decode(who, i4, o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_o
     Nq = q.shape[1]
     _heads(f"kvcache.{who}", Nq, N)
     if gqa and Nq // N > 16:
-        raise RuntimeError(f"kvcache.{who}: {Nq // N} query heads per kv head, at most 16 (batch_decode_i4 takes any number)")
+        raise RuntimeError(f"kvcache.{who}: {Nq // N} query heads per kv head, at most 16 (batch_decode_{'i4' if i4 else 'f16'} takes any number)")
     _same_device(f"kvcache.{who}", q, o, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset)
     lib, nnz = _lib.lib(), kv_indices.numel()
     query, call = (lib.arcq_kv_decode_gqa_workspace_bytes, lib.arcq_kv_batch_decode_gqa) if gqa else (lib.arcq_kv_decode_workspace_bytes, lib.arcq_kv_batch_decode)
+    fmt = (_lib.KV_INT4 if i4 else _lib.KV_16BIT,)
+    if gqa and not i4:                                   # its own entry point, which takes no format
+        call, fmt = lib.arcq_kv_batch_decode_gqa_16bit, ()
     ws_bytes = int(query(B, Nq, N, nnz, P))
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=q.device) if ws_bytes else None
     with _on(q.device):
         st = call(o.data_ptr(), q.data_ptr(), kv_data.data_ptr(), kv_param.data_ptr(), kv_indptr.data_ptr(), kv_indices.data_ptr(),
-                  last_page_offset.data_ptr(), B, Nq, L, layer_idx, N, P, nnz, _lib.KV_INT4 if i4 else _lib.KV_16BIT, _DTYPES[dtype],
+                  last_page_offset.data_ptr(), B, Nq, L, layer_idx, N, P, nnz, *fmt, _DTYPES[dtype],
                   None if ws is None else ws.data_ptr(), ws_bytes, _stream(q))
     _lib.check(st, f"kvcache.{who}")
     return o

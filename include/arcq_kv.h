@@ -92,6 +92,19 @@ int arcq_kv_batch_decode_gqa(void *o, const void *q, const void *kv_data, const 
                              const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx,
                              int64_t N, int64_t P, int64_t nnz, int format, int dtype, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* arcq_kv_batch_decode of an ARCQ_KV_16BIT cache of `dtype` for GQA models, 1 <= g = Nq / N <= 16: arcq_kv_batch_decode_gqa's arguments
+ * without `format`, and its work split, over rows that are MFMA operands as they stand -- every K and V row is read once, whatever g is
+ * (arcq_kv_batch_decode: ceil(g / 4) passes).  Products of the 16-bit values with fp32 accumulation, softmax in fp32, the weights p_t
+ * rounded once to `dtype` for the matrix cores (the row sum is over the unrounded weights), one rounding of the result to `dtype`: it
+ * agrees with arcq_kv_batch_decode within the two error bounds, not bit for bit.  A sequence without positions gives zeros.  kv_param is
+ * not read and may be NULL.  g > 16: ARCQ_ERR_UNSUPPORTED before any launch.  workspace_bytes >=
+ * arcq_kv_decode_gqa_workspace_bytes(B, Nq, N, nnz, P) (0: workspace may be NULL).  No state, no host read of a device table: the call
+ * can be captured into a HIP graph. */
+int arcq_kv_batch_decode_gqa_16bit(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                   const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L,
+                                   int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int dtype, void *workspace,
+                                   int64_t workspace_bytes, void *stream);
+
 /* Causal prefill attention over the pages: several query tokens per sequence, each attending over everything the cache holds up to and
  * including its own position.  o, q = `dtype` [ntok, Nq, 128], contiguous, Nq = g * N.  qo_indptr = int32 [B + 1] on the device,
  * non-decreasing from 0 with qo_indptr[B] <= ntok (the caller's contract, like the other tables): sequence b has

@@ -4,6 +4,7 @@ MFMA, kv_decode_gqa.hip) against kvcache.batch_decode_i4 (the VALU kernel, ceil(
 process on one device; writes profiles/kv_int4_decode_gqa.json (the evidence behind DESIGN.md 11 "GQA decode on MFMA").
 
     python tools/kv_gqa_bench.py [--rounds 3] [--out profiles/kv_int4_decode_gqa.json]
+    python tools/kv_gqa_bench.py --table f16 [--rounds 3] [--out profiles/kv_f16_decode_gqa.json]
 
 Shapes: (Nq, N) = (28, 4), (32, 8), (64, 8) -- Qwen2.5-7B, Llama-3-8B, Llama-3-70B -- at batch sizes 1, 4, 16 and 1040, 4096, 16384
 positions, bf16, P = 16.  Method (tools/kv_bench.py's): a record's launches -- one per layer over separate layers' caches, enough layers
@@ -11,6 +12,10 @@ that a round reads >= 600 MB (more than L2 and MALL hold; at most 512 layers, `c
 one HIP graph, warmed for ~40 ms and timed for >= 10 ms between two events; us is per launch.  Bytes are the pages read once:
 2 * B * N * T * (64 + 4).  The two kernels ALTERNATE for `--rounds` rounds; a record keeps the best round of each and `round_spread`.
 Before a shape is timed the two results are compared (max |difference| is recorded).
+
+``--table f16`` (DESIGN.md 11 "GQA decode over a 16-bit cache"): kvcache.batch_decode_gqa_f16 (kv_decode_gqa16.hip) against
+kvcache.batch_decode_f16 on the same bf16 pages (randn * 3 rows; bytes 2 * B * N * T * 256), and against batch_decode_gqa_i4 over int4
+pages that hold the quantised values of the same rows (bytes as above), the three alternating in the same rounds.
 """
 from __future__ import annotations
 
@@ -56,21 +61,55 @@ def record(B, Nq, N, T, dev, rounds):
             "i4_slices": int(lib.arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P)) // (B * Nq * 130 * 4) or 1}
 
 
+def record_f16(B, Nq, N, T, dev, rounds):
+    lib = _lib.lib()
+    nbytes, nbytes_i4 = 2 * B * N * T * 256, 2 * B * N * T * 68
+    layers = int(max(2, min(MAX_LAYERS, -(-COLD_BYTES // nbytes))))
+    c = kvcache.PagedKVCacheI4(B, P, T, dev, layers, N)
+    t4 = c.tables(T)
+    pages16 = (torch.randn(c.pages.shape[:-1] + (128,), device=dev, dtype=torch.bfloat16) * 3)
+    for layer in range(layers):                          # the int4 pages: the quantised values of the same rows
+        codes, scale, zero = kvcache.asym_quantize_and_pack_i4(pages16[:, layer])
+        c.pages[:, layer] = codes
+        c.scales[:, layer] = torch.cat((scale, zero), -1).to(torch.float16)
+    t16 = dict(t4, kv_data=pages16)
+    q = torch.randn(B, Nq, 128, device=dev).to(torch.bfloat16)
+    fns = {"gqa16": (kvcache.batch_decode_gqa_f16, t16), "f16": (kvcache.batch_decode_f16, t16), "gqa_i4": (kvcache.batch_decode_gqa_i4, t4)}
+    o = {n: torch.empty_like(q) for n in fns}
+    for n, (fn, tables) in fns.items():
+        fn(o[n], q, **tables, layer_idx=layers - 1)
+    diff = float((o["gqa16"].float() - o["f16"].float()).abs().max())
+    chains = {n: [lambda layer=layer, n=n: fns[n][0](o[n], q, **fns[n][1], layer_idx=layer) for layer in range(layers)] for n in fns}
+    us, spread = alternate(chains, rounds)
+    nnz = t4["kv_indices"].numel()
+    return {"Nq": Nq, "N": N, "g": Nq // N, "B": B, "positions": T, "page_size": P, "dtype": "bf16", "layers_rotated": layers,
+            "cold": layers * nbytes >= COLD_BYTES, "bytes": nbytes, "bytes_i4": nbytes_i4, "gqa16_us": round(us["gqa16"], 2),
+            "f16_us": round(us["f16"], 2), "gqa_i4_us": round(us["gqa_i4"], 2), "gqa16_GBps": round(nbytes / us["gqa16"] / 1e3, 1),
+            "f16_GBps": round(nbytes / us["f16"] / 1e3, 1), "gqa_i4_GBps": round(nbytes_i4 / us["gqa_i4"] / 1e3, 1),
+            "speedup_over_f16": round(us["f16"] / us["gqa16"], 3), "time_over_gqa_i4": round(us["gqa16"] / us["gqa_i4"], 3),
+            "round_spread": spread, "max_abs_diff_f16": diff,
+            "gqa_slices": int(lib.arcq_kv_decode_gqa_workspace_bytes(B, Nq, N, nnz, P)) // (B * Nq * 130 * 4) or 1,
+            "f16_slices": int(lib.arcq_kv_decode_workspace_bytes(B, Nq, N, nnz, P)) // (B * Nq * 130 * 4) or 1}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kv_int4_decode_gqa.json"))
+    ap.add_argument("--table", choices=("i4", "f16"), default="i4")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "kv_int4_decode_gqa.json" if a.table == "i4" else "kv_f16_decode_gqa.json")
+    one = record if a.table == "i4" else record_f16
     dev = torch.device("cuda:0")
     records = []
     with torch.no_grad():
         for Nq, N in HEADS:
             for B in (1, 4, 16):
                 for T in (1040, 4096, 16384):
-                    records.append(record(B, Nq, N, T, dev, a.rounds))
+                    records.append(one(B, Nq, N, T, dev, a.rounds))
                     print(json.dumps(records[-1]), flush=True)
                     torch.cuda.empty_cache()
-    res = {"tool": "tools/kv_gqa_bench.py", "device": torch.cuda.get_device_name(0), "records": records}
+    res = {"tool": "tools/kv_gqa_bench.py", "table": a.table, "device": torch.cuda.get_device_name(0), "records": records}
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
