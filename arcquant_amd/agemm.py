@@ -754,7 +754,8 @@ _FROM_MX = ("MX_REPACKED_MAX_M", "mx_repack_w", "mx_unrepack_w", "mx_repacked_su
             "matmul_silu_mul_rw", "matmul_silu_mul_quantize_rw", "mx_rw_route")
 
 
-_FROM_MX6 = ("mx6_reorder_quantize_x", "mx6_reorder_quantize_w", "mx6_matmul")       # quant_type='MXFP6' (arcquant_amd/mx6.py)
+_FROM_MX6 = ("mx6_reorder_quantize_x", "mx6_reorder_quantize_w", "mx6_matmul", "MX6_REPACKED_MAX_M", "mx6_repack_w", "mx6_unrepack_w",
+             "mx6_repacked_supported", "mx6_matmul_repacked")                          # quant_type='MXFP6' (arcquant_amd/mx6.py)
 
 
 def __getattr__(name):

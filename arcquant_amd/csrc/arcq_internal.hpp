@@ -144,6 +144,13 @@ int mx6_quantize_x(const void* X, const int16_t* idx, uint8_t* QX, uint8_t* SFX,
 int mx6_quantize_w(const void* W, const int16_t* idx, uint8_t* QW, uint8_t* SFW, int64_t N, int64_t KQ, int64_t KE, hipStream_t stream);
 int gemm_mx6(const uint8_t* A, const uint8_t* B, const uint8_t* SFA, const uint8_t* SFB, void* D, int64_t M, int64_t N, int64_t Kp, int b_format,
              float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype, hipStream_t stream);
+// gemm_mx6_rw.hip: M <= 64 with e3m2 activations over a repacked weight (arcq.h "MXFP6 repacked weight"): MRW6 for b_format e3m2, MXFP4's
+// MRW for e2m1; MRSF is MXFP4's in both (gemm_mx_repacked_sf_bytes)
+int64_t gemm_mx6_repacked_w_bytes(int64_t N, int64_t Kp);
+int gemm_mx6_repacked_supported(int64_t M, int64_t N, int64_t Kp);
+int gemm_mx6_repacked(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* D, int64_t M, int64_t N, int64_t Kp,
+                      int b_format, float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype,
+                      hipStream_t stream);
 // gemm_mx_rw.hip: M <= 64 over the MXFP4 repacked weight (arcq.h "MXFP4 repacked weight"); the sums are gemm_mx's, bit for bit
 int64_t gemm_mx_repacked_w_bytes(int64_t N, int64_t Kp);
 int64_t gemm_mx_repacked_sf_bytes(int64_t N, int64_t Kp);

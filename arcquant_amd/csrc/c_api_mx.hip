@@ -120,6 +120,22 @@ int arcq_gemm_mxfp4_repacked_silu_mul(const uint8_t* A, const uint8_t* MRW, cons
   return gemm_mx_repacked_silu_mul(A, MRW, SFA, MRSF, ACT, M, N, K, alpha_host, alpha_dev, bias, (hipStream_t)stream);
 }
 
+// ---- MXFP6 repacked weight (arcq.h): arcq_gemm_mxfp6's rules after b_format, M bounded as arcq_gemm_mxfp4_repacked bounds it
+int64_t arcq_mx6_repacked_w_bytes(int64_t N, int64_t K) { return gemm_mx6_repacked_w_bytes(N, K); }
+int arcq_gemm_mxfp6_repacked_supported(int64_t M, int64_t N, int64_t K) { return gemm_mx6_repacked_supported(M, N, K); }
+
+int arcq_gemm_mxfp6_repacked(const uint8_t* A, const uint8_t* MRW, const uint8_t* SFA, const uint8_t* MRSF, void* D, int64_t M, int64_t N, int64_t K,
+                             int b_format, float alpha_host, const float* alpha_dev, const void* bias, const void* residual, int out_dtype,
+                             void* stream) {
+  GemmRule r{"arcq_gemm_mxfp6_repacked"};
+  r.k_mult = 128; r.n_mult = 16; r.max_m = 64; r.epi_align = 2; r.b = "MRW"; r.sfb = "MRSF";
+  if (b_format != ARCQ_MX_B_E3M2 && b_format != ARCQ_MX_B_E2M1) return fail(ARCQ_ERR_SHAPE, "%s: unknown b_format %d", r.who, b_format);
+  if (int rc = mx_repacked_max_m(r, M, N, K)) return rc;
+  const int rc = gemm_checks(r, A, MRW, SFA, MRSF, D, nullptr, M, N, K, bias, residual, out_dtype);
+  if (rc != ARCQ_OK) return rc < 0 ? rc : ARCQ_OK;
+  return gemm_mx6_repacked(A, MRW, SFA, MRSF, D, M, N, K, b_format, alpha_host, alpha_dev, bias, residual, out_dtype, (hipStream_t)stream);
+}
+
 // ---- every M over the repacked weight alone: the namesakes' rules and order, the weight operands named MRW / MRSF
 int arcq_gemm_mxfp4_rw_route(int64_t M, int64_t N, int64_t K) { return gemm_mx_rw_route(M, N, K); }
 

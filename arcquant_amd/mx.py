@@ -131,15 +131,29 @@ def mx_repack_w(QW: torch.Tensor, SFW: torch.Tensor):
     if tuple(SFW.shape) != (N, K // 32):
         raise RuntimeError(f"Value error in mx_repack_w: SFW must be [{N}, {K // 32}]")
     RB, T = N // 16, K // 128
-    R = (T + _MX_ROUND - 1) // _MX_ROUND
     # codes: [RB, r, T, q, 16 B] -> [RB, T, q, r, 16 B]
     MRW = QW.view(RB, 16, T, 4, 16).permute(0, 2, 3, 1, 4).contiguous().view(-1)
-    # scales: step t = 32 round + 8 u + wave; [RB, r, round, u, wave, q] -> [RB, round, wave, q, r, u]
-    sf = torch.full((RB, 16, R * _MX_ROUND, 4), _MX_SF_PAD, dtype=torch.uint8, device=QW.device)
-    sf[:, :, :T] = SFW.view(RB, 16, T, 4)
-    MRSF = sf.view(RB, 16, R, 4, 8, 4).permute(0, 2, 4, 5, 1, 3).contiguous().view(-1)
+    MRSF = _mx_repack_sf(SFW)
     assert (MRW.numel(), MRSF.numel()) == _mx_repacked_bytes(N, K)
     return MRW, MRSF
+
+
+def _mx_repack_sf(SFW: torch.Tensor) -> torch.Tensor:
+    # SFW [N, K/32] -> MRSF (also the scale array of the MXFP6 repacked weight, arcquant_amd/mx6.py)
+    RB, T = SFW.shape[0] // 16, SFW.shape[1] // 4
+    R = (T + _MX_ROUND - 1) // _MX_ROUND
+    # scales: step t = 32 round + 8 u + wave; [RB, r, round, u, wave, q] -> [RB, round, wave, q, r, u]
+    sf = torch.full((RB, 16, R * _MX_ROUND, 4), _MX_SF_PAD, dtype=torch.uint8, device=SFW.device)
+    sf[:, :, :T] = SFW.view(RB, 16, T, 4)
+    return sf.view(RB, 16, R, 4, 8, 4).permute(0, 2, 4, 5, 1, 3).contiguous().view(-1)
+
+
+def _mx_unrepack_sf(MRSF: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    # the inverse of _mx_repack_sf: SFW [N, K/32], the padding bytes dropped
+    RB, T = N // 16, K // 128
+    R = (T + _MX_ROUND - 1) // _MX_ROUND
+    sf = MRSF.view(RB, R, 8, 4, 16, 4).permute(0, 4, 1, 5, 2, 3).reshape(RB, 16, R * _MX_ROUND, 4)
+    return sf[:, :, :T].reshape(N, K // 32)
 
 
 def mx_unrepack_w(MRW: torch.Tensor, MRSF: torch.Tensor, N: int, K: int):
@@ -151,10 +165,8 @@ def mx_unrepack_w(MRW: torch.Tensor, MRSF: torch.Tensor, N: int, K: int):
     if N <= 0 or K <= 0 or N % 16 or K % 128 or (MRW.numel(), MRSF.numel()) != _mx_repacked_bytes(N, K):
         raise RuntimeError(f"Value error in mx_unrepack_w: MRW / MRSF do not belong to a [{N}, {K}] MXFP4 weight (N % 16 == 0, K % 128 == 0)")
     RB, T = N // 16, K // 128
-    R = (T + _MX_ROUND - 1) // _MX_ROUND
     QW = MRW.view(RB, T, 4, 16, 16).permute(0, 3, 1, 2, 4).reshape(N, K // 2)
-    sf = MRSF.view(RB, R, 8, 4, 16, 4).permute(0, 4, 1, 5, 2, 3).reshape(RB, 16, R * _MX_ROUND, 4)
-    return QW, sf[:, :, :T].reshape(N, K // 32)
+    return QW, _mx_unrepack_sf(MRSF, N, K)
 
 
 @functools.lru_cache(maxsize=None)

@@ -106,7 +106,7 @@ class QLinearLayer(nn.Module):
 
     def __init__(self, originalLayer: nn.Linear, select_num, reorder_index, out_reorder_index=None, quant_type="NVFP4",
                  repack_for_decode: bool = False, repacked_only: bool = False, mx_repack_for_decode: bool = False,
-                 mx_repacked_only: bool = False, mx6_weight: str | None = None):
+                 mx_repacked_only: bool = False, mx6_weight: str | None = None, mx6_repack_for_decode: bool = False):
         """``repack_for_decode`` (extension, default off = the reference's behaviour and memory): additionally keep the
         weight in MFMA-operand-order tiles (``agemm.repack_w``) and use ``agemm.matmul_repacked`` for calls of at most 16
         tokens.  ``repacked_only`` (extension): keep ONLY that copy -- ``W`` / ``scale_w`` are registered as None, every call
@@ -119,7 +119,11 @@ class QLinearLayer(nn.Module):
         any token count, runs through ``agemm.mx_matmul_rw`` (the same bits again); ``agemm.mx_unrepack_w(MRW, MRSF, out_features, Kp)``
         rebuilds the reference-layout pair.  ``mx6_weight`` (quant_type='MXFP6' only): the weight's element, "e3m2" (the default:
         ``MXFP6_reorder_quantize_w``) or "e2m1" (``MXFP4_reorder_quantize_w``: the activations keep six bits, the weight four);
-        either way forward takes ``MXFP6_reorder_quantize_x``'s tuple and runs ``agemm.mx6_matmul``."""
+        either way forward takes ``MXFP6_reorder_quantize_x``'s tuple and runs ``agemm.mx6_matmul``.  ``mx6_repack_for_decode``
+        (extension, quant_type='MXFP6' only, either ``mx6_weight``): additionally keep the weight in MFMA operand order (``MRW`` / ``MRSF``:
+        ``agemm.mx6_repack_w`` for an e3m2 weight, ``agemm.mx_repack_w`` for an e2m1 one); calls of at most ``agemm.MX6_REPACKED_MAX_M``
+        tokens run through ``agemm.mx6_matmul_repacked``, longer ones through ``agemm.mx6_matmul`` -- the same bits for an e2m1 weight,
+        the same sums in another grouping, within the fp32 summation bound, for an e3m2 one."""
         super().__init__()
         if quant_type not in ("NVFP4", "MXFP4", "MXFP6"):
             raise NotImplementedError(f"quant_type={quant_type!r} is not built (NVFP4, MXFP4 and MXFP6 are)")
@@ -133,6 +137,8 @@ class QLinearLayer(nn.Module):
             raise ValueError("mx_repack_for_decode applies to quant_type='MXFP4' only (NVFP4 has repack_for_decode / repacked_only)")
         if mx_repacked_only and quant_type != "MXFP4":
             raise ValueError("mx_repacked_only applies to quant_type='MXFP4' only (NVFP4 has repacked_only)")
+        if mx6_repack_for_decode and quant_type != "MXFP6":
+            raise ValueError("mx6_repack_for_decode applies to quant_type='MXFP6' only (MXFP4 has mx_repack_for_decode, NVFP4 repack_for_decode)")
         self.in_features = originalLayer.in_features
         self.out_features = originalLayer.out_features
         if originalLayer.bias is not None:
@@ -154,6 +160,8 @@ class QLinearLayer(nn.Module):
         W, scale_w, scale = quantize_w(w, idx, self.select_num)
         RW, RSF = agemm.repack_w(W, scale_w) if (repack_for_decode or repacked_only) else (None, None)
         MRW, MRSF = agemm.mx_repack_w(W, scale_w) if (mx_repack_for_decode or mx_repacked_only) else (None, None)
+        if mx6_repack_for_decode:
+            MRW, MRSF = (agemm.mx6_repack_w if self.mx6_weight == "e3m2" else agemm.mx_repack_w)(W, scale_w)
         if repacked_only or mx_repacked_only:
             W = scale_w = None
         self.register_buffer("W", W)
@@ -170,7 +178,9 @@ class QLinearLayer(nn.Module):
         # `y = matmul(...); y = y + bias` (model/qLinearLayer.py:74-76): the bias add runs in the GEMM epilogue with the same
         # two roundings (the bf16 product, then the bf16 sum), so the result is bit-identical to the two torch steps
         bias = self.bias if self.bias is None or self.bias.dtype == torch.bfloat16 else None
-        if self.quant_type == "MXFP6":
+        if self.quant_type == "MXFP6" and self.MRW is not None and qx.shape[0] <= agemm.MX6_REPACKED_MAX_M:
+            y = agemm.mx6_matmul_repacked(qx, self.MRW, scale_x, self.MRSF, scale * self.scale, self.out_features, b_format=self.mx6_weight, bias=bias)
+        elif self.quant_type == "MXFP6":
             y = agemm.mx6_matmul(qx, self.W, scale_x, self.scale_w, scale * self.scale, b_format=self.mx6_weight, bias=bias)
         elif self.quant_type == "MXFP4" and self.W is None:         # mx_repacked_only: the one copy serves every token count
             y = agemm.mx_matmul_rw(qx, self.MRW, scale_x, self.MRSF, scale * self.scale, self.out_features, bias=bias)

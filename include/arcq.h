@@ -403,6 +403,34 @@ int arcq_gemm_mxfp4_repacked_silu_mul(const uint8_t *A, const uint8_t *MRW, cons
                                       int64_t M, int64_t N, int64_t K, float alpha_host, const float *alpha_dev, const void *bias,
                                       void *stream);
 
+/* ---- MXFP6 repacked weight: decode GEMMs (1 <= M <= 64) with e3m2 activations over a weight laid out in MFMA operand order -------------
+ * The weight of arcq_gemm_mxfp6 laid out once for the hardware; arcquant_amd/mx6.py:mx6_repack_w builds the arrays (pure data movement),
+ * mx6_unrepack_w inverts it.  N % 16 == 0, K % 128 == 0 (K = Kp).  With row block b = n / 16, r = n % 16, step t = k / 128,
+ * q = (k % 128) / 32, T = K / 128, lane l = 16*q + r:
+ *   b_format ARCQ_MX_B_E3M2: MRW is the layout MRW6, 3 * N * K / 4 bytes, no padding.  (b, t) owns the 1536 bytes at (b*T + t) * 1536:
+ *           MRW[(b*T + t) * 1536 + 16*l + j]           = QW[n][96*t + 24*q + j],       j = 0 .. 15
+ *           MRW[(b*T + t) * 1536 + 1024 + 8*l + j]     = QW[n][96*t + 24*q + 16 + j],  j = 0 .. 7
+ *         lane l's 24-byte block of (row 16*b + r, K elements [128*t + 32*q, +32)), unchanged, as the 16 bytes every lane has first and
+ *         the 8 bytes every lane has last: the six-register e3m2 B operand of one scaled 16x16x128 MFMA, fetched by a wave as one
+ *         contiguous 1 KB (16 bytes per lane) and one contiguous 512 bytes (8 per lane), both naturally aligned.
+ *   b_format ARCQ_MX_B_E2M1: MRW is MXFP4's repacked weight above, as mx_repack_w returns it (W4A6: no second copy).
+ *   MRSF  is MXFP4's above in both forms, arcq_mx_repacked_sf_bytes(N, K) bytes; no result depends on its padding bytes.
+ * A / SFA stay in the row-major form arcq_mx6_quantize_x writes.  Per output: K steps s = w mod 8 accumulated in ascending order per w
+ * (against an e3m2 weight two accumulations per step: the WEIGHT's codes of magnitude >= 2, then its others), the eight partial sums
+ * added w = 0 .. 7, then arcq_gemm_mxfp6's epilogue.  Against an e2m1 weight the result is BIT FOR BIT arcq_gemm_mxfp6's at M <= 64;
+ * against an e3m2 weight it is the same exact products grouped differently (arcq_gemm_mxfp6 splits the activations): equal within
+ * the fp32 summation bound, not bit for bit.  The weight is read once whatever M is. */
+int64_t arcq_mx6_repacked_w_bytes(int64_t N, int64_t K);    /* MRW6: 3 * N * K / 4; 0 unless N % 16 == 0 and K % 128 == 0 (both positive) */
+int arcq_gemm_mxfp6_repacked_supported(int64_t M, int64_t N, int64_t K);   /* 1 <= M <= 64, N % 16 == 0, K % 128 == 0 */
+/* arcq_gemm_mxfp6's contract (b_format, alpha, bias, residual -- may alias D --, out_dtype) with B given as (MRW, MRSF).
+ *   Status, all before any HIP call and in this order: ARCQ_ERR_SHAPE for an unknown b_format; then arcq_gemm_mxfp4_repacked's:
+ *   ARCQ_ERR_SHAPE for M or N < 0, K % 128 or N % 16; ARCQ_ERR_SHAPE for M > 64; ARCQ_ERR_SHAPE for a bad out_dtype; M == 0 or N == 0
+ *   returns ARCQ_OK; ARCQ_ERR_NULL for a NULL operand; ARCQ_ERR_SHAPE for a misaligned pointer (A, MRW, D 16 bytes; SFA, MRSF 4 bytes;
+ *   bias, residual 2 bytes). */
+int arcq_gemm_mxfp6_repacked(const uint8_t *A, const uint8_t *MRW, const uint8_t *SFA, const uint8_t *MRSF, void *D, int64_t M,
+                             int64_t N, int64_t K, int b_format, float alpha_host, const float *alpha_dev, const void *bias,
+                             const void *residual, int out_dtype, void *stream);
+
 /* ---- MXFP4 repacked weight, every batch size: one weight copy per layer ----------------------------------------------------------
  * The three GEMMs of the MXFP4 path over (MRW, MRSF) alone, for ANY M >= 0, so that a layer need not keep (QW, SFW) beside them.
  * M <= 64 runs the decode kernels above (arcq_gemm_mxfp4_rw at such an M IS arcq_gemm_mxfp4_repacked; the quantising form has a decode
