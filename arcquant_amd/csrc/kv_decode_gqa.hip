@@ -41,29 +41,16 @@
 
 namespace arcq {
 
-// the codes in bits 0-3 and 16-19 of x as two packed 16-bit values (exact: fp16 through 1024 + c, bf16 as the top half of the fp32)
-template <bool BF16>
-__device__ __forceinline__ uint32_t gq_code_pair(uint32_t x) {
-  x &= 0x000f000fu;
-  if constexpr (BF16) {
-    return (__float_as_uint((float)(x & 0xffu)) >> 16) | (__float_as_uint((float)(x >> 16)) & 0xffff0000u);
-  } else {
-    const f16x2 v = __builtin_bit_cast(f16x2, 0x64006400u | x);
-    const f16x2 k = {(_Float16)1024.0f, (_Float16)1024.0f};
-    return __builtin_bit_cast(uint32_t, v - k);
-  }
-}
-
 // the four pairs of one k-step from a word that holds them in nibbles (m, m + 4), m = 0..3
 template <bool BF16>
-__device__ __forceinline__ gq_u32x4 gq_code_word(uint32_t w) {
-  return gq_u32x4{gq_code_pair<BF16>(w), gq_code_pair<BF16>(w >> 4), gq_code_pair<BF16>(w >> 8), gq_code_pair<BF16>(w >> 12)};
+__device__ __forceinline__ u32x4 gq_code_word(uint32_t w) {
+  return u32x4{kv_code_pair<BF16>(w), kv_code_pair<BF16>(w >> 4), kv_code_pair<BF16>(w >> 8), kv_code_pair<BF16>(w >> 12)};
 }
 
 // what a lane holds of a block: 16 bytes of the K rows of tb + i and tb + 16 + i, one dword of the V rows of its eight slots, and the
 // (scale, zero) pair of position tb + lane % 32 (K's in lanes 0-31, V's in lanes 32-63)
 struct GqBlock {
-  gq_u32x4 k[2];
+  u32x4 k[2];
   uint32_t v[8];
   uint32_t prm;
 };
@@ -85,23 +72,21 @@ __global__ __launch_bounds__(kGqWaves * 64) void kv_decode_gqa_kernel(KvGqaParam
   // ---- this lane's query head: elements 32 c .. 32 c + 31, each k-step's eight in the order 0, 4, 1, 5, 2, 6, 3, 7 (a head past the
   //      group is a zero column: nothing of q is read for it)
   const bool head = i < p.g;
-  gq_u32x4 qf[4];
+  u32x4 qf[4];
   float qsum = 0.f;
   {
     const uint16_t* qrow = reinterpret_cast<const uint16_t*>(p.q) + ((size_t)b * p.Nq + (size_t)n * p.g + i) * kKvD + c * 32;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      gq_u32x4 w = {0u, 0u, 0u, 0u};
-      if (head) w = *reinterpret_cast<const gq_u32x4*>(qrow + ks * 8);
+      u32x4 w = {0u, 0u, 0u, 0u};
+      if (head) w = *reinterpret_cast<const u32x4*>(qrow + ks * 8);
 #pragma unroll
       for (int j = 0; j < 4; ++j) qsum += kv_to_f32<BF16>(w[j] & 0xffffu) + kv_to_f32<BF16>(w[j] >> 16);
-      qf[ks] = gq_u32x4{(w[0] & 0xffffu) | (w[2] << 16), (w[0] >> 16) | (w[2] & 0xffff0000u), (w[1] & 0xffffu) | (w[3] << 16),
+      qf[ks] = u32x4{(w[0] & 0xffffu) | (w[2] << 16), (w[0] >> 16) | (w[2] & 0xffff0000u), (w[1] & 0xffffu) | (w[3] << 16),
                         (w[1] >> 16) | (w[3] & 0xffff0000u)};
     }
   }
-  qsum += __shfl_xor(qsum, 16, 64);
-  qsum += __shfl_xor(qsum, 32, 64);
-  const float nqsum = -qsum;
+  const float nqsum = -kv_row_sum<kGqShare>(qsum);
 
   // slot j of this lane is position tb + slot[j] of the block; the lanes that looked that position up are slot[j] (K) and 32 + slot[j] (V)
   int slot[8];
@@ -112,16 +97,14 @@ __global__ __launch_bounds__(kGqWaves * 64) void kv_decode_gqa_kernel(KvGqaParam
     const int pos = min(tb + (lane & 31), T - 1);       // past the range: the sequence's last valid row, masked below
     const size_t row = kv_row(p.t, b, n, pos, p.L, p.layer, p.N, p.P);
     x.prm = p.param[row + (lane >> 5 ? vrows : (size_t)0)];
-    const uint32_t rlo = (uint32_t)row, rhi = (uint32_t)((uint64_t)row >> 32);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      const int src = u * 16 + i;
-      const size_t r = (size_t)__shfl(rlo, src, 64) | ((size_t)__shfl(rhi, src, 64) << 32);
-      x.k[u] = *reinterpret_cast<const gq_u32x4*>(p.data + r * 64 + c * 16);
+      const size_t r = gq_row_of(row, u * 16 + i);
+      x.k[u] = *reinterpret_cast<const u32x4*>(p.data + r * 64 + c * 16);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const size_t r = ((size_t)__shfl(rlo, slot[j], 64) | ((size_t)__shfl(rhi, slot[j], 64) << 32)) + vrows;
+      const size_t r = gq_row_of(row, slot[j]) + vrows;
       x.v[j] = *reinterpret_cast<const uint32_t*>(p.data + r * 64 + i * 4);
     }
   };
@@ -138,7 +121,7 @@ __global__ __launch_bounds__(kGqWaves * 64) void kv_decode_gqa_kernel(KvGqaParam
     for (int u = 0; u < 2; ++u) {
       sc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) sc[u] = gq_mfma<BF16>(gq_code_word<BF16>(x.k[u][ks]), qf[ks], sc[u]);
+      for (int ks = 0; ks < 4; ++ks) sc[u] = kv_mfma16<BF16>(gq_code_word<BF16>(x.k[u][ks]), qf[ks], sc[u]);
     }
     float sv[8], vs[8], vz[8];
     bool ok[8];
@@ -154,16 +137,7 @@ __global__ __launch_bounds__(kGqWaves * 64) void kv_decode_gqa_kernel(KvGqaParam
       sv[j] = ok[j] ? val : kKvIdle;
       mb = fmaxf(mb, sv[j]);
     }
-    mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-    mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-    const float mn = fmaxf(m, mb), alpha = __builtin_amdgcn_exp2f(m - mn);
-    m = mn;
-    if (__any(alpha != 1.0f)) {                          // (wave-uniform: once the maxima have settled most blocks rescale nothing)
-      l *= alpha;
-      zacc *= alpha;
-#pragma unroll
-      for (int m8 = 0; m8 < 8; ++m8) acc[m8] *= alpha;
-    }
+    kv_new_max<kGqShare>(mb, m, l, acc, zacc);
     // ---- weights: p_t s_t rounded once, the B fragment as it stands
     float w[8];
 #pragma unroll
@@ -173,7 +147,7 @@ __global__ __launch_bounds__(kGqWaves * 64) void kv_decode_gqa_kernel(KvGqaParam
       zacc = fmaf(pt, vz[j], zacc);
       w[j] = pt * vs[j];
     }
-    const gq_u32x4 wf = {gq_pack<BF16>(w[0], w[1]), gq_pack<BF16>(w[2], w[3]), gq_pack<BF16>(w[4], w[5]), gq_pack<BF16>(w[6], w[7])};
+    const u32x4 wf = kv_pack8<BF16>(w);
     // ---- values: z0[q] / z1[q] hold nibbles 0-3 / 4-7 of slots 2 q (low half) and 2 q + 1 (high half)
     uint32_t z0[4], z1[4];
 #pragma unroll
@@ -184,10 +158,10 @@ __global__ __launch_bounds__(kGqWaves * 64) void kv_decode_gqa_kernel(KvGqaParam
 #pragma unroll
     for (int m8 = 0; m8 < 8; ++m8) {
       const int sh = 4 * (m8 & 3);
-      gq_u32x4 a;
+      u32x4 a;
 #pragma unroll
-      for (int q2 = 0; q2 < 4; ++q2) a[q2] = gq_code_pair<BF16>((m8 < 4 ? z0[q2] : z1[q2]) >> sh);
-      acc[m8] = gq_mfma<BF16>(a, wf, acc[m8]);
+      for (int q2 = 0; q2 < 4; ++q2) a[q2] = kv_code_pair<BF16>((m8 < 4 ? z0[q2] : z1[q2]) >> sh);
+      acc[m8] = kv_mfma16<BF16>(a, wf, acc[m8]);
     }
   };
 
@@ -241,7 +215,7 @@ __global__ __launch_bounds__(kGqWaves * 64) void kv_decode_gqa_kernel(KvGqaParam
       float* o = p.ws + (bh * p.S + s) * kKvRec;
       o[2 + d] = a;
       if (d == 0) {
-        o[0] = M * 0.6931471805599453f;
+        o[0] = M * kKvLn2;
         o[1] = Ls;
       }
     }
@@ -264,14 +238,9 @@ int kv_decode_gqa_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t 
 int kv_decode_gqa(const KvDecodeArgs& a, hipStream_t stream) {
   const char* who = "arcq_kv_batch_decode_gqa";
   KvGqaParams p{};
-  p.o = a.o; p.q = a.q; p.data = (const uint8_t*)a.kv_data; p.param = (const uint32_t*)a.kv_param;
-  p.t = {a.kv_indptr, a.kv_indices, a.last_page_offset};
-  p.ws = (float*)a.workspace;
-  p.B = (int)a.B; p.Nq = (int)a.Nq; p.L = (int)a.L; p.layer = (int)a.layer; p.N = (int)a.N; p.P = (int)a.P;
-  p.g = (int)(a.Nq / a.N);
-  p.S = kv_decode_gqa_splits(a.B, a.Nq, a.N, a.nnz, a.P);
-  p.sm_scale = 0.12751743074602467f;                    // 128^-0.5 * log2(e): the softmax runs in base 2 (v_exp_f32)
-  const dim3 grid((unsigned)(a.B * a.N), (unsigned)p.S), block(kGqWaves * 64);
+  kv_gqa_fill(p, a);
+  p.param = (const uint32_t*)a.kv_param;
+  const dim3 grid = kv_gqa_grid(p, a), block(kGqWaves * 64);
   const int rc = a.dtype == ARCQ_KV_BF16 ? launch_kernel<kv_decode_gqa_kernel<true>>(grid, block, 0, stream, who, p)
                                          : launch_kernel<kv_decode_gqa_kernel<false>>(grid, block, 0, stream, who, p);
   if (rc != ARCQ_OK || p.S <= 1) return rc;

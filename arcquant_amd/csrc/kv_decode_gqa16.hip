@@ -42,8 +42,8 @@ constexpr int kG16RowBytes = kKvD * 2;
 // what a lane holds of a block: per score tile u and k-step s 16 bytes of the K row of tb + 16 u + i, and 16 bytes of the V row of each
 // of its eight slots -- 64 VGPRs
 struct G16Block {
-  gq_u32x4 k[2][4];
-  gq_u32x4 v[8];
+  u32x4 k[2][4];
+  u32x4 v[8];
 };
 
 template <bool BF16>
@@ -61,13 +61,13 @@ __global__ __launch_bounds__(kGqWaves * 64, 2) void kv_decode_gqa16_kernel(KvGqa
   const size_t vrows = (size_t)p.N * p.P;
 
   // ---- this lane's query head: k-step ks is elements 32 ks + 8 c .. + 7 (a head past the group is a zero column: nothing is read)
-  gq_u32x4 qf[4];
+  u32x4 qf[4];
   {
     const uint16_t* qrow = reinterpret_cast<const uint16_t*>(p.q) + ((size_t)b * p.Nq + (size_t)n * p.g + i) * kKvD + c * 8;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      qf[ks] = gq_u32x4{0u, 0u, 0u, 0u};
-      if (i < p.g) qf[ks] = *reinterpret_cast<const gq_u32x4*>(qrow + ks * 32);
+      qf[ks] = u32x4{0u, 0u, 0u, 0u};
+      if (i < p.g) qf[ks] = *reinterpret_cast<const u32x4*>(qrow + ks * 32);
     }
   }
 
@@ -79,19 +79,17 @@ __global__ __launch_bounds__(kGqWaves * 64, 2) void kv_decode_gqa16_kernel(KvGqa
   auto load_block = [&](int tb, G16Block& x) __attribute__((always_inline)) {
     const int pos = min(tb + (lane & 31), T - 1);       // past the range: the sequence's last valid row, masked below
     const size_t row = kv_row(p.t, b, n, pos, p.L, p.layer, p.N, p.P);
-    const uint32_t rlo = (uint32_t)row, rhi = (uint32_t)((uint64_t)row >> 32);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      const int src = u * 16 + i;
-      const size_t r = (size_t)__shfl(rlo, src, 64) | ((size_t)__shfl(rhi, src, 64) << 32);
+      const size_t r = gq_row_of(row, u * 16 + i);
       const uint8_t* krow = p.data + r * kG16RowBytes + c * 16;
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) x.k[u][ks] = *reinterpret_cast<const gq_u32x4*>(krow + ks * 64);
+      for (int ks = 0; ks < 4; ++ks) x.k[u][ks] = *reinterpret_cast<const u32x4*>(krow + ks * 64);
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const size_t r = ((size_t)__shfl(rlo, slot[j], 64) | ((size_t)__shfl(rhi, slot[j], 64) << 32)) + vrows;
-      x.v[j] = *reinterpret_cast<const gq_u32x4*>(p.data + r * kG16RowBytes + i * 16);
+      const size_t r = gq_row_of(row, slot[j]) + vrows;
+      x.v[j] = *reinterpret_cast<const u32x4*>(p.data + r * kG16RowBytes + i * 16);
     }
   };
 
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(kGqWaves * 64, 2) void kv_decode_gqa16_kernel(KvGqa
     for (int u = 0; u < 2; ++u) {
       sc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) sc[u] = gq_mfma<BF16>(x.k[u][ks], qf[ks], sc[u]);
+      for (int ks = 0; ks < 4; ++ks) sc[u] = kv_mfma16<BF16>(x.k[u][ks], qf[ks], sc[u]);
     }
     float sv[8];
     bool ok[8];
@@ -118,15 +116,7 @@ __global__ __launch_bounds__(kGqWaves * 64, 2) void kv_decode_gqa16_kernel(KvGqa
       sv[j] = ok[j] ? sc[j >> 2][j & 3] * p.sm_scale : kKvIdle;
       mb = fmaxf(mb, sv[j]);
     }
-    mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-    mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-    const float mn = fmaxf(m, mb), alpha = __builtin_amdgcn_exp2f(m - mn);
-    m = mn;
-    if (__any(alpha != 1.0f)) {                          // (wave-uniform: once the maxima have settled most blocks rescale nothing)
-      l *= alpha;
-#pragma unroll
-      for (int m8 = 0; m8 < 8; ++m8) acc[m8] *= alpha;
-    }
+    kv_new_max<kGqShare>(mb, m, l, acc);
     // ---- weights: rounded once, the B fragment as it stands
     float w[8];
 #pragma unroll
@@ -134,14 +124,14 @@ __global__ __launch_bounds__(kGqWaves * 64, 2) void kv_decode_gqa16_kernel(KvGqa
       w[j] = ok[j] ? __builtin_amdgcn_exp2f(sv[j] - m) : 0.f;
       l += w[j];
     }
-    const gq_u32x4 wf = {gq_pack<BF16>(w[0], w[1]), gq_pack<BF16>(w[2], w[3]), gq_pack<BF16>(w[4], w[5]), gq_pack<BF16>(w[6], w[7])};
+    const u32x4 wf = kv_pack8<BF16>(w);
     // ---- values: tile m8's fragment is half-word m8 of the eight slot vectors, slots 2 q (low half) and 2 q + 1 (high half) to a register
 #pragma unroll
     for (int m8 = 0; m8 < 8; ++m8) {
-      gq_u32x4 a;
+      u32x4 a;
 #pragma unroll
       for (int q2 = 0; q2 < 4; ++q2) a[q2] = __builtin_amdgcn_perm(x.v[2 * q2 + 1][m8 >> 1], x.v[2 * q2][m8 >> 1], m8 & 1 ? 0x07060302u : 0x05040100u);
-      acc[m8] = gq_mfma<BF16>(a, wf, acc[m8]);
+      acc[m8] = kv_mfma16<BF16>(a, wf, acc[m8]);
     }
   };
 
@@ -193,7 +183,7 @@ __global__ __launch_bounds__(kGqWaves * 64, 2) void kv_decode_gqa16_kernel(KvGqa
       float* o = p.ws + (bh * p.S + s) * kKvRec;
       o[2 + d] = a;
       if (d == 0) {
-        o[0] = M * 0.6931471805599453f;
+        o[0] = M * kKvLn2;
         o[1] = Ls;
       }
     }
@@ -204,14 +194,8 @@ __global__ __launch_bounds__(kGqWaves * 64, 2) void kv_decode_gqa16_kernel(KvGqa
 int kv_decode_gqa16(const KvDecodeArgs& a, hipStream_t stream) {
   const char* who = "arcq_kv_batch_decode_gqa_16bit";
   KvGqaParams p{};
-  p.o = a.o; p.q = a.q; p.data = (const uint8_t*)a.kv_data;
-  p.t = {a.kv_indptr, a.kv_indices, a.last_page_offset};
-  p.ws = (float*)a.workspace;
-  p.B = (int)a.B; p.Nq = (int)a.Nq; p.L = (int)a.L; p.layer = (int)a.layer; p.N = (int)a.N; p.P = (int)a.P;
-  p.g = (int)(a.Nq / a.N);
-  p.S = kv_decode_gqa_splits(a.B, a.Nq, a.N, a.nnz, a.P);
-  p.sm_scale = 0.12751743074602467f;                    // 128^-0.5 * log2(e): the softmax runs in base 2 (v_exp_f32)
-  const dim3 grid((unsigned)(a.B * a.N), (unsigned)p.S), block(kGqWaves * 64);
+  kv_gqa_fill(p, a);
+  const dim3 grid = kv_gqa_grid(p, a), block(kGqWaves * 64);
   const int rc = a.dtype == ARCQ_KV_BF16 ? launch_kernel<kv_decode_gqa16_kernel<true>>(grid, block, 0, stream, who, p)
                                          : launch_kernel<kv_decode_gqa16_kernel<false>>(grid, block, 0, stream, who, p);
   if (rc != ARCQ_OK || p.S <= 1) return rc;

@@ -1,10 +1,13 @@
-// Device-side helpers shared by the paged KV cache kernels (kv_cache.hip, kv_prefill.hip, kv_rope.hip): the tables of include/arcq_kv.h,
-// the row addressing of the reference's page layout, the two 16-bit element types, and what the quantising writers share.
+// Device-side helpers shared by the paged KV cache kernels (kv_cache.hip, kv_rope.hip, and through kv_prefill_device.hpp and
+// kv_gqa_device.hpp the MFMA attention units kv_prefill.hip, kv_prefill16.hip, kv_decode_gqa.hip, kv_decode_gqa16.hip): the tables of
+// include/arcq_kv.h, the row addressing of the reference's page layout, the two 16-bit element types with their MFMA operand forms, the
+// constants and lane exchanges of the MFMA attention kernels' base-2 softmax, and what the quantising writers share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "arcq_device.hpp"
+#include "gemm_common.hpp"
 
 namespace arcq {
 
@@ -40,6 +43,73 @@ __device__ __forceinline__ uint32_t kv_from_f32(float f) {
 }
 template <bool BF16>
 __device__ __forceinline__ float kv_round(float f) { return kv_to_f32<BF16>(kv_from_f32<BF16>(f)); }
+
+// MFMA operands of either type travel as dwords: eight 16-bit elements are a u32x4
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// v_mfma_f32_32x32x16_{f16,bf16} (prefill) and v_mfma_f32_16x16x32_{f16,bf16} (GQA decode)
+template <bool BF16>
+__device__ __forceinline__ f32x16 kv_mfma32(u32x4 a, u32x4 b, f32x16 c) {
+  if constexpr (BF16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+template <bool BF16>
+__device__ __forceinline__ f32x4 kv_mfma16(u32x4 a, u32x4 b, f32x4 c) {
+  if constexpr (BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+
+// two fp32 weights rounded to the 16-bit type (nearest even), a in the low half
+template <bool BF16>
+__device__ __forceinline__ uint32_t kv_pack2(float a, float b) {
+  if constexpr (BF16) {
+    return pack_bf16x2_hw(a, b);
+  } else {
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    const f32x2_t v = {a, b};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
+  }
+}
+// eight of them: one operand fragment
+template <bool BF16>
+__device__ __forceinline__ u32x4 kv_pack8(const float* w) {
+  return u32x4{kv_pack2<BF16>(w[0], w[1]), kv_pack2<BF16>(w[2], w[3]), kv_pack2<BF16>(w[4], w[5]), kv_pack2<BF16>(w[6], w[7])};
+}
+
+// the int4 codes in bits 0-3 and 16-19 of x as two packed 16-bit values (exact: fp16 through 1024 + c, bf16 as the top half of the fp32)
+template <bool BF16>
+__device__ __forceinline__ uint32_t kv_code_pair(uint32_t x) {
+  x &= 0x000f000fu;
+  if constexpr (BF16) {
+    return (__float_as_uint((float)(x & 0xffu)) >> 16) | (__float_as_uint((float)(x >> 16)) & 0xffff0000u);
+  } else {
+    const f16x2 v = __builtin_bit_cast(f16x2, 0x64006400u | x);
+    const f16x2 k = {(_Float16)1024.0f, (_Float16)1024.0f};
+    return __builtin_bit_cast(uint32_t, v - k);
+  }
+}
+
+// ---- the online softmax of the MFMA attention kernels.  It runs in base 2 (v_exp_f32): the launchers fold log2(e) into the score scale,
+//      and a maximum that leaves its kernel as a natural-log score is multiplied by ln 2.
+constexpr float kKvSmScaleLog2 = 0.12751743074602467f;   // 128^-1/2 * log2(e)
+constexpr float kKvLn2 = 0.6931471805599453f;
+
+// A query row's state is spread over the lanes whose numbers differ in the bits of SHARE (32: prefill's two lane halves; 16 | 32: the GQA
+// kernels' four k-groups).  The sum and the maximum of x over those lanes, in every one of them:
+template <int SHARE>
+__device__ __forceinline__ float kv_row_sum(float x) {
+  if constexpr (SHARE & 16) x += __shfl_xor(x, 16, 64);
+  if constexpr (SHARE & 32) x += __shfl_xor(x, 32, 64);
+  return x;
+}
+template <int SHARE>
+__device__ __forceinline__ float kv_row_max(float x) {
+  if constexpr (SHARE & 16) x = fmaxf(x, __shfl_xor(x, 16, 64));
+  if constexpr (SHARE & 32) x = fmaxf(x, __shfl_xor(x, 32, 64));
+  return x;
+}
 
 // ---- the writers' parameters, token lookup and row quantiser (kv_cache.hip, kv_rope.hip)
 struct KvWriteParams {

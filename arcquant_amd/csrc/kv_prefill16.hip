@@ -1,12 +1,7 @@
 // Causal prefill attention over the 16-bit pages of include/arcq_kv.h (arcq_kv_batch_prefill_16bit) on v_mfma_f32_32x32x16_{f16,bf16}.
 //
-//   grid (tiles, N * chunks), 256 threads = 4 waves.  The work split is kv_prefill.hip's: a workgroup owns a tile of 128 query-row slots
-//   of one (sequence, kv head), slot r = (token r / hc of the tile, head ch * hc + r % hc of the kv head's group), hc = min(g, 128) and
-//   tpt = 128 / hc tokens per tile, so the g heads of a group share every K / V block; workgroup x walks qo_indptr to its (sequence, tile)
-//   or leaves (the launch has ceil(ntok / tpt) + B tiles).  A wave owns 32 slots and keeps its query rows in registers.
-//
-//   Per block of 32 kv positions (blocks wholly above the tile's last query position are never visited; a wave skips the MFMAs of
-//   blocks above its own):
+//   The work split and the MFMA roles are kv_prefill.hip's and are described in kv_prefill_device.hpp, with the LDS strides as far as the
+//   fragment reads go.  What is this kernel's own, per block of 32 kv positions:
 //     staging   a block is 32 K rows and 32 V rows of 256 bytes: 1024 pieces of 16 bytes, four per thread, and ALL four waves stage.
 //               Thread (rp, vc) takes the 16 bytes vc of rows 2 rp and 2 rp + 1, of K and of V: one pair of page lookups serves the four
 //               loads, and four adjacent lanes read 64 contiguous bytes.  The pieces are loaded one block ahead into registers.  Rows
@@ -15,19 +10,12 @@
 //               K goes to LDS as [position][d], one 16-byte write per piece.  V goes transposed as [d][position'] with position' =
 //               position with bits 2 and 3 swapped (the k order in which the score tile presents its rows): the thread's two rows are
 //               adjacent in that order too, so element e of both is one packed pair and one 32-bit write into row 8 vc + e.
-//     scores    S^T = K Q^T: K from LDS is the A operand, the wave's 32 query rows (registers, loaded once) the B operand; lane (i, h)
-//               holds query column i and positions 8 (r >> 2) + 4 h + (r & 3) in accumulator registers r = 0..15.  Eight MFMAs;
-//               score = sm_scale * s in fp32 with sm_scale = 128^-1/2 log2(e): the softmax runs in base 2.
-//     softmax   online, per lane + one exchange with lane i + 32; the causal mask is a select on the score and on the weight; the
-//               accumulators are rescaled only in a block that moved some lane's maximum.
-//     values    O^T += V^T P^T: registers 8 s .. 8 s + 7 of the weight tile, rounded once to the 16-bit type, are the B fragment of
-//               k-step s with no lane movement; V^T comes from LDS.  The row sum is an fp32 VALU sum over the unrounded weights.
-//   O^T leaves lane (i, h) holding four consecutive d per register group: 8-byte stores of O / l (zeros when l == 0).
+//     scores    score = sm_scale * s in fp32 with sm_scale = 128^-1/2 log2(e): the softmax runs in base 2.
+//   The stores are of O / l.
 //
-//   LDS strides.  K rows are 136 elements (272 bytes = 68 banks of 4 bytes) apart: a 16-byte fragment read of lane (i, h) starts at
-//   bank 4 i + const (mod 64), so 16 lanes of consecutive i cover the 64 banks once; the staging writes of four lanes fill 64 contiguous
-//   bytes and the lanes are ordered so that 16 consecutive ones write rows 4 apart -- the same cover.  V^T rows are 40 elements (80
-//   bytes = 20 banks) apart: a fragment read starts at bank 20 i + const and i -> 5 i (mod 16) permutes the sixteen 4-bank groups.  A
+//   LDS strides and the staging writes.  K rows are 68 banks apart and 16 fragment reads of consecutive i cover the 64 banks once
+//   (kv_prefill_device.hpp); the staging writes of four lanes fill 64 contiguous bytes and the lanes are ordered so that 16 consecutive
+//   ones write rows 4 apart -- the same cover.  V^T rows are 20 banks apart.  A
 //   wave's 32-bit V^T writes go to banks 32 vc + 20 e + tp: tp takes 16 consecutive values, 32 vc only two, so the lanes whose vc has bit 1 set
 //   write their eight pairs in the order 4..7, 0..3 -- 20 * 4 = 16 (mod 64) moves them into the banks the others leave free.
 //
@@ -40,13 +28,10 @@
 #include "arcq_internal.hpp"
 #include "gemm_common.hpp"
 #include "kv_device.hpp"
+#include "kv_prefill_device.hpp"
 
 namespace arcq {
 
-constexpr int kP16Rows = 128;      // query-row slots of a tile
-constexpr int kP16Blk = 32;        // kv positions per block
-constexpr int kP16KStride = 136;   // 16-bit elements of a K row in LDS
-constexpr int kP16VStride = 40;    // of a V^T row
 constexpr int kP16RowBytes = kKvD * 2;
 
 struct KvPrefill16Params {
@@ -59,37 +44,15 @@ struct KvPrefill16Params {
   float sm_scale;
 };
 
-typedef __bf16 p16_bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t p16_u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t p16_u32x2 __attribute__((ext_vector_type(2)));
-
-template <bool BF16>
-__device__ __forceinline__ f32x16 p16_mfma(p16_u32x4 a, p16_u32x4 b, f32x16 c) {
-  if constexpr (BF16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(p16_bf16x8, a), __builtin_bit_cast(p16_bf16x8, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-// two fp32 weights rounded to the 16-bit type (nearest even), a in the low half
-template <bool BF16>
-__device__ __forceinline__ uint32_t p16_pack(float a, float b) {
-  if constexpr (BF16) {
-    return pack_bf16x2_hw(a, b);
-  } else {
-    typedef float f32x2_t __attribute__((ext_vector_type(2)));
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
-  }
-}
-
 // what a thread holds of the next block: the 16 bytes vc of K rows 2 rp, 2 rp + 1 and of V rows 2 rp, 2 rp + 1
 struct P16Stage {
-  p16_u32x4 ka, kb, va, vb;
+  u32x4 ka, kb, va, vb;
 };
 
 template <bool BF16>
 __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params p) {
-  __shared__ __attribute__((aligned(16))) uint16_t k_lds[kP16Blk * kP16KStride];
-  __shared__ __attribute__((aligned(16))) uint16_t v_lds[kKvD * kP16VStride];
+  __shared__ __attribute__((aligned(16))) uint16_t k_lds[kPfBlk * kPfKStride];
+  __shared__ __attribute__((aligned(16))) uint16_t v_lds[kKvD * kPfVStride];
 
   // ---- this workgroup's (sequence, tile) or nothing
   int x = blockIdx.x, b = 0, q0 = 0, nb = 0;
@@ -107,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
   const int tok0 = x * p.tpt;                           // first token of the tile inside the sequence
   const int base = T - nb;                              // position of the sequence's first query token
   const int tile_last = base + min(nb, tok0 + p.tpt) - 1;              // the tile's causal limit
-  const int nblk = tile_last / kP16Blk + 1;
+  const int nblk = tile_last / kPfBlk + 1;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -124,11 +87,11 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
   const int wave_last = (wtl0 < p.tpt && tok0 + wtl0 < nb) ? base + min(tok0 + wtl1, nb - 1) : -1;
   const size_t orow = ((size_t)(q0 + tok) * p.Nq + (size_t)n * p.g + head) * kKvD;
 
-  p16_u32x4 qf[8];
+  u32x4 qf[8];
 #pragma unroll
   for (int ks = 0; ks < 8; ++ks) {
-    qf[ks] = p16_u32x4{0u, 0u, 0u, 0u};
-    if (valid) qf[ks] = *reinterpret_cast<const p16_u32x4*>(reinterpret_cast<const uint16_t*>(p.q) + orow + ks * 16 + h * 8);
+    qf[ks] = u32x4{0u, 0u, 0u, 0u};
+    if (valid) qf[ks] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const uint16_t*>(p.q) + orow + ks * 16 + h * 8);
   }
 
   // ---- staging role: piece vc (16 bytes = 8 d) of rows 2 rp and 2 rp + 1.  Lanes 0..3 of a quad take adjacent pieces; the quads of a
@@ -139,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
   const int r0 = 2 * rp;
   const int tp = (rp & 9) | ((rp & 2) << 1) | ((rp & 4) >> 1);          // the pair's place in position' order: bits 1 and 2 of rp swapped
   // (page slot, entry) of position tb + r0, carried from block to block; those of T - 1, where the loads clamp
-  const int d32 = kP16Blk / p.P, r32 = kP16Blk - d32 * p.P;
+  const int d32 = kPfBlk / p.P, r32 = kPfBlk - d32 * p.P;
   const int pgT = (T - 1) / p.P, eT = (T - 1) - pgT * p.P;
   int pg = r0 / p.P, en = r0 - pg * p.P;
   const int32_t* own = p.t.indices + p.t.indptr[b];                     // the sequence's pages
@@ -161,10 +124,10 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
     }
     const uint8_t* ra = p.data + ((size_t)own[pa] * page_rows + head_row + ea) * kP16RowBytes + vc * 16;
     const uint8_t* rb = p.data + ((size_t)own[pb] * page_rows + head_row + eb) * kP16RowBytes + vc * 16;
-    s.ka = *reinterpret_cast<const p16_u32x4*>(ra);
-    s.kb = *reinterpret_cast<const p16_u32x4*>(rb);
-    s.va = *reinterpret_cast<const p16_u32x4*>(ra + v_rows * kP16RowBytes);
-    s.vb = *reinterpret_cast<const p16_u32x4*>(rb + v_rows * kP16RowBytes);
+    s.ka = *reinterpret_cast<const u32x4*>(ra);
+    s.kb = *reinterpret_cast<const u32x4*>(rb);
+    s.va = *reinterpret_cast<const u32x4*>(ra + v_rows * kP16RowBytes);
+    s.vb = *reinterpret_cast<const u32x4*>(rb + v_rows * kP16RowBytes);
     en += r32;                                                          // en, r32 < P: one correction
     pg += d32;
     if (en >= p.P) {
@@ -173,13 +136,13 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
     }
   };
   const bool flip = (vc >> 1) & 1;
-  uint16_t* const kdst = &k_lds[r0 * kP16KStride + vc * 8];
-  uint16_t* const vdst = &v_lds[(vc * 8) * kP16VStride + 2 * tp];
-  uint16_t* const vdst_lo = vdst + (flip ? 4 * kP16VStride : 0);        // where the first four writes go, and the last four
-  uint16_t* const vdst_hi = vdst + (flip ? 0 : 4 * kP16VStride);
+  uint16_t* const kdst = &k_lds[r0 * kPfKStride + vc * 8];
+  uint16_t* const vdst = &v_lds[(vc * 8) * kPfVStride + 2 * tp];
+  uint16_t* const vdst_lo = vdst + (flip ? 4 * kPfVStride : 0);        // where the first four writes go, and the last four
+  uint16_t* const vdst_hi = vdst + (flip ? 0 : 4 * kPfVStride);
   auto stage = [&](const P16Stage& s) __attribute__((always_inline)) {
-    *reinterpret_cast<p16_u32x4*>(kdst) = s.ka;
-    *reinterpret_cast<p16_u32x4*>(kdst + kP16KStride) = s.kb;
+    *reinterpret_cast<u32x4*>(kdst) = s.ka;
+    *reinterpret_cast<u32x4*>(kdst + kPfKStride) = s.kb;
     uint32_t pair[8];                                                   // element e of row 2 rp (low half) and of row 2 rp + 1
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -188,8 +151,8 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      *reinterpret_cast<uint32_t*>(vdst_lo + e * kP16VStride) = flip ? pair[e + 4] : pair[e];
-      *reinterpret_cast<uint32_t*>(vdst_hi + e * kP16VStride) = flip ? pair[e] : pair[e + 4];
+      *reinterpret_cast<uint32_t*>(vdst_lo + e * kPfVStride) = flip ? pair[e + 4] : pair[e];
+      *reinterpret_cast<uint32_t*>(vdst_hi + e * kPfVStride) = flip ? pair[e] : pair[e + 4];
     }
   };
 
@@ -203,18 +166,18 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
   P16Stage st;
   fetch(0, st);
   for (int blk = 0; blk < nblk; ++blk) {
-    const int tb = blk * kP16Blk;
+    const int tb = blk * kPfBlk;
     stage(st);
     __syncthreads();
-    if (blk + 1 < nblk) fetch(tb + kP16Blk, st);         // in flight behind this block's MFMAs
+    if (blk + 1 < nblk) fetch(tb + kPfBlk, st);         // in flight behind this block's MFMAs
     if (tb <= wave_last) {
       f32x16 s;
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) {
-        const p16_u32x4 a = *reinterpret_cast<const p16_u32x4*>(&k_lds[i * kP16KStride + ks * 16 + h * 8]);
-        s = p16_mfma<BF16>(a, qf[ks], s);
+        const u32x4 a = *reinterpret_cast<const u32x4*>(&k_lds[i * kPfKStride + ks * 16 + h * 8]);
+        s = kv_mfma32<BF16>(a, qf[ks], s);
       }
       // register r of lane half h is position tb + 8 (r >> 2) + 4 h + (r & 3)
       bool ok[16];
@@ -241,17 +204,17 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
         w[r] = ok[r] ? __builtin_amdgcn_exp2f(s[r] - m) : 0.f;
         l += w[r];
       }
-      p16_u32x4 pf[2];
+      u32x4 pf[2];
 #pragma unroll
       for (int sk = 0; sk < 2; ++sk)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) pf[sk][j] = p16_pack<BF16>(w[sk * 8 + 2 * j], w[sk * 8 + 2 * j + 1]);
+        for (int j = 0; j < 4; ++j) pf[sk][j] = kv_pack2<BF16>(w[sk * 8 + 2 * j], w[sk * 8 + 2 * j + 1]);
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
         for (int sk = 0; sk < 2; ++sk) {
-          const p16_u32x4 a = *reinterpret_cast<const p16_u32x4*>(&v_lds[(dt * 32 + i) * kP16VStride + sk * 16 + h * 8]);
-          acc[dt] = p16_mfma<BF16>(a, pf[sk], acc[dt]);
+          const u32x4 a = *reinterpret_cast<const u32x4*>(&v_lds[(dt * 32 + i) * kPfVStride + sk * 16 + h * 8]);
+          acc[dt] = kv_mfma32<BF16>(a, pf[sk], acc[dt]);
         }
     }
     __syncthreads();
@@ -269,8 +232,8 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
       float y[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) y[e] = acc[dt][gq * 4 + e] * inv;
-      const p16_u32x2 pk = {kv_from_f32<BF16>(y[0]) | (kv_from_f32<BF16>(y[1]) << 16), kv_from_f32<BF16>(y[2]) | (kv_from_f32<BF16>(y[3]) << 16)};
-      *reinterpret_cast<p16_u32x2*>(orow_p + dt * 32 + gq * 8 + h * 4) = pk;
+      const u32x2 pk = {kv_from_f32<BF16>(y[0]) | (kv_from_f32<BF16>(y[1]) << 16), kv_from_f32<BF16>(y[2]) | (kv_from_f32<BF16>(y[3]) << 16)};
+      *reinterpret_cast<u32x2*>(orow_p + dt * 32 + gq * 8 + h * 4) = pk;
     }
 }
 
@@ -278,16 +241,8 @@ __global__ __launch_bounds__(256, 2) void kv_prefill16_kernel(KvPrefill16Params 
 int kv_prefill16(const KvPrefillArgs& a, hipStream_t stream) {
   const char* who = "arcq_kv_batch_prefill_16bit";
   KvPrefill16Params p{};
-  p.o = a.o; p.q = a.q; p.qo_indptr = a.qo_indptr; p.data = (const uint8_t*)a.kv_data;
-  p.t = {a.kv_indptr, a.kv_indices, a.last_page_offset};
-  p.B = (int)a.B; p.Nq = (int)a.Nq; p.L = (int)a.L; p.layer = (int)a.layer; p.N = (int)a.N; p.P = (int)a.P;
-  p.g = (int)(a.Nq / a.N);
-  p.hc = p.g < kP16Rows ? p.g : kP16Rows;
-  p.tpt = kP16Rows / p.hc;
-  p.chunks = (p.g + p.hc - 1) / p.hc;
-  p.sm_scale = 0.12751743074602467f;                    // 128^-0.5 * log2(e): the softmax runs in base 2 (v_exp_f32)
-  const int64_t tiles = (a.ntok + p.tpt - 1) / p.tpt + a.B;
-  const dim3 grid((unsigned)tiles, (unsigned)(a.N * p.chunks)), block(256);
+  kv_prefill_fill(p, a);
+  const dim3 grid = kv_prefill_grid(p, a), block(256);
   if (a.dtype == ARCQ_KV_BF16) return launch_kernel<kv_prefill16_kernel<true>>(grid, block, 0, stream, who, p);
   return launch_kernel<kv_prefill16_kernel<false>>(grid, block, 0, stream, who, p);
 }
