@@ -112,6 +112,9 @@ KV_SYMBOLS = {
     "arcq_kv_decode_gqa_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64]),
     "arcq_kv_batch_decode_gqa": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p]),
     "arcq_kv_batch_decode_gqa_16bit": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _i64, _p]),
+    "arcq_kv_fp8_append_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i32, _p]),
+    "arcq_kv_fp8_init_quantize": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p]),
+    "arcq_kv_batch_decode_gqa_fp8": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _p, _i64, _p]),
     "arcq_kv_decode_step_state_bytes":(_i64, [_i64, _i64, _i64]),
     "arcq_kv_decode_step": (_i32, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _p, _i64, _p,
                                    _i64, _p]),

@@ -329,6 +329,10 @@ int kv_decode_gqa_splits(int64_t B, int64_t Nq, int64_t N, int64_t nnz, int64_t 
 int kv_decode_gqa(const KvDecodeArgs& a, hipStream_t stream);
 // kv_decode_gqa16.hip: the same pass over the 16-bit pages of a.dtype (a.kv_param is not read; kv_decode_gqa_splits' slices)
 int kv_decode_gqa16(const KvDecodeArgs& a, hipStream_t stream);
+// kv_decode_gqa8.hip: the same pass over FP8 (e4m3) pages with fp16 (scale, 0) pairs in a.kv_param (a.format is not read)
+int kv_decode_gqa8(const KvDecodeArgs& a, hipStream_t stream);
+// kv_write8.hip: the quantising writers of that cache (a.quantize = true; a.k_param, a.v_param and a.format are not read)
+int kv_write8(const KvWriteArgs& a, hipStream_t stream);
 
 // kv_rope.hip: rotary position embedding in front of the quantising writers, and alone (arguments validated by c_api_kv.hip)
 struct KvRopeArgs {

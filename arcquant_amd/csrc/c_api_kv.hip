@@ -104,6 +104,20 @@ int write_call(const char* who, KvWriteArgs& a, bool init, void* stream) {
   return kv_write(a, (hipStream_t)stream);
 }
 
+// the FP8 cache's quantising writers: write_call's checks of a quantising write, in its order.  The entry points take no format (geometry
+// gets one it accepts); a workgroup takes 32 rows (kv_write8)
+int write8_call(const char* who, KvWriteArgs& a, bool init, void* stream) {
+  int rc;
+  if ((rc = geometry(who, a.B, a.L, a.layer, a.N, a.P, ARCQ_KV_INT4)) || (rc = dtype_ok(who, a.dtype)) || (rc = ntok_ok(who, a.ntok))) return rc;
+  if (a.ntok * 2 * a.N > 32 * (int64_t)INT32_MAX) return fail(ARCQ_ERR_SHAPE, "%s: ntok * 2 N rows are out of range", who);
+  if (a.B == 0 || a.ntok == 0) return ARCQ_OK;
+  if ((rc = none_null(who, {a.kv_data, a.kv_param, a.kv_indptr, a.kv_indices, a.last_page_offset, a.k, a.v, when(init, a.seqlen_indptr)})) ||
+      (rc = aligned16(who, {a.kv_data, a.k, a.v}, "kv_data, k and v")) ||
+      (rc = aligned4(who, {a.kv_param, a.kv_indptr, a.kv_indices, a.last_page_offset, a.seqlen_indptr}, "kv_param and the index tensors")))
+    return rc;
+  return kv_write8(a, (hipStream_t)stream);
+}
+
 // a contiguous [ntok, heads, 128] result and a strided source of the same rows: the same tensor, or apart
 bool overlaps(const void* out, const void* in, int64_t ntok, int64_t heads, int64_t in_stride) {
   const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), o1 = o0 + (uintptr_t)(ntok * heads * 256);
@@ -273,6 +287,39 @@ int arcq_kv_batch_decode_gqa_16bit(void* o, const void* q, const void* kv_data, 
     return rc;
   KvDecodeArgs a{o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, B, Nq, L, layer_idx, N, P, nnz, ARCQ_KV_16BIT, dtype, workspace};
   return kv_decode_gqa16(a, (hipStream_t)stream);
+}
+
+int arcq_kv_fp8_append_quantize(void* kv_data, void* kv_param, const int32_t* kv_indptr, const int32_t* kv_indices, const int32_t* last_page_offset,
+                                const void* k, const void* v, int64_t B, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int dtype, void* stream) {
+  KvWriteArgs a{kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, k, v, nullptr, nullptr, nullptr, B, B, L, layer_idx, N, P, ARCQ_KV_FP8, dtype,
+                true};
+  return write8_call("arcq_kv_fp8_append_quantize", a, false, stream);
+}
+
+int arcq_kv_fp8_init_quantize(void* kv_data, void* kv_param, const int32_t* kv_indptr, const int32_t* kv_indices, const int32_t* last_page_offset,
+                              const void* k, const void* v, const int32_t* seqlen_indptr, int64_t ntok, int64_t B, int64_t L, int64_t layer_idx,
+                              int64_t N, int64_t P, int dtype, void* stream) {
+  KvWriteArgs a{kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, k, v, nullptr, nullptr, seqlen_indptr, ntok, B, L, layer_idx, N, P, ARCQ_KV_FP8,
+                dtype, true};
+  return write8_call("arcq_kv_fp8_init_quantize", a, true, stream);
+}
+
+int arcq_kv_batch_decode_gqa_fp8(void* o, const void* q, const void* kv_data, const void* kv_param, const int32_t* kv_indptr, const int32_t* kv_indices,
+                                 const int32_t* last_page_offset, int64_t B, int64_t Nq, int64_t L, int64_t layer_idx, int64_t N, int64_t P,
+                                 int64_t nnz, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "arcq_kv_batch_decode_gqa_fp8";
+  int rc;
+  if ((rc = geometry(who, B, L, layer_idx, N, P, ARCQ_KV_INT4)) || (rc = dtype_ok(who, dtype)) || (rc = heads_ok(who, Nq, N)) ||   // (no format: as above)
+      (rc = pages_ok(who, nnz, P)) || (rc = batch_heads_ok(who, B, Nq)) || (rc = group_ok(who, Nq, N, 16)))
+    return rc;
+  if (B == 0) return ARCQ_OK;
+  if ((rc = none_null(who, {o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset})) ||       // (the scales are read: kv_param is needed)
+      (rc = aligned16(who, {o, q, kv_data}, "o, q and kv_data")) ||
+      (rc = aligned4(who, {kv_param, kv_indptr, kv_indices, last_page_offset, workspace}, "kv_param, the index tensors and the workspace")) ||
+      (rc = workspace_ok(who, workspace, workspace_bytes, arcq_kv_decode_gqa_workspace_bytes(B, Nq, N, nnz, P), "arcq_kv_decode_gqa_workspace_bytes")))
+    return rc;
+  KvDecodeArgs a{o, q, kv_data, kv_param, kv_indptr, kv_indices, last_page_offset, B, Nq, L, layer_idx, N, P, nnz, ARCQ_KV_FP8, dtype, workspace};
+  return kv_decode_gqa8(a, (hipStream_t)stream);
 }
 
 int arcq_kv_batch_prefill(void* o, const void* q, const int32_t* qo_indptr, const void* kv_data, const void* kv_param, const int32_t* kv_indptr,

@@ -15,7 +15,8 @@ reference's flow, ``PagedKVCacheI4`` holds the pages and builds the tables.  ``b
 of several query tokens per sequence over the int4 pages: chunked prefill, a second turn, speculative verification; ``batch_prefill_f16``
 (kvprefill.py) is the same over the 16-bit pages.
 ``batch_decode_gqa_i4`` (kvgqa.py) is ``batch_decode_i4`` for GQA models, 1 <= g <= 16, on the matrix cores, and ``batch_decode_gqa_f16``
-(kvgqa.py) is ``batch_decode_f16`` for them.
+(kvgqa.py) is ``batch_decode_f16`` for them.  ``append_kv_quantize_fp8`` / ``init_kv_quantize_fp8`` / ``batch_decode_gqa_fp8`` (kvfp8.py) are
+the FP8 (e4m3) cache: torch.float8_e4m3fn pages [pages, L, 2, N, P, 128] with (scale, 0) pairs, ``quantize_fp8`` its rule in torch.
 
 This module is a ctypes mirror only.  Validation follows the mirror's order (``agemm._need`` ...): dtype / rank / contiguity, then the size
 relations, and LAST where everything lives.  The CONTENTS of the index tensors are the caller's contract, as in the reference.
@@ -29,6 +30,7 @@ from ._kvargs import _DTYPES, HEAD_DIM, _cache, _dtype_of, _heads, _params, _row
 from .agemm import _need, _on, _same_device, _stream
 # extensions in modules of their own, as kvstep is: decode attention for GQA models on the matrix cores, causal prefill attention over the
 # int4 pages (several query tokens per sequence), and rotary position embedding at write time, fused into the quantising writers
+from .kvfp8 import append_kv_quantize_fp8, batch_decode_gqa_fp8, init_kv_quantize_fp8, quantize_fp8  # noqa: F401
 from .kvgqa import batch_decode_gqa_f16, batch_decode_gqa_i4  # noqa: F401
 from .kvprefill import batch_prefill_f16, batch_prefill_i4  # noqa: F401
 from .kvrope import rope_append_kv_quantize_i4, rope_init_kv_quantize_i4, rope_qk_, rope_tables  # noqa: F401

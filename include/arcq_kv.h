@@ -37,6 +37,7 @@ extern "C" {
 
 #define ARCQ_KV_INT4 0  /* cache format: 4-bit codes + (scale, zero) */
 #define ARCQ_KV_16BIT 1 /* cache format: 16-bit values (the reference's `_f16` trio) */
+#define ARCQ_KV_FP8 2   /* the FP8 cache below: internal to its own entry points, NOT a `format` any entry point accepts */
 #define ARCQ_KV_F16 0   /* element dtype of q / o / k / v (and of an ARCQ_KV_16BIT cache): float16, the reference's */
 #define ARCQ_KV_BF16 1  /* bfloat16, the harness's */
 
@@ -104,6 +105,42 @@ int arcq_kv_batch_decode_gqa_16bit(void *o, const void *q, const void *kv_data, 
                                    const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L,
                                    int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int dtype, void *workspace,
                                    int64_t workspace_bytes, void *stream);
+
+/* ---- The FP8 cache (what vLLM calls kv_cache_dtype=fp8): three entry points of its own, none of which takes a `format`; the entry points
+ * above keep refusing every format but ARCQ_KV_INT4 / ARCQ_KV_16BIT.
+ *   kv_data   OCP e4m3 (e4m3fn) bytes [pages, L, 2, N, P, 128]: a row is 128 bytes, one cache line
+ *   kv_param  fp16 [pages, L, 2, N, P, 2] = (scale, 0): value = float(code) * float(scale); the second element is written as zero and
+ *             never read.  Tables and K / V placement are those of the other formats.
+ * QUANTISER, per row of 128 values, fp32 arithmetic, IEEE division, both conversions round to nearest even (subnormal codes included):
+ *     amax = max |x|;   scale = fp16(max(amax / 448, 2^-14));   code = e4m3(clamp(x / float(scale), -448, 448))
+ * The clamp is part of the rule: a scale rounded DOWN to fp16 can leave a quotient a hair above 448.  Inputs are finite.  Codes and scales
+ * are byte for byte what kvfp8.quantize_fp8 (that formula in torch) gives on a CPU tensor.  A row whose amax / 448 overflows fp16 (bf16
+ * inputs beyond 448 * 65504) gets scale = inf and codes +-0: such a row is outside the format. */
+
+/* arcq_kv_append_quantize for the FP8 cache, ONE launch: k, v = `dtype` [B, N, 128]; token b is quantised by the rule above and written at
+ * position seq_len(b) - 1.  The checks are arcq_kv_append_quantize's, in its order.  B == 0 returns ARCQ_OK without a launch. */
+int arcq_kv_fp8_append_quantize(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                                const int32_t *last_page_offset, const void *k, const void *v, int64_t B, int64_t L, int64_t layer_idx,
+                                int64_t N, int64_t P, int dtype, void *stream);
+
+/* arcq_kv_init_quantize for the FP8 cache: k, v = `dtype` [ntok, N, 128]; tokens seqlen_indptr[b] .. seqlen_indptr[b+1] become the LAST
+ * positions of sequence b.  B == 0 or ntok == 0 returns ARCQ_OK without a launch. */
+int arcq_kv_fp8_init_quantize(void *kv_data, void *kv_param, const int32_t *kv_indptr, const int32_t *kv_indices,
+                              const int32_t *last_page_offset, const void *k, const void *v, const int32_t *seqlen_indptr, int64_t ntok,
+                              int64_t B, int64_t L, int64_t layer_idx, int64_t N, int64_t P, int dtype, void *stream);
+
+/* Decode attention over the FP8 cache for 1 <= g = Nq / N <= 16 (g = 1: MHA): arcq_kv_batch_decode_gqa_16bit's arguments, work split,
+ * slices and workspace (arcq_kv_decode_gqa_workspace_bytes); kv_param IS read (the scales) and must not be NULL.  NUMERICS: the codes
+ * are converted exactly to `dtype` in registers and multiplied on the 16-bit matrix cores with fp32 accumulation; K's row scale
+ * multiplies the fp32 score (together with 128^-1/2), V's row scale the fp32 weight, which is then rounded ONCE to `dtype`; the row sum is
+ * over the unrounded, unscaled weights; one rounding of the result.  Neither q nor the weights are rounded to 8 bits.  The rounded
+ * weights of a head are taken relative to the largest scaled weight (an exact power-of-two renormalisation), so a small scale does not
+ * push fp16 weights into the subnormal range.  A sequence without positions gives zeros.  g > 16: ARCQ_ERR_UNSUPPORTED before any launch.
+ * No state, no host read of a device table: the call can be captured into a HIP graph. */
+int arcq_kv_batch_decode_gqa_fp8(void *o, const void *q, const void *kv_data, const void *kv_param, const int32_t *kv_indptr,
+                                 const int32_t *kv_indices, const int32_t *last_page_offset, int64_t B, int64_t Nq, int64_t L,
+                                 int64_t layer_idx, int64_t N, int64_t P, int64_t nnz, int dtype, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
 
 /* Causal prefill attention over the pages: several query tokens per sequence, each attending over everything the cache holds up to and
  * including its own position.  o, q = `dtype` [ntok, Nq, 128], contiguous, Nq = g * N.  qo_indptr = int32 [B + 1] on the device,
